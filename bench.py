@@ -1,18 +1,25 @@
 """Benchmark: BASELINE config 2 — 4096 concurrent boards per GPU, pure env
-step / legal_actions / score HIP kernels, bit-exact vs the CPU engine — with
-config 3 (and, at N > 1, config 4's exchange) measured in the same run.
+step / legal_actions / score HIP kernels, bit-exact vs the CPU engine — and,
+with --full, config 3 (and, at N > 1, config 4's exchange) measured in the
+same run.
 
 Headline (config 2): one bench step = `--launches-per-step` (256) batched
 passes of the env hot path over 4096 boards, each a single hz_play launch:
 HarmoniesGameState() on every board (CPython-exact seeding and opening
 draws), then play to the end of every game (legal mask -> build-defined
 splitmix rule pick -> apply_move, incl. chance draws and final scoring).
-The final states of the first and the last timed launch are compared with
-the C oracle board by board.
 Boards are seeded by their global id (rank * 4096 + b), so N GPUs run N
 independent shards (weak scaling, no data-path collective).
 
-`selfplay` sub-object (config 3, profile_self_play.py's loop batched): 4096
+A plain run sets up, warms up, times the steps, writes the last timed step's
+outputs if --dump-outputs DIR is given, and prints the headline fields.
+Everything else is --full's: the final states of the first and the last
+timed launch compared with the C oracle board by board, the kernel's
+roofline, the chance-ahead-off comparison, the api_path / api_caller /
+auto_reset legs, the encoder roofline, cpu_baseline and the selfplay
+sub-object.
+
+`selfplay` sub-object (--full; config 3, profile_self_play.py's loop batched): 4096
 boards x 200 MCTS simulations per move with the default 128-filter x
 8-block network in fp32, 2 warm-up + 3 timed moves; at N > 1 the timed
 moves' (s, pi, player) records are all-gathered over RCCL (config 4's
@@ -23,7 +30,7 @@ Other configs: --config 3 (self-play moves only, or --full-game), --config 4
 buffer), --config 5 (the full training loop).
 
 Prints one JSON line (rank 0).  Usage:
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--boards 4096]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--boards 4096] [--full] [--dump-outputs DIR]
   torchrun --nproc-per-node N bench.py --gpus N ...
 """
 import argparse
@@ -80,6 +87,14 @@ def parse():
                     help="initialise torch.distributed (RCCL) even at one rank, so the N > 1 collectives run")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="config 2: besides the headline, run every other leg (kernel roofline, chance-ahead off, "
+                         "api_path, api_caller, auto_reset, encoder roofline, the C-oracle parity guard, the selfplay "
+                         "sub-object, cpu_baseline; each has its own --no-* switch).  Without it a run sets up, "
+                         "warms up, times the steps and prints the headline fields only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="config 2: after the timed steps, write what the last timed step returned (its launches' "
+                         "per-board game and env-step counters and the boards' final states) as DIR/<name>.npy")
     ap.add_argument("--boards", type=int, default=4096)
     ap.add_argument("--pipeline", type=int, choices=(1, 2), default=2,
                     help="config 2: hz_play's pipeline (1 = chance-ahead k_rollout, 2 = k_play2's thirteen stages; "
@@ -139,6 +154,10 @@ def parse():
     args = ap.parse_args()
     if args.stub and args.config != 4:
         ap.error("--stub applies to --config 4 only (the other configs time the network)")
+    if args.dump_outputs and args.config != 2:
+        ap.error("--dump-outputs applies to the default config (2) only")
+    if args.config == 2 and (args.steps < 1 or args.launches_per_step < 1):
+        ap.error("--steps and --launches-per-step must be at least 1")
     return args
 
 
@@ -1297,21 +1316,25 @@ def main():
     elapsed = time.perf_counter() - t0
     last_ep = launches[0] - 1
     last_state = env.export_state()
-    # the dominant kernel's average launch duration: HIP events on the env's
-    # stream around a block of K back-to-back launches (no markers between
-    # them), outside the timed region; rocprofv3's per-dispatch average for
-    # k_rollout (profiles/<round>/stats) is the figure it must agree with
-    K = min(T, 512)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    env._sync_stream()
-    gp = [ctypes.c_void_p(games.data_ptr())] * K
-    spp = [ctypes.c_void_p(steps.data_ptr())] * K
-    ev0.record(stream)
-    for i in range(K):
-        fast_launch(i)
-    ev1.record(stream)
-    torch.cuda.synchronize(dev)
-    kern_ms = ev0.elapsed_time(ev1) / K
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, games_t[T - L:], steps_t[T - L:], last_state)
+    # --full: the dominant kernel's average launch duration: HIP events on the
+    # env's stream around a block of K back-to-back launches (no markers
+    # between them), outside the timed region; rocprofv3's per-dispatch average
+    # for k_rollout (profiles/<round>/stats) is the figure it must agree with
+    K = min(T, 512) if args.full else 0
+    kern_ms = None
+    if args.full:
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        env._sync_stream()
+        gp = [ctypes.c_void_p(games.data_ptr())] * K
+        spp = [ctypes.c_void_p(steps.data_ptr())] * K
+        ev0.record(stream)
+        for i in range(K):
+            fast_launch(i)
+        ev1.record(stream)
+        torch.cuda.synchronize(dev)
+        kern_ms = ev0.elapsed_time(ev1) / K
     env.epoch += 1  # (games were started outside env.rollout)
     env.check_errors()  # no pipeline wave gave up waiting in any launch so far (else NativeError)
 
@@ -1327,6 +1350,16 @@ def main():
     value = env_steps_all / elapsed
     games_per_s = games_all / elapsed
     ms_per_step = elapsed * 1000.0 / args.steps
+
+    if not args.full:
+        # a plain run: the headline alone (every other leg, the C-oracle
+        # parity guard included, is --full's)
+        if rank == 0:
+            print(json.dumps(headline(args, world, value, games_per_s, ms_per_step, timed_steps, timed_games)))
+        env.close()
+        if dd():
+            dist.destroy_process_group()
+        return
 
     # roofline of the dominant kernel (hz_play = k_rollout with reset, or
     # k_play2), per launch
@@ -1394,34 +1427,11 @@ def main():
 
     if rank == 0:
         cpu = None if args.no_cpu_baseline or world > 1 else cpu_baseline(n, args.cpu_seconds)
-        out = {
-            "metric": "self-play env-steps/sec + games/sec @4096 boards, 1/2/4/8 GPUs; bit-exact vs CPU",
-            "value": value,
-            "unit": "env-steps/s",
-            "headline_basis": "value = config 2: rule-driven env play (reset, legal mask, step, chance draws, "
-                              "final scoring) on 4096 boards/GPU, NO MCTS and no network; the self-play "
-                              "(config 3: 200-sim MCTS + network per move) figures are selfplay_env_steps_per_s "
-                              "and selfplay_games_per_s",
+        out = headline(args, world, value, games_per_s, ms_per_step, timed_steps, timed_games)
+        out.update({
             "selfplay_env_steps_per_s": (sp or {}).get("env_steps_per_s"),
             "selfplay_games_per_s": (sp or {}).get("games_per_s"),
             "selfplay_steady_games_per_s": (sp or {}).get("steady_games_per_s"),
-            "env_games_per_s": games_per_s,
-            "env_games_basis": "rule-driven env games (config 2, no MCTS) per second; the self-play games/s "
-                               "is selfplay.games_per_s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": "synthetic: CPython-seeded games, seeds = global board id, build-defined splitmix rule policy",
-            "config": {"workload": f"config2: 4096 concurrent boards/GPU, reset + rule-driven play to game end "
-                                   f"(legal mask, step, chance draws, final scoring); one step = {L} hz_play "
-                                   f"launches of 4096 boards",
-                       "boards_per_gpu": n, "launches_per_step": L, "env_steps_per_step": timed_steps / args.steps,
-                       "games_per_step": timed_games / args.steps, "parallelism": f"shard{world}"},
             "roofline": {"bound": "latency (per-lane chains)", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "traffic_gbs": tr["traffic_gbs"] if tr else None,
@@ -1451,7 +1461,7 @@ def main():
             "cpu_baseline": cpu,
             "parity": parity,
             "selfplay": sp,
-        }
+        })
         out["api_path"] = api
         out["api_caller"] = caller
         out["auto_reset"] = auto
@@ -1460,6 +1470,60 @@ def main():
         env.close()
     if dd():
         dist.destroy_process_group()
+
+
+def headline(args, world, value, games_per_s, ms_per_step, timed_steps, timed_games):
+    """The result line's headline fields (config 2), the whole line of a run
+    without --full."""
+    n, L = args.boards, args.launches_per_step
+    return {
+        "metric": "self-play env-steps/sec + games/sec @4096 boards, 1/2/4/8 GPUs; bit-exact vs CPU",
+        "value": value,
+        "unit": "env-steps/s",
+        "headline_basis": "value = config 2: rule-driven env play (reset, legal mask, step, chance draws, "
+                          "final scoring) on 4096 boards/GPU, NO MCTS and no network; the self-play "
+                          "(config 3: 200-sim MCTS + network per move) figures are selfplay_env_steps_per_s "
+                          "and selfplay_games_per_s (--full)",
+        "env_games_per_s": games_per_s,
+        "env_games_basis": "rule-driven env games (config 2, no MCTS) per second; the self-play games/s "
+                           "is selfplay.games_per_s (--full)",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic: CPython-seeded games, seeds = global board id, build-defined splitmix rule policy",
+        "full": bool(args.full),
+        "config": {"workload": f"config2: 4096 concurrent boards/GPU, reset + rule-driven play to game end "
+                               f"(legal mask, step, chance draws, final scoring); one step = {L} hz_play "
+                               f"launches of 4096 boards",
+                   "boards_per_gpu": n, "launches_per_step": L, "env_steps_per_step": timed_steps / args.steps,
+                   "games_per_step": timed_games / args.steps, "parallelism": f"shard{world}"},
+    }
+
+
+def dump_outputs(folder, games_l, steps_l, state):
+    """--dump-outputs: what the last timed step's hz_play launches returned to
+    their caller, as .npy files: the per-board counters of each of its
+    launches (games ended, env steps played; int32 [L, n], written as
+    float32, exact below 2^24) and the boards' final state words after its
+    last launch (int64 [6, n], written as float64 [6, n, 2]: the low and the
+    high 32 bits of every word, both exact).  8.4 MB at the defaults; of a
+    larger run the last launches and the first boards are kept (at most 4M
+    counters per file and 256K boards' states: under 60 MB in all)."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    keep = max(1, (4 << 20) // max(1, games_l.shape[1]))
+    games_l, steps_l = games_l[-keep:, :4 << 20], steps_l[-keep:, :4 << 20]
+    state = state[:, :1 << 18]
+    np.save(os.path.join(folder, "games_done.npy"), games_l.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(folder, "steps_done.npy"), steps_l.cpu().numpy().astype(np.float32))
+    w = state.cpu().numpy().view(np.uint64)
+    halves = np.stack([w & np.uint64(0xFFFFFFFF), w >> np.uint64(32)], axis=-1)
+    np.save(os.path.join(folder, "final_state_words.npy"), halves.astype(np.float64))
 
 
 def encoder_roofline(dev, n, seed_base):

@@ -14,7 +14,7 @@ OUT=$REPO/gpurun_out/$R
 mkdir -p "$OUT/stats"
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- \
-  python3 "$REPO/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-off-compare --sp-cpu-seconds 0 \
+  python3 "$REPO/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-off-compare --sp-cpu-seconds 0 \
   > "$OUT/stats/bench_under_prof.json"
 k=0
 for C in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU" \
@@ -22,7 +22,7 @@ for C in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ
          "FETCH_SIZE" "WRITE_SIZE"; do
   mkdir -p "$OUT/pmc/p$k"
   timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d "$OUT/pmc/p$k" -o run -- \
-    python3 "$REPO/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-off-compare --no-selfplay \
+    python3 "$REPO/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-off-compare --no-selfplay \
     > "$OUT/pmc/p$k/bench.json"
   k=$((k+1))
 done

@@ -24,6 +24,14 @@ def test_stub_needs_config4():
     assert r.returncode != 0 and "config 4" in r.stderr
 
 
+def test_dump_outputs_needs_the_default_config_and_a_timed_step(tmp_path):
+    r = _run(["--config", "3", "--dump-outputs", str(tmp_path / "d")])
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr
+    r = _run(["--steps", "0"])
+    assert r.returncode != 0 and "at least 1" in r.stderr
+    assert not (tmp_path / "d").exists()
+
+
 def test_spawn_refuses_more_gpus_than_visible():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK",
                                                             "HZ_BENCH_REHEARSAL")}

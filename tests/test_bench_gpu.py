@@ -48,8 +48,8 @@ def test_bench_gpus_n_spawns_its_ranks():
     env = dict(os.environ, HZ_BENCH_REHEARSAL="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = _single(["--gpus", "2", "--steps", "2", "--warmup", "1", "--launches-per-step", "4", "--no-off-compare",
-                 "--no-selfplay"], env=env)
+    r = _single(["--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--launches-per-step", "4",
+                 "--no-off-compare", "--no-selfplay"], env=env)
     d = _last_json(r.stdout)
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "shard2"
     assert "8192/8192 boards bit-exact vs C oracle" in d["parity"]
@@ -61,7 +61,7 @@ def test_bench_rccl_one_rank():
     collectives run on device tensors: the parity all-reduces, and the
     complete games' records all-gathered (all_gather_into_tensor) into the
     replay buffer; with one rank the gathered records are the rank's own."""
-    r = _single(["--dist", "--steps", "2", "--warmup", "1", "--launches-per-step", "4", "--no-off-compare",
+    r = _single(["--dist", "--full", "--steps", "2", "--warmup", "1", "--launches-per-step", "4", "--no-off-compare",
                  "--no-cpu-baseline", "--sp-cpu-seconds", "0"] + SMALL_SP)
     assert "backend nccl" in r.stderr, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -87,8 +87,8 @@ def test_config4_rccl_one_rank_equals_plain(tmp_path):
 
 
 def test_bench_two_ranks_rehearsal():
-    r = _torchrun(["--steps", "2", "--warmup", "1", "--launches-per-step", "8", "--no-off-compare"] + SMALL_SP,
-                  29517)
+    r = _torchrun(["--full", "--steps", "2", "--warmup", "1", "--launches-per-step", "8", "--no-off-compare"]
+                  + SMALL_SP, 29517)
     d = _last_json(r.stdout)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert d["config"]["parallelism"] == "shard2"
@@ -107,7 +107,7 @@ def test_bench_two_ranks_rehearsal():
 
 
 def test_bench_single_rank_contract():
-    r = _single(["--steps", "2", "--warmup", "1", "--launches-per-step", "16", "--cpu-seconds", "1",
+    r = _single(["--full", "--steps", "2", "--warmup", "1", "--launches-per-step", "16", "--cpu-seconds", "1",
                  "--sp-cpu-seconds", "1"] + SMALL_SP)
     d = _last_json(r.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -148,6 +148,45 @@ def test_bench_single_rank_contract():
     assert "load_checkpoint" in sp["network"]
     for k in ("value", "unit", "cores", "kind", "sample", "nn_cpu_ms_per_eval"):
         assert k in sp["cpu_baseline"], k
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """Without --full the line holds the headline fields and none of the
+    other legs; --steps sets the number of timed steps (the dumped counters
+    are the last step's launches); --dump-outputs writes the last timed
+    step's outputs, which equal the C oracle's games of the same episodes
+    and are identical from run to run."""
+    import numpy as np
+    import oracle
+    from hzamd.state import unpack_ref
+    L, steps, warmup, n = 16, 3, 1, 4096
+    args = ["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--launches-per-step", str(L)]
+    d = _last_json(_single(args + ["--dump-outputs", str(tmp_path / "a")]).stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup",
+              "config"):
+        assert k in d, k
+    for k in ("selfplay", "cpu_baseline", "parity", "roofline", "api_path", "api_caller", "auto_reset",
+              "encoder_roofline", "chance_ahead"):
+        assert k not in d, k
+    assert d["unit"] == "env-steps/s" and d["steps"] == steps and d["full"] is False and d["ms_per_step"] > 0
+    assert d["config"]["games_per_step"] == L * n
+    assert abs(d["value"] - d["config"]["env_steps_per_step"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("games_done", "steps_done", "final_state_words")}
+    assert a["games_done"].dtype == a["steps_done"].dtype == np.float32 and a["final_state_words"].dtype == np.float64
+    assert a["games_done"].shape == a["steps_done"].shape == (L, n) and a["final_state_words"].shape == (6, n, 2)
+    assert (a["games_done"] == 1).all()
+    # launch k plays every board's episode k: the last timed launch is episode (warmup + steps) * L - 1
+    last = (warmup + steps) * L - 1
+    _, finals, plies, _ = oracle.play_rule_games(n, 0, nthreads=8, episode=last)
+    assert (a["steps_done"][-1] == plies).all()
+    _, _, plies0, _ = oracle.play_rule_games(n, 0, nthreads=8, episode=last - L + 1)
+    assert (a["steps_done"][0] == plies0).all()
+    w = a["final_state_words"].astype(np.uint64)
+    words = (w[..., 0] | (w[..., 1] << np.uint64(32))).view(np.int64)
+    assert all((unpack_ref(words[:, b]) == finals[b]).all() for b in range(n))
+    _single(args + ["--dump-outputs", str(tmp_path / "b")])
+    for k, v in a.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{k}.npy")), k
 
 
 CFG4 = ["--config", "4", "--boards", "48", "--sims", "6", "--iterations", "2", "--warmup", "2"]

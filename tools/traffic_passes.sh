@@ -10,7 +10,7 @@ k=0
 for C in FETCH_SIZE WRITE_SIZE; do
   mkdir -p "$REPO/$OUT/p$k"
   timeout -s KILL 120 rocprofv3 --pmc $C --output-format csv -d "$REPO/$OUT/p$k" -o run -- \
-    python3 "$REPO/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-off-compare --no-selfplay \
+    python3 "$REPO/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-off-compare --no-selfplay \
     > "$REPO/$OUT/p$k/bench.json"
   k=$((k+1))
 done
