@@ -13,8 +13,10 @@
 #include "../../include/hz_abi.h"
 #include "hz_device.hpp"
 #include "hz_encode.hpp"
+#include "hz_host.hpp"
 
 using namespace hz;
+using namespace hz_host;
 
 // pipeline-2 hand-offs (k_play2), per board, rows of nrow
 struct P2Draw {   // a draw stage's output: the pile script so far
@@ -31,7 +33,11 @@ struct P2Mid {    // a play stage's end state, for the next play stage
   int32_t *i;     // [3][nrow] script entries used, plies played, stream cursor if fell (else -1)
 };
 
+// Created by value-initialising new: every field starts zero.  The device
+// buffers belong to three owners by lifetime (bufs: hz_env_create; p2_bufs:
+// alloc_p2; ar_bufs: alloc_ar), each freed by its release().
 struct hz_env {
+  DevBufs bufs, p2_bufs, ar_bufs;
   int32_t n;
   uint64_t seed_base;
   hipStream_t stream;
@@ -83,7 +89,7 @@ struct hz_env {
   uint32_t *pw_words;        // [kPlyWin][nrow]
   int32_t *pw_tag;           // [nrow] cursor the words start at (-1: none)
   int32_t *pw_ep;            // [nrow] stream epoch of the words
-  int32_t mt_epoch;
+  uint32_t mt_epoch;         // moved by streams_touched alone
   // pipeline 2 (hz_env_set_pipeline(e, 2); see k_play2): every board's game
   // spread over thirteen consecutive hz_play calls, one stage per call
   int pipeline;              // 1: chance-ahead (k_rollout's roles), 2: k_play2
@@ -2564,11 +2570,6 @@ __global__ void __launch_bounds__(kBlock) k_mt_import(int32_t *__restrict__ pos,
   pos[b] = index[b] | (kMT << 16);  // CPython states are fully twisted
 }
 
-inline int launch_err() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
-
 }  // namespace
 
 // ======================================================================= ABI
@@ -2608,11 +2609,14 @@ __global__ void __launch_bounds__(64) k_mt_materialize_ar(uint32_t *__restrict__
   if (lane == 0) mt_src[b] = -1;
 }
 
-static PlyWin ply_win(hz_env *e) { return PlyWin{e->pw_words, e->pw_tag, e->pw_ep, (long)e->nrow, e->mt_epoch}; }
+// (the device side keeps the epoch as int32: only ever compared for equality)
+static PlyWin ply_win(hz_env *e) {
+  return PlyWin{e->pw_words, e->pw_tag, e->pw_ep, (long)e->nrow, (int32_t)e->mt_epoch};
+}
 
 static int materialize(hz_env *e) {
   if (!e->lazy) return 0;
-  e->mt_epoch++;  // streams rewritten (PlyWin's saved words are stale)
+  streams_touched(e);  // streams rewritten (PlyWin's saved words are stale)
   if (e->ar_mt)
     hipLaunchKernelGGL(k_mt_materialize_ar, dim3(e->n), dim3(64), 0, e->stream, e->mt, e->ar_mt, e->mt_src, e->n);
   hipLaunchKernelGGL(k_mt_materialize, dim3(e->n), dim3(64), 0, e->stream, e->mt, e->ahead_mt[0], e->ahead_mt[1],
@@ -2629,44 +2633,6 @@ static int materialize(hz_env *e) {
 
 // ---------------------------------------------------------- pipeline 2 host
 static_assert(sizeof(((hz_env *)0)->p2_s) / sizeof(uint32_t *) == kP2Stream, "slot ring");
-static void free_p2(hz_env *e) {
-  auto f = [](auto *&p) {
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
-  };
-  for (int k = 0; k < kP2Stream; k++) {
-    f(e->p2_s[k]);
-    f(e->p2_s_tag[k]);
-    f(e->p2_s_cur[k]);
-  }
-  auto fd = [&](P2Draw &d) {
-    f(d.tag);
-    f(d.k);
-    f(d.q);
-    f(d.bag);
-    f(d.c);
-  };
-  for (int k = 0; k < 3; k++) fd(e->p2_x[k][0]), fd(e->p2_x[k][1]);
-  for (int k = 0; k < kP2Ring; k++) fd(e->p2_pl[k]);
-  for (int k = 0; k < kP2Play - 1; k++)
-    for (int j = 0; j < 2; j++) {
-      P2Mid &m = e->p2_m[k][j];
-      f(m.tag);
-      f(m.st);
-      f(m.q);
-      f(m.i);
-    }
-  for (int k = 0; k < kP2Ring; k++) {
-    f(e->p2_h[k]);
-    f(e->p2_h_tag[k]);
-  }
-  for (int k = 0; k < 2; k++) {
-    f(e->p2_p1h[k]);
-    f(e->p2_p2h[k]);
-    f(e->p2_p3h[k]);
-    f(e->p2_ep[k]);
-  }
-}
 
 // every hand-off tag to "none" (a tag names the episode its slot holds, and a
 // slot's contents depend only on (board, episode), so this is never needed
@@ -2690,28 +2656,41 @@ static int p2_clear_tags(hz_env *e) {
 static int alloc_p2(hz_env *e) {
   if (e->p2_s[0]) return 0;
   const size_t nr = e->nrow;
-  auto m = [](auto **p, size_t bytes) { return hipMalloc((void **)p, bytes) == hipSuccess; };
-  bool ok = true;
-  for (int k = 0; ok && k < kP2Stream; k++)
-    ok = m(&e->p2_s[k], nr * kMT * 4) && m(&e->p2_s_tag[k], nr * 4) &&
-         m(&e->p2_s_cur[k], (kAheadDraws + 1) * nr * 4);
+  DevBufs &o = e->p2_bufs;  // (a request after a failed one does nothing: one check at the end)
+  for (int k = 0; k < kP2Stream; k++) {
+    o.get(e->p2_s[k], nr * kMT * 4);
+    o.get(e->p2_s_tag[k], nr * 4);
+    o.get(e->p2_s_cur[k], (kAheadDraws + 1) * nr * 4);
+  }
   auto md = [&](P2Draw &d) {
-    return m(&d.tag, nr * 4) && m(&d.k, nr * 4) && m(&d.q, kAheadWords * nr * 8) && m(&d.bag, nr * 8) &&
-           m(&d.c, nr * 4);
+    o.get(d.tag, nr * 4);
+    o.get(d.k, nr * 4);
+    o.get(d.q, kAheadWords * nr * 8);
+    o.get(d.bag, nr * 8);
+    o.get(d.c, nr * 4);
   };
-  for (int k = 0; ok && k < 3; k++) ok = md(e->p2_x[k][0]) && md(e->p2_x[k][1]);
-  for (int k = 0; ok && k < kP2Ring; k++)
-    ok = md(e->p2_pl[k]) && m(&e->p2_h[k], kRulePlies * nr * 4) && m(&e->p2_h_tag[k], nr * 4);
-  for (int k = 0; ok && k < kP2Play - 1; k++)
-    for (int j = 0; ok && j < 2; j++) {
+  for (int k = 0; k < 3; k++) md(e->p2_x[k][0]), md(e->p2_x[k][1]);
+  for (int k = 0; k < kP2Ring; k++) {
+    md(e->p2_pl[k]);
+    o.get(e->p2_h[k], kRulePlies * nr * 4);
+    o.get(e->p2_h_tag[k], nr * 4);
+  }
+  for (int k = 0; k < kP2Play - 1; k++)
+    for (int j = 0; j < 2; j++) {
       P2Mid &mm = e->p2_m[k][j];
-      ok = m(&mm.tag, nr * 4) && m(&mm.st, 6 * nr * 8) && m(&mm.q, 4 * nr * 8) && m(&mm.i, 3 * nr * 4);
+      o.get(mm.tag, nr * 4);
+      o.get(mm.st, 6 * nr * 8);
+      o.get(mm.q, 4 * nr * 8);
+      o.get(mm.i, 3 * nr * 4);
     }
-  for (int k = 0; ok && k < 2; k++)
-    ok = m(&e->p2_p1h[k], nr * 4) && m(&e->p2_p2h[k], 3 * nr * 4) && m(&e->p2_p3h[k], 3 * nr * 4) &&
-         m(&e->p2_ep[k], nr * 4);
-  if (!ok || p2_clear_tags(e)) {
-    free_p2(e);
+  for (int k = 0; k < 2; k++) {
+    o.get(e->p2_p1h[k], nr * 4);
+    o.get(e->p2_p2h[k], 3 * nr * 4);
+    o.get(e->p2_p3h[k], 3 * nr * 4);
+    o.get(e->p2_ep[k], nr * 4);
+  }
+  if (!o.ok || p2_clear_tags(e)) {
+    o.release();
     return 1;
   }
   e->primed2 = 0;
@@ -2724,7 +2703,7 @@ static int alloc_p2(hz_env *e) {
 // hashes in rings of kP2Ring (read by play stage st st + 1 calls later).  Every slot written by call c is read by call c + 1 or later,
 // so launch order on the stream is the only synchronisation.
 static int launch_play2(hz_env *e, int32_t max_plies, int32_t *games_done, int32_t *steps_done) {
-  if (e) e->mt_epoch++;  // (may move or rewrite streams: PlyWin)
+  streams_touched(e);  // (may move or rewrite streams: PlyWin; hz_play checked e)
   if (alloc_p2(e)) return 1;
   const int c = e->calls2, r = c & 1, w = r ^ 1;
   if (!e->primed2) {
@@ -2798,95 +2777,60 @@ extern "C" {
 hz_env *hz_env_create(int32_t n_boards, uint64_t seed_base, void *stream) {
   if (n_boards <= 0) return nullptr;
   if (install_comp_table()) return nullptr;  // scoring's component table (hz_device.hpp)
-  hz_env *e = (hz_env *)calloc(1, sizeof(hz_env));
+  // k_reset / k_rollout stage 64 boards' MT words in 158 KiB of LDS
+  if (lds_opt_in<k_reset>(kResetLds) || lds_opt_in<k_rollout<false, false>>(kResetLds) ||
+      lds_opt_in<k_rollout<false, true>>(kResetLds) || lds_opt_in<k_rollout<true, false>>(kResetLds) ||
+      lds_opt_in<k_rollout<true, true>>(kResetLds) || lds_opt_in<k_play2>(kResetLds))
+    return nullptr;
+  hz_env *e = new (std::nothrow) hz_env();
   if (!e) return nullptr;
   e->n = n_boards;
   e->seed_base = seed_base;
   e->stream = (hipStream_t)stream;
-  size_t n = (size_t)n_boards;
-  // k_reset / k_rollout stage 64 boards' MT words in 158 KiB of LDS
-  if (hipFuncSetAttribute((const void *)k_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kResetLds) !=
-          hipSuccess ||
-      hipFuncSetAttribute((const void *)k_rollout<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)kResetLds) != hipSuccess ||
-      hipFuncSetAttribute((const void *)k_rollout<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)kResetLds) != hipSuccess ||
-      hipFuncSetAttribute((const void *)k_rollout<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)kResetLds) != hipSuccess ||
-      hipFuncSetAttribute((const void *)k_rollout<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)kResetLds) != hipSuccess ||
-      hipFuncSetAttribute((const void *)k_play2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kResetLds) !=
-          hipSuccess) {
-    free(e);
-    return nullptr;
+  const size_t n = (size_t)n_boards, nr = (n + kBlock - 1) / kBlock * kBlock, i32 = sizeof(int32_t);
+  e->nrow = nr;
+  DevBufs &o = e->bufs;  // (a request after a failed one does nothing: one check at the end)
+  o.get(e->state, n * 6 * sizeof(uint64_t), 0);
+  o.get(e->mt, n * 624 * sizeof(uint32_t));
+  o.get(e->pos, n * i32, 0);
+  o.get(e->ply, n * i32, 0);
+  o.get(e->episode, n * i32, 0);
+  o.get(e->seed, n * sizeof(uint64_t), 0);
+  o.get(e->mt_src, n * i32, 0xff);
+  for (int k = 0; k < 2; k++) {
+    o.get(e->ahead_mt[k], n * kMT * sizeof(uint32_t));
+    o.get(e->ahead_tag[k], n * i32, 0xff);
+    o.get(e->ahead_pile[k], n * kAheadWords * sizeof(uint64_t));
+    o.get(e->ahead_cur[k], n * (kAheadDraws + 1) * i32);
+    o.get(e->ahead_rule[k], nr * kRulePlies * sizeof(uint32_t));
+    o.get(e->ep_final[k], n * i32);
   }
-  bool ok = hipMalloc(&e->state, n * 6 * sizeof(uint64_t)) == hipSuccess &&
-            hipMalloc(&e->mt, n * 624 * sizeof(uint32_t)) == hipSuccess &&
-            hipMalloc(&e->pos, n * sizeof(int32_t)) == hipSuccess &&
-            hipMalloc(&e->ply, n * sizeof(int32_t)) == hipSuccess &&
-            hipMalloc(&e->episode, n * sizeof(int32_t)) == hipSuccess &&
-            hipMalloc(&e->seed, n * sizeof(uint64_t)) == hipSuccess &&
-            hipMalloc(&e->mt_src, n * sizeof(int32_t)) == hipSuccess;
-  if (ok) {
-    ok = hipMemset(e->state, 0, n * 6 * sizeof(uint64_t)) == hipSuccess &&
-         hipMemset(e->pos, 0, n * sizeof(int32_t)) == hipSuccess &&
-         hipMemset(e->ply, 0, n * sizeof(int32_t)) == hipSuccess &&
-         hipMemset(e->episode, 0, n * sizeof(int32_t)) == hipSuccess &&
-         hipMemset(e->seed, 0, n * sizeof(uint64_t)) == hipSuccess &&
-         hipMemset(e->mt_src, 0xff, n * sizeof(int32_t)) == hipSuccess;
+  for (int k = 0; k < kRing; k++) {
+    o.get(e->ring_mt[k], nr * kMT * sizeof(uint32_t));
+    o.get(e->ring_tag[k], nr * i32, 0xff);
+    o.get(e->ring_pile[k], nr * 3 * sizeof(uint64_t));
+    o.get(e->ring_cur[k], nr * (kD1Draws + 1) * i32);
+    o.get(e->ring_k1[k], nr * i32);
   }
-  for (int k = 0; ok && k < 2; k++) {
-    ok = hipMalloc(&e->ahead_mt[k], n * kMT * sizeof(uint32_t)) == hipSuccess &&
-         hipMalloc(&e->ahead_tag[k], n * sizeof(int32_t)) == hipSuccess &&
-         hipMalloc(&e->ahead_pile[k], n * kAheadWords * sizeof(uint64_t)) == hipSuccess &&
-         hipMalloc(&e->ahead_cur[k], n * (kAheadDraws + 1) * sizeof(int32_t)) == hipSuccess &&
-         hipMalloc(&e->ahead_rule[k], (n + kBlock - 1) / kBlock * kBlock * kRulePlies * sizeof(uint32_t)) ==
-             hipSuccess &&
-         hipMalloc(&e->ep_final[k], n * sizeof(int32_t)) == hipSuccess &&
-         hipMemset(e->ahead_tag[k], 0xff, n * sizeof(int32_t)) == hipSuccess;
-  }
-  e->nrow = (n + kBlock - 1) / kBlock * kBlock;
-  for (int k = 0; ok && k < kRing; k++) {
-    size_t nr = e->nrow;
-    ok = hipMalloc(&e->ring_mt[k], nr * kMT * sizeof(uint32_t)) == hipSuccess &&
-         hipMalloc(&e->ring_tag[k], nr * sizeof(int32_t)) == hipSuccess &&
-         hipMemset(e->ring_tag[k], 0xff, nr * sizeof(int32_t)) == hipSuccess &&
-         hipMalloc(&e->ring_pile[k], nr * 3 * sizeof(uint64_t)) == hipSuccess &&
-         hipMalloc(&e->ring_cur[k], nr * (kD1Draws + 1) * sizeof(int32_t)) == hipSuccess &&
-         hipMalloc(&e->ring_k1[k], nr * sizeof(int32_t)) == hipSuccess;
-  }
-  ok = ok && hipDeviceSynchronize() == hipSuccess;
+  o.get(e->pw_words, nr * kPlyWin * sizeof(uint32_t));
+  o.get(e->pw_tag, nr * i32, 0xff);
+  o.get(e->pw_ep, nr * i32, 0);
+  o.get(e->wait_err_own, i32, 0);
   e->seed_ahead = kAheadDraws;
-  {
-    const char *av = getenv("HZ_AR_AHEAD");
-    e->ar_ahead = av && atoi(av) == 0 ? 0 : 1;
-  }
-  {  // hz_play's pipeline: 2 by default, HZ_PIPELINE=1 for the first (hz_env_set_pipeline)
-    const char *pv = getenv("HZ_PIPELINE");
-    e->pipeline = pv && atoi(pv) == 1 ? 1 : 2;
-    // HZ_P2_CUTS="a,b,c": pipeline 2's play stage boundaries (plies,
-    // increasing multiples of 4: whole turns; a stage that starts at player
-    // 1's turn plays single plies up to the next turn pair)
-    e->p2_cut[0] = 24;
-    e->p2_cut[1] = 40;
-    e->p2_cut[2] = 56;
-    const char *cv = getenv("HZ_P2_CUTS");
-    int c[3];
-    if (cv && sscanf(cv, "%d,%d,%d", &c[0], &c[1], &c[2]) == 3 && c[0] > 0 && c[1] > c[0] && c[2] > c[1] &&
-        c[0] % 4 == 0 && c[1] % 4 == 0 && c[2] % 4 == 0)
-      for (int k = 0; k < 3; k++) e->p2_cut[k] = c[k];
-  }
-  ok = ok && hipMalloc(&e->pw_words, e->nrow * kPlyWin * sizeof(uint32_t)) == hipSuccess &&
-       hipMalloc(&e->pw_tag, e->nrow * sizeof(int32_t)) == hipSuccess &&
-       hipMalloc(&e->pw_ep, e->nrow * sizeof(int32_t)) == hipSuccess &&
-       hipMemset(e->pw_tag, 0xff, e->nrow * sizeof(int32_t)) == hipSuccess &&
-       hipMemset(e->pw_ep, 0, e->nrow * sizeof(int32_t)) == hipSuccess;
+  e->ar_ahead = env_pick("HZ_AR_AHEAD", 0, 1);
+  // hz_play's pipeline: 2 by default, HZ_PIPELINE=1 for the first (hz_env_set_pipeline)
+  e->pipeline = env_pick("HZ_PIPELINE", 1, 2);
+  // HZ_P2_CUTS="a,b,c": pipeline 2's play stage boundaries (plies,
+  // increasing multiples of 4: whole turns; a stage that starts at player
+  // 1's turn plays single plies up to the next turn pair)
+  e->p2_cut[0] = 24;
+  e->p2_cut[1] = 40;
+  e->p2_cut[2] = 56;
+  env_cuts("HZ_P2_CUTS", e->p2_cut);
   e->mt_epoch = 1;
-  ok = ok && hipMalloc(&e->wait_err_own, sizeof(int32_t)) == hipSuccess &&
-       hipMemset(e->wait_err_own, 0, sizeof(int32_t)) == hipSuccess;
   e->wait_err = e->wait_err_own;
   e->spin_limit = kSpinLimitDefault;
-  if (!ok) {
+  if (!o.ok || hipDeviceSynchronize() != hipSuccess) {
     hz_env_destroy(e);
     return nullptr;
   }
@@ -2895,40 +2839,10 @@ hz_env *hz_env_create(int32_t n_boards, uint64_t seed_base, void *stream) {
 
 void hz_env_destroy(hz_env *e) {
   if (!e) return;
-  free_p2(e);
-  if (e->wait_err_own) (void)hipFree(e->wait_err_own);
-  for (int k = 0; k < 2; k++) {
-    if (e->ahead_mt[k]) (void)hipFree(e->ahead_mt[k]);
-    if (e->ahead_tag[k]) (void)hipFree(e->ahead_tag[k]);
-    if (e->ahead_pile[k]) (void)hipFree(e->ahead_pile[k]);
-    if (e->ahead_cur[k]) (void)hipFree(e->ahead_cur[k]);
-    if (e->ahead_rule[k]) (void)hipFree(e->ahead_rule[k]);
-    if (e->ep_final[k]) (void)hipFree(e->ep_final[k]);
-  }
-  for (int k = 0; k < kRing; k++) {
-    if (e->ring_mt[k]) (void)hipFree(e->ring_mt[k]);
-    if (e->ring_tag[k]) (void)hipFree(e->ring_tag[k]);
-    if (e->ring_pile[k]) (void)hipFree(e->ring_pile[k]);
-    if (e->ring_cur[k]) (void)hipFree(e->ring_cur[k]);
-    if (e->ring_k1[k]) (void)hipFree(e->ring_k1[k]);
-  }
-  if (e->pw_words) (void)hipFree(e->pw_words);
-  if (e->pw_tag) (void)hipFree(e->pw_tag);
-  if (e->pw_ep) (void)hipFree(e->pw_ep);
-  if (e->ar_mt) (void)hipFree(e->ar_mt);
-  if (e->ar_tag) (void)hipFree(e->ar_tag);
-  if (e->ar_pile) (void)hipFree(e->ar_pile);
-  if (e->ar_cur) (void)hipFree(e->ar_cur);
-  for (int k = 0; k < 2; k++)
-    if (e->ar_ep[k]) (void)hipFree(e->ar_ep[k]);
-  if (e->state) (void)hipFree(e->state);
-  if (e->mt) (void)hipFree(e->mt);
-  if (e->pos) (void)hipFree(e->pos);
-  if (e->ply) (void)hipFree(e->ply);
-  if (e->episode) (void)hipFree(e->episode);
-  if (e->seed) (void)hipFree(e->seed);
-  if (e->mt_src) (void)hipFree(e->mt_src);
-  free(e);
+  e->p2_bufs.release();
+  e->ar_bufs.release();
+  e->bufs.release();
+  delete e;
 }
 
 int32_t hz_env_size(const hz_env *e) { return e ? e->n : -1; }
@@ -2969,12 +2883,12 @@ int hz_env_set_stream(hz_env *e, void *stream) {
 uint64_t *hz_env_state_ptr(hz_env *e) { return e ? e->state : nullptr; }
 uint32_t *hz_env_mt_ptr(hz_env *e) {  // the streams are made current first (materialize)
   if (!e || materialize(e)) return nullptr;
-  e->mt_epoch++;  // the caller may move or rewrite streams (PlyWin)
+  streams_touched(e);  // the caller may move or rewrite streams (PlyWin)
   return e->mt;
 }
 int32_t *hz_env_mt_pos_ptr(hz_env *e) {
   if (!e) return nullptr;
-  e->mt_epoch++;
+  streams_touched(e);
   return e->pos;
 }
 int32_t *hz_env_ply_ptr(hz_env *e) { return e ? e->ply : nullptr; }
@@ -2993,8 +2907,8 @@ int hz_env_set_seed_ahead(hz_env *e, int32_t draws) {
 }
 
 int hz_reset(hz_env *e, const uint8_t *sel, const uint64_t *seeds) {
-  if (e) e->mt_epoch++;  // (may move or rewrite streams: PlyWin)
   if (!e) return -1;
+  streams_touched(e);  // (may move or rewrite streams: PlyWin)
   if (int err = materialize(e)) return err;  // unselected boards keep their streams
   e->primed = 0;  // episode counters move outside hz_play's plan
   e->primed2 = 0;
@@ -3054,8 +2968,8 @@ int hz_rule_actions(hz_env *e, const uint64_t *mask, const int32_t *count, int16
 }
 
 int hz_greedy_actions(hz_env *e, const uint8_t *sel, int16_t *action) {
-  if (e) e->mt_epoch++;  // (may move or rewrite streams: PlyWin)
   if (!e || !action) return -1;
+  streams_touched(e);  // (may move or rewrite streams: PlyWin)
   if (int err = materialize(e)) return err;
   hipLaunchKernelGGL(k_greedy, dim3(e->n), dim3(64), 0, e->stream, e->state, e->mt, e->pos, e->n, sel, action);
   return launch_err();
@@ -3066,24 +2980,15 @@ int hz_greedy_actions(hz_env *e, const uint8_t *sel, int16_t *action) {
 static int alloc_ar(hz_env *e) {
   if (e->ar_mt) return 0;
   const size_t n = (size_t)e->n;
-  bool ok = hipMalloc(&e->ar_mt, kArSlots * n * kMT * sizeof(uint32_t)) == hipSuccess &&
-            hipMalloc(&e->ar_tag, kArSlots * n * sizeof(int32_t)) == hipSuccess &&
-            hipMalloc(&e->ar_pile, kArSlots * kAheadWords * n * sizeof(uint64_t)) == hipSuccess &&
-            hipMalloc(&e->ar_cur, kArSlots * (kAheadDraws + 1) * n * sizeof(int32_t)) == hipSuccess &&
-            hipMalloc(&e->ar_ep[0], n * sizeof(int32_t)) == hipSuccess &&
-            hipMalloc(&e->ar_ep[1], n * sizeof(int32_t)) == hipSuccess &&
-            hipMemsetAsync(e->ar_tag, 0xff, kArSlots * n * sizeof(int32_t), e->stream) == hipSuccess;
-  if (!ok) {
-    auto f = [](auto *&p) {
-      if (p) (void)hipFree((void *)p);
-      p = nullptr;
-    };
-    f(e->ar_mt);
-    f(e->ar_tag);
-    f(e->ar_pile);
-    f(e->ar_cur);
-    f(e->ar_ep[0]);
-    f(e->ar_ep[1]);
+  DevBufs &o = e->ar_bufs;
+  o.get(e->ar_mt, kArSlots * n * kMT * sizeof(uint32_t));
+  o.get(e->ar_tag, kArSlots * n * sizeof(int32_t), 0xff, e->stream);
+  o.get(e->ar_pile, kArSlots * kAheadWords * n * sizeof(uint64_t));
+  o.get(e->ar_cur, kArSlots * (kAheadDraws + 1) * n * sizeof(int32_t));
+  o.get(e->ar_ep[0], n * sizeof(int32_t));
+  o.get(e->ar_ep[1], n * sizeof(int32_t));
+  if (!o.ok) {
+    o.release();
     return 1;
   }
   e->ar_primed = 0;
@@ -3105,8 +3010,8 @@ static int alloc_ar(hz_env *e) {
 // ep_final from the counters.
 static int launch_rollout(hz_env *e, int32_t max_plies, int32_t auto_reset, int reset_first, uint64_t *traj_state,
                           uint64_t *traj_mask, int16_t *traj_action, int32_t *games_done, int32_t *steps_done) {
-  if (e) e->mt_epoch++;  // (may move or rewrite streams: PlyWin)
   if (!e || max_plies < 0) return -1;
+  streams_touched(e);  // (may move or rewrite streams: PlyWin)
   e->primed2 = 0;  // (pipeline 2's episode prediction is stale after this launch)
   // hz_rollout continues the current games on their streams; hz_play starts
   // every board's next game (its old stream is dead)
@@ -3219,8 +3124,8 @@ int hz_export_state(hz_env *e, uint64_t *state, uint32_t *mt, int32_t *mt_index)
 }
 
 int hz_import_state(hz_env *e, const uint64_t *state, const uint32_t *mt, const int32_t *mt_index) {
-  if (e) e->mt_epoch++;  // (may move or rewrite streams: PlyWin)
   if (!e) return -1;
+  streams_touched(e);  // (may move or rewrite streams: PlyWin)
   if ((mt == nullptr) != (mt_index == nullptr)) return -2;
   size_t n = (size_t)e->n;
   if (state && hipMemcpyAsync(e->state, state, n * 6 * sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream))
@@ -3235,8 +3140,8 @@ int hz_import_state(hz_env *e, const uint64_t *state, const uint32_t *mt, const 
 }
 
 int hz_replenish(hz_env *e, const uint8_t *sel) {
-  if (e) e->mt_epoch++;  // (may move or rewrite streams: PlyWin)
   if (!e) return -1;
+  streams_touched(e);  // (may move or rewrite streams: PlyWin)
   if (int err = materialize(e)) return err;
   hipLaunchKernelGGL(k_turn_op, dim3(grid_for(e->n)), dim3(kBlock), 0, e->stream, e->state, e->mt, e->pos, e->n, sel,
                      0);
@@ -3244,8 +3149,8 @@ int hz_replenish(hz_env *e, const uint8_t *sel) {
 }
 
 int hz_end_turn(hz_env *e, const uint8_t *sel) {
-  if (e) e->mt_epoch++;  // (may move or rewrite streams: PlyWin)
   if (!e) return -1;
+  streams_touched(e);  // (may move or rewrite streams: PlyWin)
   if (int err = materialize(e)) return err;
   hipLaunchKernelGGL(k_turn_op, dim3(grid_for(e->n)), dim3(kBlock), 0, e->stream, e->state, e->mt, e->pos, e->n, sel,
                      1);

@@ -24,8 +24,10 @@
 #include "../../include/hz_abi.h"
 #include "hz_device.hpp"
 #include "hz_encode.hpp"
+#include "hz_host.hpp"
 
 using namespace hz;
+using namespace hz_host;
 
 struct hz_env;  // defined in hz_env.hip; accessed through the ABI getters
 
@@ -68,11 +70,6 @@ constexpr int kMaxChildren = 69;  // measured max legal moves
 constexpr int kChildSlots = 128;  // two per lane (loop bound: lanes c and c + 64)
 constexpr int kChildLds = 72;     // LDS rows per child array: every access has c < nl <= kMaxChildren
 constexpr int kDedupSlots = 128;  // sibling-dedup table (load factor <= 69/128)
-
-inline int launch_err() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
 
 __device__ __forceinline__ uint64_t ht_entry(int gen, int node) {
   return ((uint64_t)(uint32_t)gen << 32) | (uint32_t)node;
@@ -1421,10 +1418,7 @@ int hz_mcts_gather_leaves(hz_mcts *m, float *board, float *glob, int32_t *rows, 
   if (!m || !count || (!board && !glob)) return -1;
   // default: k_gather_encode (one launch); HZ_GATHER_ENCODE=0: k_gather + the
   // encoder launches (same results)
-  static const bool fused_default = [] {
-    const char *e = getenv("HZ_GATHER_ENCODE");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool fused_default = env_pick("HZ_GATHER_ENCODE", 0, 1);
   const bool fused = m->gather_mode < 0 ? fused_default : m->gather_mode == 1;
   if (fused && board && glob) {
     hipLaunchKernelGGL(k_gather_encode, dim3((m->n + kGERows - 1) / kGERows), dim3(kGEThreads), 0, m->stream, *m,
@@ -1441,10 +1435,7 @@ int hz_mcts_gather_leaves(hz_mcts *m, float *board, float *glob, int32_t *rows, 
 constexpr int kGatherBPW = 16;
 static_assert(kGatherBPW * sizeof(ExpandLds) <= 160 * 1024, "the workgroup's records fit the LDS");
 static int gather_bpw() {
-  static const int v = [] {
-    const char *e = getenv("HZ_GATHER_BPW");
-    return e && atoi(e) == 8 ? 8 : kGatherBPW;
-  }();
+  static const int v = env_pick("HZ_GATHER_BPW", 8, kGatherBPW);
   return v;
 }
 
@@ -1458,23 +1449,17 @@ static int expand_backup(hz_mcts *m, hz_env *env, const float *policy, const flo
   // default: registers capped for four waves per SIMD (38 VGPRs spilled;
   // with the 9.8 KB LDS, 4096 boards fit the chip in one round): 44.7 vs
   // 47.3 us per sim step for three waves (HZ_EXPAND_WAVES=3), profiles/r03
-  static const int waves = [] {
-    const char *e = getenv("HZ_EXPAND_WAVES");
-    return e && atoi(e) == 3 ? 3 : 4;
-  }();
+  static const int waves = env_pick("HZ_EXPAND_WAVES", 3, 4);
   // HZ_EXPAND_PRIO=0: the turn-end waves keep the default issue priority (A/B)
-  static const int prio = [] {
-    const char *e = getenv("HZ_EXPAND_PRIO");
-    return e && atoi(e) == 0 ? 0 : 1;
-  }();
-  static const bool wave_slot = [] {
-    const char *e = getenv("HZ_SLOT_WAVE");
-    return e && atoi(e) == 1;
-  }();
+  static const int prio = env_pick("HZ_EXPAND_PRIO", 0, 1);
+  static const bool wave_slot = env_pick("HZ_SLOT_WAVE", 1, 0);
+  // the env's streams made current (materialize) and its epoch moved, once per call
+  uint32_t *const mt = hz_env_mt_ptr(env);
+  int32_t *const mt_pos = hz_env_mt_pos_ptr(env);
+  if (!mt || !mt_pos) return 1;
 #define HZ_EXPAND_LAUNCH(W, S, G, BP, ...)                                                                      \
   hipLaunchKernelGGL((k_expand_backup<W, S, G, BP, ##__VA_ARGS__>), dim3((m->n + (BP) - 1) / (BP)), dim3(kWave * (BP)), \
-                     0, m->stream, *m, hz_env_mt_ptr(env),                                                        \
-                     hz_env_mt_pos_ptr(env), policy, value, noise, eps, ome, testing, slot, prio, active, cpuct,     \
+                     0, m->stream, *m, mt, mt_pos, policy, value, noise, eps, ome, testing, slot, prio, active, cpuct, \
                      board, glob, rows, count_out, count_prev, add_prev)
   const bool gat = sel && count_out;
   if (waves == 4) {

@@ -18,6 +18,9 @@
 #include <type_traits>
 
 #include "../../include/hz_abi.h"
+#include "hz_host.hpp"
+
+using namespace hz_host;
 
 namespace {
 
@@ -274,16 +277,8 @@ extern "C" int hz_conv3x3_bias_act(const float *x, const float *wpack, const flo
   if (((uintptr_t)x | (uintptr_t)wpack | (uintptr_t)out | (uintptr_t)res) & 15) return -1;
   if (batch == 0) return 0;
   // the 145 KB dynamic-LDS opt-in, once per device
-  static std::atomic<uint64_t> init_mask{0};
   const size_t lds = 2 * (size_t)kBuf * sizeof(float);
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1;
-  if (!(init_mask.load(std::memory_order_acquire) >> dev & 1)) {
-    if (hipFuncSetAttribute((const void *)k_conv3x3_w8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess)
-      return 1;
-    init_mask.fetch_or(1ull << dev, std::memory_order_release);
-  }
+  if (lds_opt_in<k_conv3x3_w8>(lds)) return 1;
   hipLaunchKernelGGL(k_conv3x3_w8, dim3((batch + kCS - 1) / kCS), dim3(512), lds, (hipStream_t)stream, x,
                      (const float4 *)wpack, bias, res, out, batch, live);
   return hipGetLastError() == hipSuccess ? 0 : 1;
@@ -1463,16 +1458,8 @@ __global__ void __launch_bounds__(256, 1)
 template <int NQ, bool Stem, int CS, int NCB>
 static int launch_x6_cs(const float *x, const void *wpack6, const float *bias, const float *res, float *out,
                         int32_t batch, const int32_t *live, void *stream) {
-  static std::atomic<uint64_t> init_mask{0};
   const size_t lds = 2 * (size_t)((CS * 35 * kX6Cell + 255) / 256 * 256 + kX6Zero);
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1;
-  if (!(init_mask.load(std::memory_order_acquire) >> dev & 1)) {
-    if (hipFuncSetAttribute((const void *)k_conv3x3_x6<NQ, Stem, CS, NCB>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return 1;
-    init_mask.fetch_or(1ull << dev, std::memory_order_release);
-  }
+  if (lds_opt_in<k_conv3x3_x6<NQ, Stem, CS, NCB>>(lds)) return 1;
   hipLaunchKernelGGL((k_conv3x3_x6<NQ, Stem, CS, NCB>), dim3((batch + CS - 1) / CS),
                      dim3((CS == 8 ? 2 : 1) * (8 / NCB) * 64), lds, (hipStream_t)stream, x, (const bf16x8 *)wpack6,
                      bias, res, out, batch, live);
@@ -1482,20 +1469,14 @@ static int launch_x6_cs(const float *x, const void *wpack6, const float *bias, c
 // batches of at most this many rows (the buffer's, known on the host) run
 // one state per workgroup; HZ_X6_SMALL_MAX overrides it (tools/conv_bench.py)
 static int32_t x6_small_max() {
-  static const int32_t v = [] {
-    const char *e = getenv("HZ_X6_SMALL_MAX");
-    return e ? (int32_t)atoi(e) : (int32_t)kX6SmallMax;
-  }();
+  static const int32_t v = env_int("HZ_X6_SMALL_MAX", kX6SmallMax);
   return v;
 }
 
 // ... and up to this many, one state per workgroup with 8 waves of 16
 // output channels (half of each wave's MFMA chain; HZ_X6_TINY_MAX overrides)
 static int32_t x6_tiny_max() {
-  static const int32_t v = [] {
-    const char *e = getenv("HZ_X6_TINY_MAX");
-    return e ? (int32_t)atoi(e) : (int32_t)kX6TinyMax;
-  }();
+  static const int32_t v = env_int("HZ_X6_TINY_MAX", kX6TinyMax);
   return v;
 }
 
@@ -1503,10 +1484,7 @@ static int32_t x6_tiny_max() {
 // complete self-play games 131.6 vs 127.4-127.7 games/s on one box,
 // profiles/r03/ab_w4_fullgame.json) unless HZ_X6_W4=0 (A/B measurements)
 static bool x6_w4() {
-  static const bool v = [] {
-    const char *e = getenv("HZ_X6_W4");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool v = env_pick("HZ_X6_W4", 0, 1);
   return v;
 }
 
@@ -1514,16 +1492,8 @@ template <bool Block, bool Cf = false>
 static int launch_x6w4(const float *x, const void *wpack6, const float *bias, const float *res, float *out,
                        int32_t batch, const int32_t *live, void *stream, const void *wpack6_2 = nullptr,
                        const float *bias2 = nullptr, float *tmp = nullptr) {
-  static std::atomic<uint64_t> init_mask{0};
   const size_t lds = 2 * (size_t)(kCS * 35 * kX6Cell + kX6Zero) + (Block ? (size_t)(kRows + 1) * 128 + kX6Cell : 0);
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1;
-  if (!(init_mask.load(std::memory_order_acquire) >> dev & 1)) {
-    if (hipFuncSetAttribute((const void *)k_conv3x3_x6w4<Block, Cf>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-      return 1;
-    init_mask.fetch_or(1ull << dev, std::memory_order_release);
-  }
+  if (lds_opt_in<k_conv3x3_x6w4<Block, Cf>>(lds)) return 1;
   hipLaunchKernelGGL((k_conv3x3_x6w4<Block, Cf>), dim3((batch + kCS - 1) / kCS), dim3(256), lds, (hipStream_t)stream, x,
                      (const bf16x8 *)wpack6, bias, res, out, batch, live, (const bf16x8 *)wpack6_2, bias2, tmp);
   return hipGetLastError() == hipSuccess ? 0 : 1;
@@ -1532,16 +1502,8 @@ static int launch_x6w4(const float *x, const void *wpack6, const float *bias, co
 template <bool Cf>
 static int launch_x6w4_tower(const float *x, float *out, float *tmp, const X6Tower &tw, int32_t batch,
                              const int32_t *live, void *stream) {
-  static std::atomic<uint64_t> init_mask{0};
   const size_t lds = 2 * (size_t)(kCS * 35 * kX6Cell + kX6Zero) + (size_t)(kRows + 1) * 128 + kX6Cell;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1;
-  if (!(init_mask.load(std::memory_order_acquire) >> dev & 1)) {
-    if (hipFuncSetAttribute((const void *)k_x6w4_tower<Cf>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess)
-      return 1;
-    init_mask.fetch_or(1ull << dev, std::memory_order_release);
-  }
+  if (lds_opt_in<k_x6w4_tower<Cf>>(lds)) return 1;
   hipLaunchKernelGGL((k_x6w4_tower<Cf>), dim3((batch + kCS - 1) / kCS), dim3(256), lds, (hipStream_t)stream, x, out,
                      batch, live, tmp, tw);
   return hipGetLastError() == hipSuccess ? 0 : 1;
@@ -1554,17 +1516,8 @@ static int launch_x6w4_tower(const float *x, float *out, float *tmp, const X6Tow
 // intermediate activation's write and re-read are gone: 2.29 vs 2.41 ms per
 // 4096-row forward, 138.4-138.8 vs 132.9-133.6 complete self-play games/s
 // on one box (profiles/r03/block)
-static std::atomic<int32_t> g_x6_block{-1};  // -1: from HZ_X6_BLOCK on first use
-static bool x6_block() {
-  int32_t v = g_x6_block.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char *e = getenv("HZ_X6_BLOCK");
-    int32_t want = e && atoi(e) == 0 ? 0 : 1, expect = -1;
-    g_x6_block.compare_exchange_strong(expect, want);
-    v = g_x6_block.load(std::memory_order_relaxed);
-  }
-  return v == 1;
-}
+static Setting g_x6_block{"HZ_X6_BLOCK", 1};  // (hz_resblock_x6_set_fused)
+static bool x6_block() { return g_x6_block.get() != 0; }
 
 // the fused block's row table: 1 (the default since round 5) the
 // bank-conflict-free kX6ClassRow, 0 round 3's kX6ClassRowBlk
@@ -1572,17 +1525,8 @@ static bool x6_block() {
 // interleaved in one process (tools/blk_table_ab.py, 12 rounds x 20
 // forwards each): 2.2378 vs 2.2368 ms and 2.3143 vs 2.3073 ms on two boxes
 // (profiles/r05/blk_table), bit-identical
-static std::atomic<int32_t> g_x6_blk_cf{-1};
-static bool x6_blk_cf() {
-  int32_t v = g_x6_blk_cf.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char *e = getenv("HZ_BLK_TABLE");
-    int32_t want = e && atoi(e) == 0 ? 0 : 1, expect = -1;
-    g_x6_blk_cf.compare_exchange_strong(expect, want);
-    v = g_x6_blk_cf.load(std::memory_order_relaxed);
-  }
-  return v == 1;
-}
+static Setting g_x6_blk_cf{"HZ_BLK_TABLE", 1};
+static bool x6_blk_cf() { return g_x6_blk_cf.get() != 0; }
 
 // HZ_X6_CS4=1: the tower conv above the one-state forms' limit as the
 // 4-state form (k_conv3x3_x6<4, false, 4, 2>: two 4-wave workgroups per CU,
@@ -1593,17 +1537,11 @@ static bool x6_blk_cf() {
 // 47.8 vs 49.6 us at 4,096 encoder rows, bit-identical (tools/stem_ab.py,
 // alternating processes, profiles/r06/stem_cs4); HZ_STEM_CS4=0: 8 states
 static bool stem_cs4() {
-  static const bool v = [] {
-    const char *e = getenv("HZ_STEM_CS4");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool v = env_pick("HZ_STEM_CS4", 0, 1);
   return v;
 }
 static bool x6_cs4() {
-  static const bool v = [] {
-    const char *e = getenv("HZ_X6_CS4");
-    return e && atoi(e) == 1;
-  }();
+  static const bool v = env_pick("HZ_X6_CS4", 1, 0);
   return v;
 }
 
@@ -1658,10 +1596,7 @@ extern "C" int32_t hz_resblock_x6_fused(int32_t batch);
 // the default stagger (4 units, ~33 k cycles): 0.3-0.6 % per 4096-row forward
 // against none, bit-identical (tools/tower_stagger_ab.py, profiles/r06/s6d,
 // s6e); HZ_TOWER_STAGGER overrides it
-static std::atomic<int32_t> g_tower_stagger{[] {
-  const char *e = getenv("HZ_TOWER_STAGGER");
-  return e ? (int32_t)atoi(e) : (int32_t)4;
-}()};
+static Setting g_tower_stagger{"HZ_TOWER_STAGGER", 4};
 static int32_t tower_round() {  // the device's CU count: workgroups of the tower's first round
   static std::atomic<int32_t> cus{0};
   int32_t v = cus.load(std::memory_order_relaxed);
@@ -1679,7 +1614,7 @@ static int32_t tower_round() {  // the device's CU count: workgroups of the towe
 // A/B knob (no reference counterpart): the tower launch's stagger (above)
 extern "C" int hz_tower_x6_set_stagger(int32_t units) {
   if (units < 0 || units > 1000) return -1;
-  g_tower_stagger.store(units, std::memory_order_relaxed);
+  g_tower_stagger.set(units);
   return 0;
 }
 extern "C" int hz_tower_x6_blocks(const float *x, const void *const *w1, const float *const *b1,
@@ -1698,7 +1633,7 @@ extern "C" int hz_tower_x6_blocks(const float *x, const void *const *w1, const f
     tw.b2[k] = b2[k];
   }
   tw.nblk = nblk;
-  tw.stagger = g_tower_stagger.load(std::memory_order_relaxed);
+  tw.stagger = g_tower_stagger.get();
   tw.round = tower_round();
   return x6_blk_cf() ? launch_x6w4_tower<true>(x, out, tmp, tw, batch, live, stream)
                      : launch_x6w4_tower<false>(x, out, tmp, tw, batch, live, stream);
@@ -1708,14 +1643,14 @@ extern "C" int hz_tower_x6_blocks(const float *x, const void *const *w1, const f
 // as the two layered convs (the same bits either way; A/B and tests)
 extern "C" int hz_resblock_x6_set_fused(int32_t on) {
   if (on != 0 && on != 1) return -1;
-  g_x6_block.store(on, std::memory_order_relaxed);
+  g_x6_block.set(on);
   return 0;
 }
 
 // the fused block's row table (A/B and tests; the same bits either way)
 extern "C" int hz_resblock_x6_set_table(int32_t cf) {
   if (cf != 0 && cf != 1) return -1;
-  g_x6_blk_cf.store(cf, std::memory_order_relaxed);
+  g_x6_blk_cf.set(cf);
   return 0;
 }
 
@@ -1905,15 +1840,7 @@ extern "C" int hz_tower_x6_resident(const float *x0, const void *wpack6, const f
   if (!x0 || !wpack6 || !bias || !out || batch < 0 || nconv < 2 || nconv > kTRMaxConv || (nconv & 1)) return -1;
   if (((uintptr_t)x0 | (uintptr_t)wpack6 | (uintptr_t)out) & 15) return -1;
   if (batch == 0) return 0;
-  static std::atomic<uint64_t> init_mask{0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1;
-  if (!(init_mask.load(std::memory_order_acquire) >> dev & 1)) {
-    if (hipFuncSetAttribute((const void *)k_tower_x6_resident, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            kTRLds + kTRMaxConv * 128 * 4) != hipSuccess)
-      return 1;
-    init_mask.fetch_or(1ull << dev, std::memory_order_release);
-  }
+  if (lds_opt_in<k_tower_x6_resident>(kTRLds + kTRMaxConv * 128 * 4)) return 1;
   hipLaunchKernelGGL(k_tower_x6_resident, dim3(batch), dim3(512), kTRLds + nconv * 128 * 4, (hipStream_t)stream, x0,
                      (const bf16x8 *)wpack6, bias, out, nconv, batch, live);
   return hipGetLastError() == hipSuccess ? 0 : 1;
@@ -2170,11 +2097,8 @@ static int32_t split_resident_groups_device() {
   hipDeviceProp_t prop;
   int per_cu = 0, per_cu3 = 0;
   int32_t v = 0;
-  if (hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-      hipFuncSetAttribute((const void *)k_tower_x6_split<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          kTSLds) == hipSuccess &&
-      hipFuncSetAttribute((const void *)k_tower_x6_split<4, 3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          kTSLds) == hipSuccess &&
+  if (hipGetDeviceProperties(&prop, dev) == hipSuccess && !lds_opt_in<k_tower_x6_split<4, 1>>(kTSLds) &&
+      !lds_opt_in<k_tower_x6_split<4, 3>>(kTSLds) &&
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_tower_x6_split<4, 1>, 192, kTSLds) ==
           hipSuccess &&
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu3, (const void *)k_tower_x6_split<4, 3>, 192, kTSLds) ==
@@ -2194,11 +2118,7 @@ static int32_t split_groups_per_state(int32_t batch, int32_t rb1max) { return ba
 static int32_t split_rb1max() {
   // one row block per workgroup (3 x kTSG groups per state) up to this batch
   // (HZ_TS_RB1_MAX; at most 256 / (3 x kTSG))
-  static const int rb1max = [] {
-    const char *e = getenv("HZ_TS_RB1_MAX");
-    const int v = e ? atoi(e) : kTSRb1Max;
-    return v < 0 ? 0 : v > 256 / (3 * kTSG) ? 256 / (3 * kTSG) : v;
-  }();
+  static const int rb1max = env_clamped("HZ_TS_RB1_MAX", kTSRb1Max, 0, 256 / (3 * kTSG));
   return rb1max;
 }
 
@@ -2231,20 +2151,11 @@ extern "C" int hz_tower_x6_split(const float *x0, const void *wpack6, const floa
   if (batch * split_groups_per_state(batch, split_rb1max()) > split_resident_groups()) return -2;
   // K-steps of B fragments in flight (HZ_TS_AHEAD=12 for measurements; 4,
   // 6, 9, 12 and 18 measured alike with three row blocks per workgroup)
-  static const int ahead = [] {
-    const char *e = getenv("HZ_TS_AHEAD");
-    return e && atoi(e) == 12 ? 12 : kTSAhead;
-  }();
+  static const int ahead = env_pick("HZ_TS_AHEAD", 12, kTSAhead);
   const bool rb1 = batch <= split_rb1max();
-  static std::atomic<uint64_t> init_mask{0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1;
-  if (!(init_mask.load(std::memory_order_acquire) >> dev & 1)) {
-    for (const void *f : {(const void *)k_tower_x6_split<4, 1>, (const void *)k_tower_x6_split<12, 1>,
-                          (const void *)k_tower_x6_split<4, 3>, (const void *)k_tower_x6_split<12, 3>})
-      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kTSLds) != hipSuccess) return 1;
-    init_mask.fetch_or(1ull << dev, std::memory_order_release);
-  }
+  if (lds_opt_in<k_tower_x6_split<4, 1>>(kTSLds) || lds_opt_in<k_tower_x6_split<12, 1>>(kTSLds) ||
+      lds_opt_in<k_tower_x6_split<4, 3>>(kTSLds) || lds_opt_in<k_tower_x6_split<12, 3>>(kTSLds))
+    return 1;
   const bf16x8 *wp = (const bf16x8 *)wpack6;
   unsigned *sy = (unsigned *)sync;
   const dim3 grid(batch * kTSG * (rb1 ? 3 : 1)), block(192);
@@ -2723,10 +2634,7 @@ extern "C" int hz_heads_fc(const float *x, const float *glob, const float *hw, c
   if (!x || !glob || !hw || !hb || !wpT || !bp || !w1T || !b1 || !w2 || !b2 || !value || batch < 0) return -1;
   if (((uintptr_t)x | (uintptr_t)hw) & 15) return -1;
   if (batch == 0) return 0;
-  static const int32_t h1max = [] {
-    const char *e = getenv("HZ_HEADS1_MAX");
-    return e ? (int32_t)atoi(e) : (int32_t)kH1Max;
-  }();
+  static const int32_t h1max = env_int("HZ_HEADS1_MAX", kH1Max);
   if (batch <= h1max)
     hipLaunchKernelGGL(k_heads_fc1, dim3(batch), dim3(1024), 0, (hipStream_t)stream, x, glob, hw, hb, wpT, bp, w1T,
                        b1, w2, b2, logits, probs, value, batch, live);
@@ -2856,16 +2764,8 @@ extern "C" int hz_stem3x3_bias_act(const float *board, const float *wpack, const
   if (!board || !wpack || !bias || !out || batch < 0) return -1;
   if (((uintptr_t)wpack | (uintptr_t)out) & 15) return -1;
   if (batch == 0) return 0;
-  static std::atomic<uint64_t> init_mask{0};
   const size_t lds = (size_t)kStemLds * sizeof(float);
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1;
-  if (!(init_mask.load(std::memory_order_acquire) >> dev & 1)) {
-    if (hipFuncSetAttribute((const void *)k_stem3x3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess)
-      return 1;
-    init_mask.fetch_or(1ull << dev, std::memory_order_release);
-  }
+  if (lds_opt_in<k_stem3x3>(lds)) return 1;
   hipLaunchKernelGGL(k_stem3x3, dim3((batch + kCS - 1) / kCS), dim3(512), lds, (hipStream_t)stream, board,
                      (const float4 *)wpack, bias, out, batch, live);
   return hipGetLastError() == hipSuccess ? 0 : 1;

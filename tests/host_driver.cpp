@@ -1,0 +1,267 @@
+// Stand-alone check of libhz's host layer (csrc/hz_host.hpp, its HIP-free
+// part): built with ASan + UBSan by tests/test_host_cpu.py and run without a
+// GPU.  The expected values are written out from the rules the knobs had
+// before they shared a reader; nothing here is computed by the code under test.
+#include <cstdio>
+#include <cstdlib>
+#include <set>
+
+#include "../harmonies-alphazero_amd/csrc/hz_host.hpp"
+
+using namespace hz_host;
+
+static int g_fail = 0;
+#define CHECK(c)                                                \
+  do {                                                          \
+    if (!(c)) {                                                 \
+      printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #c);       \
+      g_fail++;                                                 \
+    }                                                           \
+  } while (0)
+
+static void put(const char *name, const char *v) {
+  if (v) setenv(name, v, 1);
+  else unsetenv(name);
+}
+
+// ------------------------------------------------------------------ knobs
+// the seven cases of every rule: unset, "", "0", "1", "abc", the special
+// value, a value outside the knob's range
+struct PickCase {
+  const char *name;
+  int special, otherwise;
+  const char *special_s, *outside_s;
+  int want[7];
+};
+static const PickCase kPick[] = {
+    // on unless the value parses to 0
+    {"HZ_AR_AHEAD", 0, 1, "0", "-5", {1, 0, 0, 1, 0, 0, 1}},
+    {"HZ_X6_W4", 0, 1, "0", "2", {1, 0, 0, 1, 0, 0, 1}},
+    {"HZ_STEM_CS4", 0, 1, "0", "2", {1, 0, 0, 1, 0, 0, 1}},
+    {"HZ_GATHER_ENCODE", 0, 1, "0", "2", {1, 0, 0, 1, 0, 0, 1}},
+    {"HZ_EXPAND_PRIO", 0, 1, "0", "7", {1, 0, 0, 1, 0, 0, 1}},
+    // off unless it parses to 1
+    {"HZ_X6_CS4", 1, 0, "1", "2", {0, 0, 0, 1, 0, 1, 0}},
+    {"HZ_SLOT_WAVE", 1, 0, "1", "11", {0, 0, 0, 1, 0, 1, 0}},
+    // this one value or the default
+    {"HZ_PIPELINE", 1, 2, "1", "3", {2, 2, 2, 1, 2, 1, 2}},
+    {"HZ_EXPAND_WAVES", 3, 4, "3", "5", {4, 4, 4, 4, 4, 3, 4}},
+    {"HZ_GATHER_BPW", 8, 16, "8", "32", {16, 16, 16, 16, 16, 8, 16}},
+    {"HZ_TS_AHEAD", 12, 4, "12", "18", {4, 4, 4, 4, 4, 12, 4}},
+};
+
+static void test_knobs() {
+  for (const PickCase &c : kPick) {
+    const char *in[7] = {nullptr, "", "0", "1", "abc", c.special_s, c.outside_s};
+    for (int i = 0; i < 7; i++) {
+      put(c.name, in[i]);
+      const int got = env_pick(c.name, c.special, c.otherwise);
+      if (got != c.want[i]) printf("%s=%s: %d, want %d\n", c.name, in[i] ? in[i] : "(unset)", got, c.want[i]);
+      CHECK(got == c.want[i]);
+    }
+    put(c.name, nullptr);
+  }
+  // plain integers (HZ_X6_SMALL_MAX, HZ_X6_TINY_MAX, HZ_HEADS1_MAX, HZ_TOWER_STAGGER)
+  {
+    const char *in[7] = {nullptr, "", "0", "1", "abc", "4096", "-3"};
+    const int want[7] = {768, 0, 0, 1, 0, 4096, -3};
+    for (int i = 0; i < 7; i++) {
+      put("HZ_X6_SMALL_MAX", in[i]);
+      CHECK(env_int("HZ_X6_SMALL_MAX", 768) == want[i]);
+    }
+    put("HZ_X6_SMALL_MAX", nullptr);
+  }
+  // HZ_TS_RB1_MAX: default 10, clamped to [0, 256 / (3 * 8)] = [0, 10]
+  {
+    const char *in[8] = {nullptr, "", "0", "1", "abc", "7", "1000", "-4"};
+    const int want[8] = {10, 0, 0, 1, 0, 7, 10, 0};
+    for (int i = 0; i < 8; i++) {
+      put("HZ_TS_RB1_MAX", in[i]);
+      CHECK(env_clamped("HZ_TS_RB1_MAX", 10, 0, 10) == want[i]);
+    }
+    put("HZ_TS_RB1_MAX", nullptr);
+    CHECK(env_clamped("HZ_TS_RB1_MAX", 99, 0, 10) == 10);  // the default is clamped too
+  }
+  // HZ_P2_CUTS: three increasing positive multiples of 4, else 24, 40, 56
+  {
+    struct {
+      const char *in;
+      int want[3];
+    } cuts[] = {
+        {nullptr, {24, 40, 56}},       {"", {24, 40, 56}},           {"0", {24, 40, 56}},
+        {"1", {24, 40, 56}},           {"abc", {24, 40, 56}},        {"16,32,48", {16, 32, 48}},
+        {"8,20,60", {8, 20, 60}},      {"16, 32, 48", {16, 32, 48}}, {"16,32,48,64", {16, 32, 48}},
+        {"16,32", {24, 40, 56}},       {"32,16,48", {24, 40, 56}},   {"16,16,32", {24, 40, 56}},
+        {"0,4,8", {24, 40, 56}},       {"-4,4,8", {24, 40, 56}},     {"10,20,30", {24, 40, 56}},
+        {"16,32,50", {24, 40, 56}},    {"16,x,48", {24, 40, 56}},    {"4,8,12", {4, 8, 12}},
+    };
+    for (auto &c : cuts) {
+      put("HZ_P2_CUTS", c.in);
+      int got[3] = {24, 40, 56};
+      env_cuts("HZ_P2_CUTS", got);
+      if (got[0] != c.want[0] || got[1] != c.want[1] || got[2] != c.want[2])
+        printf("HZ_P2_CUTS=%s: %d,%d,%d\n", c.in ? c.in : "(unset)", got[0], got[1], got[2]);
+      CHECK(got[0] == c.want[0] && got[1] == c.want[1] && got[2] == c.want[2]);
+    }
+    put("HZ_P2_CUTS", nullptr);
+  }
+}
+
+// HZ_X6_BLOCK / HZ_BLK_TABLE (on unless 0) and HZ_TOWER_STAGGER (integer,
+// default 4): the first use reads the environment unless the setter came
+// first; the setter wins from then on; the environment is read once
+static void test_settings() {
+  const char *in[7] = {nullptr, "", "0", "1", "abc", "0", "5"};
+  const bool want_on[7] = {true, false, false, true, false, false, true};
+  const int want_stagger[7] = {4, 0, 0, 1, 0, 0, 5};
+  for (int i = 0; i < 7; i++) {
+    put("HZ_X6_BLOCK", in[i]);
+    put("HZ_TOWER_STAGGER", in[i]);
+    Setting blk{"HZ_X6_BLOCK", 1}, stg{"HZ_TOWER_STAGGER", 4};
+    CHECK((blk.get() != 0) == want_on[i]);
+    CHECK(stg.get() == want_stagger[i]);
+    put("HZ_X6_BLOCK", want_on[i] ? "0" : "1");  // too late: read once
+    put("HZ_TOWER_STAGGER", "77");
+    CHECK((blk.get() != 0) == want_on[i]);
+    CHECK(stg.get() == want_stagger[i]);
+    blk.set(want_on[i] ? 0 : 1);  // the setter after the first use
+    stg.set(9);
+    CHECK((blk.get() != 0) == !want_on[i]);
+    CHECK(stg.get() == 9);
+  }
+  put("HZ_X6_BLOCK", "0");
+  put("HZ_TOWER_STAGGER", "6");
+  Setting blk{"HZ_X6_BLOCK", 1}, stg{"HZ_TOWER_STAGGER", 4};
+  blk.set(1);  // the setter before the first use
+  stg.set(0);
+  CHECK(blk.get() == 1);
+  CHECK(stg.get() == 0);
+  stg.set(-1);  // (no value of the setter's reads as "not read yet")
+  CHECK(stg.get() == -1);
+  put("HZ_X6_BLOCK", nullptr);
+  put("HZ_TOWER_STAGGER", nullptr);
+}
+
+// ---------------------------------------------------------------- buffers
+// a counting allocator over malloc (so the leak check sees what the owner
+// drops): the k-th alloc or the k-th fill can be made to fail
+struct FakeDev {
+  static std::set<void *> live;
+  static int allocs, frees, fills, bad_frees, fail_alloc_at, fail_fill_at;
+  static void reset(int fail_alloc, int fail_fill) {
+    allocs = frees = fills = bad_frees = 0;
+    fail_alloc_at = fail_alloc;
+    fail_fill_at = fail_fill;
+  }
+  static bool alloc(void **p, size_t bytes) {
+    if (++allocs == fail_alloc_at) return false;
+    *p = malloc(bytes);
+    live.insert(*p);
+    return true;
+  }
+  static bool fill(void *p, int byte, size_t bytes) {
+    if (++fills == fail_fill_at) return false;
+    if (!live.count(p)) bad_frees++;
+    for (size_t i = 0; i < bytes; i++) ((unsigned char *)p)[i] = (unsigned char)byte;
+    return true;
+  }
+  static bool fill_async(void *p, int byte, size_t bytes, void *) { return fill(p, byte, bytes); }
+  static void free(void *p) {
+    frees++;
+    if (!live.erase(p)) {
+      bad_frees++;  // never obtained, or freed twice
+      return;
+    }
+    ::free(p);
+  }
+};
+std::set<void *> FakeDev::live;
+int FakeDev::allocs, FakeDev::frees, FakeDev::fills, FakeDev::bad_frees, FakeDev::fail_alloc_at, FakeDev::fail_fill_at;
+
+struct Handle {  // pointers of several types, some in arrays and nested structs, as hz_env has
+  DevBufsT<FakeDev> bufs;
+  uint64_t *state;
+  uint32_t *mt[2];
+  int32_t *tag;
+  struct {
+    int32_t *k;
+    uint64_t *q;
+  } draw;
+  unsigned char *bytes;
+};
+constexpr int kRequests = 7, kFills = 3;
+
+static bool request_all(Handle *h) {
+  auto &o = h->bufs;
+  o.get(h->state, 6 * 8, 0);
+  o.get(h->mt[0], 624 * 4);
+  o.get(h->mt[1], 624 * 4);
+  o.get(h->tag, 64 * 4, 0xff);
+  o.get(h->draw.k, 4);
+  o.get(h->draw.q, 8 * 3);
+  o.get(h->bytes, 5, 0xff, nullptr);
+  return o.ok;
+}
+static bool all_null(const Handle *h) {
+  return !h->state && !h->mt[0] && !h->mt[1] && !h->tag && !h->draw.k && !h->draw.q && !h->bytes;
+}
+
+static void test_bufs() {
+  Handle *h = new Handle();
+  CHECK(all_null(h));
+  // normal use, then release() twice
+  FakeDev::reset(0, 0);
+  CHECK(request_all(h));
+  CHECK(FakeDev::allocs == kRequests && FakeDev::fills == kFills && (int)FakeDev::live.size() == kRequests);
+  CHECK(h->state && h->mt[0] && h->mt[1] && h->tag && h->draw.k && h->draw.q && h->bytes);
+  CHECK(h->state[5] == 0 && h->tag[63] == -1 && h->bytes[4] == 0xff);
+  h->bufs.release();
+  CHECK(FakeDev::frees == kRequests && FakeDev::bad_frees == 0 && FakeDev::live.empty() && all_null(h));
+  h->bufs.release();
+  CHECK(FakeDev::frees == kRequests && FakeDev::bad_frees == 0 && h->bufs.ok);
+  // the k-th allocation fails, then the k-th fill
+  for (int pass = 0; pass < 2; pass++)
+    for (int k = 1; k <= (pass ? kFills : kRequests); k++) {
+      FakeDev::reset(pass ? 0 : k, pass ? k : 0);
+      CHECK(!request_all(h));
+      CHECK(!h->bufs.ok);
+      const int got = (int)FakeDev::live.size();
+      if (!pass) CHECK(got == k - 1 && FakeDev::allocs == k);  // nothing requested past the failure
+      int32_t *late = nullptr;
+      CHECK(!h->bufs.get(late, 16) && !late && (int)FakeDev::live.size() == got);
+      h->bufs.release();
+      CHECK(FakeDev::frees == got && FakeDev::bad_frees == 0 && FakeDev::live.empty() && all_null(h));
+      // the handle stays usable: the same requests succeed afterwards
+      FakeDev::reset(0, 0);
+      CHECK(request_all(h) && (int)FakeDev::live.size() == kRequests);
+      h->bufs.release();
+      CHECK(FakeDev::frees == kRequests && FakeDev::bad_frees == 0 && FakeDev::live.empty() && all_null(h));
+    }
+  delete h;
+}
+
+// ------------------------------------------------------------------ epoch
+struct FakeEnv {
+  uint32_t mt_epoch;
+};
+static void test_epoch() {
+  FakeEnv e{0xFFFFFFFEu};
+  streams_touched(&e);
+  CHECK(e.mt_epoch == 0xFFFFFFFFu);
+  streams_touched(&e);  // wraps: no report from UBSan
+  CHECK(e.mt_epoch == 0u);
+  CHECK((int32_t)e.mt_epoch == 0);
+}
+
+int main() {
+  test_knobs();
+  test_settings();
+  test_bufs();
+  test_epoch();
+  if (g_fail) {
+    printf("host driver: %d checks failed\n", g_fail);
+    return 1;
+  }
+  printf("host driver ok\n");
+  return 0;
+}
