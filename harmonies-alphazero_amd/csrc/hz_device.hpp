@@ -945,18 +945,21 @@ __device__ __forceinline__ void sample3_raw(LdsMT& m, uint32_t n, int k, uint32_
 }
 
 // A window of a pre-twisted stream in LDS: rows [0, lim) only (hz_env.hip's
-// pipeline-2 draw stages, three windows side by side).  Reads never twist:
-// past the window next() returns 0, and the caller discards any draw whose
-// cursor ends past lim (its picks depend only on the words it consumed, all
-// below the cursor).  The scan reads rows up to pos + 23, in bounds while
-// pos <= lim.
+// pipeline-2 draw stages, a window per wave side by side).  Reads never
+// twist, and the caller discards any draw whose cursor ends past lim (its
+// picks depend only on the words it consumed, all below the cursor).  The
+// scan reads rows up to pos + 23, in bounds while pos <= lim (rows the
+// window never loaded hold whatever LDS held).  Past the window next()
+// returns words that keep changing: the set method redraws while a pick
+// repeats an earlier one, so a constant there (it was 0) could repeat a pick
+// of 0 for ever.
 struct WinMT : LdsMT {
   int lim;
   __device__ __forceinline__ WinMT(int l, int cursor, int rows) : LdsMT(l, cursor), lim(rows) {}
   __device__ __forceinline__ void prefetch() {}
   __device__ __forceinline__ uint32_t next() {
     const int i = pos++;
-    return i < lim ? temper(hz_lds[i * kLdsStride + lane]) : 0u;
+    return i < lim ? temper(hz_lds[i * kLdsStride + lane]) : 0x9E3779B9u * (uint32_t)(i + 1);
   }
 };
 __device__ __forceinline__ void sample3_raw(WinMT& m, uint32_t n, int k, uint32_t j[3]) {

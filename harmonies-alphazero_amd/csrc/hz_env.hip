@@ -33,6 +33,27 @@ struct P2Mid {    // a play stage's end state, for the next play stage
   int32_t *i;     // [3][nrow] script entries used, plies played, stream cursor if fell (else -1)
 };
 
+// pipeline 2's shape (k_play2): one seeding stage for pass 1, three for pass
+// 2, kP2Draw draw stages, kP2Play play stages.  (A/B builds: -DHZ_P2_NDRAW=4
+// and / or -DHZ_P2_NPLAY=4 leave the waves of the fifth stages idle.)
+#ifndef HZ_P2_NDRAW
+#define HZ_P2_NDRAW 5
+#endif
+#ifndef HZ_P2_NPLAY
+#define HZ_P2_NPLAY 5
+#endif
+constexpr int kP2Draw = HZ_P2_NDRAW;
+constexpr int kP2Play = HZ_P2_NPLAY;
+constexpr int kP2SDraw = 4;                    // the first draw stage (after P1, P2a, P2b, P2c)
+constexpr int kP2SPlay = kP2SDraw + kP2Draw;   // the first play stage
+constexpr int kP2Stages = kP2SPlay + kP2Play;
+constexpr int kP2Last = kP2Stages - 1;  // stage s works on episode ep + kP2Last - s
+constexpr int kP2Ring = kP2Play + 1;    // the last draw stage's scripts and the rule hashes: read by the play stages 1..kP2Play calls later
+// stream slots: one per stage from P2a on (P1 runs in registers), plus one:
+// the last play stage's slot stays the board's stream
+constexpr int kP2Stream = kP2Stages;
+static_assert(kP2Draw >= 2 && kP2Draw <= 5 && kP2Play >= 2 && kP2Play <= 5, "stage counts");
+
 // Created by value-initialising new: every field starts zero.  The device
 // buffers belong to three owners by lifetime (bufs: hz_env_create; p2_bufs:
 // alloc_p2; ar_bufs: alloc_ar), each freed by its release().
@@ -91,21 +112,23 @@ struct hz_env {
   int32_t *pw_ep;            // [nrow] stream epoch of the words
   uint32_t mt_epoch;         // moved by streams_touched alone
   // pipeline 2 (hz_env_set_pipeline(e, 2); see k_play2): every board's game
-  // spread over thirteen consecutive hz_play calls, one stage per call
+  // spread over kP2Stages consecutive hz_play calls, one stage per call
   int pipeline;              // 1: chance-ahead (k_rollout's roles), 2: k_play2
   int calls2, primed2;
-  int p2_cut[3];             // the play stages' ply boundaries (HZ_P2_CUTS)
-  uint32_t *p2_s[14];        // [624][nrow] stream slots (kP2Stream)
-  int32_t *p2_s_tag[14];     // [nrow] episode * 8 + 1 P1a / 2 pass 1 / 3 P2a / 4 P2b / 5 seeded, rows 0-223 twisted
-  int32_t *p2_s_cur[14];     // [kAheadDraws + 1][nrow] the slot's cursor before draw 0 and after each draw
-  uint32_t *p2_p1h[2];       // [nrow] P1a -> P1b
-  uint32_t *p2_p2h[2];       // [2][nrow] P2a -> P2b
-  uint32_t *p2_p3h[2];       // [2][nrow] P2b -> P2c
-  P2Draw p2_x[3][2];         // D1 -> D2 -> D3 -> D4, by call parity
-  P2Draw p2_pl[5];           // D4 -> playA, playB, playC, playD: a ring of five
-  P2Mid p2_m[3][2];          // playA -> playB -> playC -> playD, by call parity
-  uint32_t *p2_h[5];         // [kRulePlies][nrow] rule hashes, a ring of five
-  int32_t *p2_h_tag[5];      // [nrow] their episode
+  int p2_cut[kP2Play - 1];   // the play stages' ply boundaries (HZ_P2_CUTS5)
+  int p2_dcut[kP2Draw + 1];  // the draw stages' first draws (HZ_P2_DCUTS); [0] = 0, [kP2Draw] = kAheadDraws
+  uint32_t *p2_s[kP2Stream];     // [624][nrow] stream slots
+  int32_t *p2_s_tag[kP2Stream];  // [nrow] episode * 8 + 3 P2a / 4 P2b / 5 seeded, rows 0-223 twisted (-1: none)
+  int32_t *p2_s_cur[kP2Stream];  // [kAheadDraws + 1][nrow] the slot's cursor before draw 0 and after each draw
+  uint32_t *p2_p1h[2];       // [nrow] P1 -> P2a: pass 1's row-1 word after its last step
+  int32_t *p2_p1t[2];        // [nrow] its tag: episode * 8 + 2
+  uint32_t *p2_p2h[2];       // [4][nrow] P2a -> P2b
+  uint32_t *p2_p3h[2];       // [4][nrow] P2b -> P2c
+  P2Draw p2_x[kP2Draw - 1][2];   // D1 -> D2 -> ... -> the last draw stage, by call parity
+  P2Draw p2_pl[kP2Ring];         // the last draw stage -> every play stage: a ring
+  P2Mid p2_m[kP2Play - 1][2];    // play stage st -> st + 1, by call parity
+  uint32_t *p2_h[kP2Ring];       // [kRulePlies][nrow] rule hashes, a ring
+  int32_t *p2_h_tag[kP2Ring];    // [nrow] their episode
   int32_t *p2_ep[2];         // [nrow] episode counter each board ended the call with
   // a pipeline wave that gives up waiting for its publisher (a bounded spin
   // on an LDS progress counter) ORs a bit into *wait_err (kWaitErr*), so the
@@ -1534,38 +1557,48 @@ __global__ void __launch_bounds__(kStageThreads) k_rollout(uint64_t *__restrict_
 // hz_play's second pipeline (hz_env_set_pipeline(e, 2)).  Each of
 // k_rollout's roles runs one serial per-board chain of ~60 k cycles (a whole
 // game, a whole seeding, 16 pile draws), and a launch lasts as long as its
-// longest chain.  Here every board's episode is cut into thirteen stages of
-// 20-30 k cycles, one per consecutive hz_play call, and one launch runs all
-// thirteen at once, each on a different episode of the board (ep = the
+// longest chain.  Here every board's episode is cut into fourteen stages of
+// about 20 k cycles, one per consecutive hz_play call, and one launch runs
+// all fourteen at once, each on a different episode of the board (ep = the
 // episode counter the previous call left, p2_ep; stage s works on episode
-// ep + 12 - s):
-//   s = 0  P1a   seeding pass 1, steps 1-312          draw-Y blocks, wave 2
-//   s = 1  P1b   pass 1, steps 313-624                draw-X blocks, wave 2
-//   s = 2  P2a   pass 2, steps 2-208                  seed blocks, wave 0
-//   s = 3  P2b   pass 2, steps 209-416                seed blocks, wave 1
-//   s = 4  P2c   pass 2, steps 417-624; rows 0-223    seed blocks, wave 2
+// ep + 13 - s).  The wave of each stage outside the seed and play blocks is
+// kP2Wave's (HZ_P2_WAVES); by default:
+//   s = 0  P1    seeding pass 1, all 624 steps, in     draw-Y blocks, wave 2
+//                registers: only its last word leaves
+//   s = 1  P2a   pass 2, steps 2-208                  seed blocks, wave 0
+//   s = 2  P2b   pass 2, steps 209-416                seed blocks, wave 1
+//   s = 3  P2c   pass 2, steps 417-624; rows 0-223    seed blocks, wave 2
 //                of the next generation twisted       (twist: wave 3)
-//   s = 5  D1    pile draws 0-5                       draw-X blocks, wave 0
-//   s = 6  D2    draws 6-11                           draw-X blocks, wave 1
-//   s = 7  D3    draws 12-17                          draw-Y blocks, wave 0
-//   s = 8  D4    draws 18-23                          draw-Y blocks, wave 1
+//   s = 4  D1    pile draws [dcut0 = 0, dcut1)        draw-X blocks, wave 0
+//   s = 5  D2    draws [dcut1, dcut2)                 draw-X blocks, wave 1
+//   s = 6  D3    draws [dcut2, dcut3)                 draw-Y blocks, wave 0
+//   s = 7  D4    draws [dcut3, dcut4)                 draw-Y blocks, wave 1
+//   s = 8  D5    draws [dcut4, 24)                    draw-X blocks, wave 2
 //          (the episode's rule hashes meanwhile:      draw-X blocks, wave 3)
-//   s = 9  playA plies [0, cut0)                      play blocks, wave 3
-//   s = 10 playB plies [cut0, cut1)                   play blocks, wave 2
-//   s = 11 playC plies [cut1, cut2)                   play blocks, wave 1
-//   s = 12 playD the rest, final scoring, the board's play blocks, wave 0
+//   s = 9  playA plies [0, cut0)                      draw-Y blocks, wave 3
+//   s = 10 playB plies [cut0, cut1)                   play blocks, wave 3
+//   s = 11 playC plies [cut1, cut2)                   play blocks, wave 2
+//   s = 12 playD plies [cut2, cut3)                   play blocks, wave 1
+//   s = 13 playE the rest, final scoring, the board's play blocks, wave 0
 //                state, cursor and counters
-// An episode's stream lives in one slot of a ring of kP2Stream from P1a to
-// playD (and afterwards as the board's current stream until materialize or
-// the next call); stage s of call c uses slot (c - s) mod kP2Stream.  A stage
-// uses an input only when its tag names the stage's episode, so a wrong
-// prediction costs time, never results: the stages skip the board and playD
+// Pass 1 never reaches memory: a pass-1 word is a function of the board's key
+// and the constant kInitGen table, so P1 hands on only what pass 2's last
+// step needs (row 1's word after the 624th step), and each pass-2 stage
+// recomputes pass 1 over its own rows next to its pass-2 chain (a second,
+// independent recurrence of four VALU operations per step), started from
+// pass 1's word at the row before its range: one step from the constants for
+// P2a, handed on with pass 2's value for P2b and P2c.
+// An episode's stream lives in one slot of a ring of kP2Stream from P2a to
+// playE (and afterwards as the board's current stream until materialize or
+// the next call); stage s >= 1 of call c uses slot (c - s) mod kP2Stream.  A
+// stage uses an input only when its tag names the stage's episode, so a wrong
+// prediction costs time, never results: the stages skip the board and playE
 // plays its whole game from scratch (seeding and drawing in LDS, like
 // k_rollout's unprepared boards).  The results are k_rollout's: the board ends
 // the call with episode ep's final state, cursor and counters, and
-// games_done / steps_done count that game (its first plies ran in the three
-// calls before, in playA, playB and playC).  In steady state a call does
-// every stage once per board: one game's worth of work per board per call.
+// games_done / steps_done count that game (its first plies ran in the four
+// calls before, in playA to playD).  In steady state a call does every stage
+// once per board: one game's worth of work per board per call.
 #ifndef HZ_P2_ST_WT
 // 1: the hand-off stores (hashes, cursors, scripts, mid-game states) write-
 // through too (global_store ... sc1): 17.0 G against 18.3 G with them plain
@@ -1583,22 +1616,65 @@ __global__ void __launch_bounds__(kStageThreads) k_rollout(uint64_t *__restrict_
 #endif
 constexpr int kP2Win = 96;        // rows a draw stage stages, from its wave's lowest cursor
 constexpr int kP2WinRows = kP2Win + 24;  // LDS rows per window (a scan reads up to 23 rows past its cursor)
-constexpr int kP2Play = 4;        // play stages
-constexpr int kP2Stages = 9 + kP2Play;
-constexpr int kP2Last = kP2Stages - 1;  // stage s works on episode ep + kP2Last - s
-constexpr int kP2Ring = kP2Play + 1;    // D4's scripts and the rule hashes: read by the play stages 1..kP2Play calls later
-constexpr int kP2Stream = 14;     // stream slots (>= kP2Stages + 1: the last play stage's slot stays the board's stream)
-constexpr int kP2DrawsPer = 6;    // pile draws per draw stage (4 x 6 = kAheadDraws)
 #ifndef HZ_P2_DCUT
-// the draw stages' first draws: D1 0-6, D2 7-12, D3 13-17, D4 18-23.  With
-// six each, D3 was the longest stage (13.8 us against 10.5 for D1) once the
-// slot stores were written through: 19.37 vs 18.24 G env-steps/s, 13.2 vs
-// 14.1 us per launch (profiles/r05/p2_dcut; A/B builds -DHZ_P2_DCUT=...)
+// the draw stages' first draws (run time: HZ_P2_DCUTS).  Later draws take
+// longer, so the early stages take more of them: with four stages of six, D3
+// ran 13.8 us against D1's 10.5, and the cuts became 0, 7, 13, 18
+// (profiles/r05/p2_dcut); five stages: profiles/r07.
+#if HZ_P2_NDRAW == 5
+#define HZ_P2_DCUT 0, 5, 10, 14, 18
+#elif HZ_P2_NDRAW == 4
 #define HZ_P2_DCUT 0, 7, 13, 18
 #endif
-constexpr int kP2DCut[4] = {HZ_P2_DCUT};
+#endif
+constexpr int kP2DCut[kP2Draw] = {HZ_P2_DCUT};
+// A draw stage's window holds kP2Win rows from its wave's lowest cursor.
+// Seven draws (the most a stage ever had) use at most ~60 words (eight
+// consecutive draws: 67 over 20,000 seeds), which leaves room for the
+// spread of the wave's cursors; a stage of twenty overruns the window for
+// about one board in twenty, every time at the cost of the draws discarded.
+constexpr int kP2StageDraws = 7;
+#ifndef HZ_P2_PCUT
+// the play stages' ply boundaries (run time: HZ_P2_CUTS5; four stages:
+// HZ_P2_CUTS).  Multiples of 8: a stage that starts inside a turn pair plays
+// single plies up to the next pair, and every such setting measured slower
+// (profiles/r07/cuts_scan.json).
+#if HZ_P2_NPLAY == 5
+#define HZ_P2_PCUT 16, 32, 48, 64
+#elif HZ_P2_NPLAY == 4
+#define HZ_P2_PCUT 24, 40, 56
+#endif
+#endif
+constexpr int kP2PCut[kP2Play - 1] = {HZ_P2_PCUT};
+// what each wave of a draw-X (first four) and a draw-Y block runs: a draw
+// stage (0 .. kP2Draw - 1), P1, the rule hashes, play stage 0, or nothing.
+// (A play wave brings the ply loop's ~50 KB of code into its CU pair's
+// instruction cache next to the draw code.)
+enum { kWvP1 = 8, kWvHash = 9, kWvPlay = 10, kWvIdle = 15 };
+#ifndef HZ_P2_WAVES
+#if HZ_P2_NDRAW == 5 && HZ_P2_NPLAY == 5
+#define HZ_P2_WAVES 0, 1, 4, 9, 2, 3, 8, 10
+#elif HZ_P2_NDRAW == 5
+#define HZ_P2_WAVES 0, 1, 4, 9, 2, 3, 8, 15
+#elif HZ_P2_NPLAY == 5
+#define HZ_P2_WAVES 0, 1, 8, 9, 2, 3, 10, 15
+#else
+#define HZ_P2_WAVES 0, 1, 8, 9, 2, 3, 15, 15
+#endif
+#endif
+constexpr int kP2Wave[8] = {HZ_P2_WAVES};
+constexpr int p2_wave_count(int code) {
+  int c = 0;
+  for (int k = 0; k < 8; k++) c += kP2Wave[k] == code;
+  return c;
+}
+constexpr bool p2_waves_ok() {
+  for (int d = 0; d < 5; d++)
+    if (p2_wave_count(d) != (d < kP2Draw ? 1 : 0)) return false;
+  return p2_wave_count(kWvP1) == 1 && p2_wave_count(kWvHash) == 1 && p2_wave_count(kWvPlay) == (kP2Play == 5 ? 1 : 0);
+}
+static_assert(p2_waves_ok(), "HZ_P2_WAVES: every stage outside the seed and play blocks on exactly one wave");
 constexpr int kP2MinPlies = 96;   // hz_play max_plies from which pipeline 2 applies (rule games end by ply 80)
-constexpr int kP1Split = 313;
 #ifdef HZ_DIAG
 constexpr int kP2Stamps = 48;  // stamp slots per board in k_play2 (tools/p2_roles.py)
 #define P2_PHASE(slot, t0)                                                                                       \
@@ -1611,10 +1687,8 @@ constexpr int kP2Stamps = 48;  // stamp slots per board in k_play2 (tools/p2_rol
 #define P2_PHASE(slot, t0) \
   do {                     \
   } while (0)
-#endif     // pass 1: P1a runs steps [1, 313), P1b [313, 624) and the 624th
-static_assert(4 * kP2DrawsPer == kAheadDraws, "four draw stages cover the script");
-static_assert(2 * kP2WinRows * kLdsStride * 4 <= (int)kResetLds, "two windows per draw block");
-static_assert((kP1Split - 1) % 8 == 0 && (617 - kP1Split) % 8 == 0, "pass-1 halves in groups of eight");
+#endif
+static_assert(4 * kP2WinRows * kLdsStride * 4 <= (int)kResetLds, "a window per wave of a draw block");
 
 struct P2Args {
   uint64_t *st;
@@ -1623,23 +1697,26 @@ struct P2Args {
   uint64_t *seed;
   int n, max_plies, draws;
   int cut[kP2Play - 1];
+  int dcut[kP2Draw + 1];      // draw stage k: draws [dcut[k], dcut[k + 1])
   uint64_t seed_base;
   long nrow;
   int32_t *games_done, *steps_done, *mt_src;
   const int32_t *ep_in;
   int32_t *ep_out;
-  uint32_t *s_mt[kP2Stages];  // the stream slot of each stage this call
-  int32_t *s_tag[kP2Stages];  // [nrow] episode * 8 + 1 P1a / 2 pass 1 / 3 P2a / 4 P2b / 5 seeded, rows 0-223 twisted
+  uint32_t *s_mt[kP2Stages];  // the stream slot of each stage this call ([0], P1: none)
+  int32_t *s_tag[kP2Stages];  // [nrow] episode * 8 + 3 P2a / 4 P2b / 5 seeded, rows 0-223 twisted
   int32_t *s_cur[kP2Stages];  // [kAheadDraws + 1][nrow] cursor before draw 0 and after each draw
   int s_idx_last;             // the last play stage's slot index (materialize: mt_src = 2 + index)
-  uint32_t *p1h_w;            // [nrow] P1a -> P1b: pass 1's last value
+  uint32_t *p1h_w;            // [nrow] P1 -> P2a: pass 1's row-1 word after its 624th step
   const uint32_t *p1h_r;
-  uint32_t *p2h_w;            // [3][nrow] P2a -> P2b: pass 2's last value, pass 1's row-1 word, row 2's final word
-  const uint32_t *p2h_r;
-  uint32_t *p3h_w;            // [2][nrow] P2b -> P2c: the same
+  int32_t *p1t_w;             // [nrow] its tag: episode * 8 + 2
+  const int32_t *p1t_r;
+  uint32_t *p2h_w;            // [4][nrow] P2a -> P2b: pass 2's last value, pass 1's row-1 word, row 2's final word,
+  const uint32_t *p2h_r;      //           pass 1's word of P2a's last row
+  uint32_t *p3h_w;            // [4][nrow] P2b -> P2c: the same
   const uint32_t *p3h_r;
-  P2Draw x_w[3], x_r[3];      // D1 -> D2 -> D3 -> D4 (tag: episode * 8 + stages done)
-  P2Draw pl_w, pl_r[kP2Play];     // D4's script: written this call; read by play stage st (st + 1 calls later)
+  P2Draw x_w[kP2Draw - 1], x_r[kP2Draw - 1];  // D1 -> D2 -> ... (tag: episode * 8 + stages done)
+  P2Draw pl_w, pl_r[kP2Play];     // the last draw stage's script: written this call; read by play stage st (st + 1 calls later)
   P2Mid m_w[kP2Play - 1], m_r[kP2Play - 1];  // play stage st -> st + 1 (written / read this call)
   uint32_t *h_w;                  // [kRulePlies][nrow] rule hashes
   const uint32_t *h_r[kP2Play];
@@ -1786,12 +1863,6 @@ __device__ __forceinline__ void p2_publish(int *flag, int v) {
   asm volatile("" ::: "memory");
   __hip_atomic_store(flag, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-// init_by_array's pass 1, steps [i0, i1) (i0 odd, groups of eight: odd
-// steps take key word kA, even ones kB), rows at w[i * ns]; step 1's value
-// goes to row 1 (the 624th step reads it back)
-// (wb = the slot's column of the wave's first board, wave-uniform, so a
-// row's address is a scalar base plus the lane: no 64-bit address
-// arithmetic per step in the chain)
 // the slot's columns of boards [b0, b0 + 64) as a buffer (rows of nr words)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t p2_slot_rsrc(uint32_t *slot, int b0, size_t nr) {
   const uint64_t base = (uint64_t)(slot + b0);
@@ -1821,30 +1892,15 @@ __device__ __forceinline__ void p2_st(T *p, T v) {
 // (the stream slots' stores: written by one stage, read by another in the
 // next call, never by this one: HZ_P2_AUX write-through (sc1) leaves no
 // dirty lines in the XCD's L2 for the end of the kernel to write back)
-__device__ __forceinline__ void mt_pass1_span(uint32_t *__restrict__ slot, int b0, int lane, size_t ns, uint32_t kA,
-                                              uint32_t kB, int i0, int i1, uint32_t &prev) {
-  const __amdgpu_buffer_rsrc_t rs = p2_slot_rsrc(slot, b0, ns);
-  const int row_bytes = __builtin_amdgcn_readfirstlane((int)(ns * 4));
-  // init_genrand's table words a group ahead (scalar loads: their wait
-  // would otherwise sit in the chain once per group)
-  uint32_t iv[8];
-#pragma unroll
-  for (int u = 0; u < 8; u++) iv[u] = kInitGen.v[i0 + u];
-#pragma unroll 1
-  for (int g = i0; g < i1; g += 8) {
-    uint32_t nx[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) nx[u] = kInitGen.v[g + 8 + u < kMT ? g + 8 + u : kMT - 1];
-    const int soff = __builtin_amdgcn_readfirstlane(g * row_bytes);
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      const uint32_t v = (iv[u] ^ ((prev ^ (prev >> 30)) * 1664525U)) + ((u & 1) ? kB : kA);
-      __builtin_amdgcn_raw_buffer_store_b32(v, rs, lane * 4, soff + u * row_bytes, HZ_P2_AUX);
-      prev = v;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; u++) iv[u] = nx[u];
-  }
+// One step of init_by_array's pass 1 at row i: q is row i - 1's pass-1 word,
+// t kInitGen's word of row i; odd rows take key word kA, even ones kB.
+__device__ __forceinline__ uint32_t p1_step(uint32_t t, uint32_t q, bool odd, uint32_t kA, uint32_t kB) {
+  return (t ^ ((q ^ (q >> 30)) * 1664525U)) + (odd ? kA : kB);
+}
+__device__ __forceinline__ int p2_tab(int i) { return i < kMT ? i : kMT - 1; }  // (a read-ahead past the table's end)
+// pass 1's row-1 word (its first step, from init_genrand's mt[0])
+__device__ __forceinline__ uint32_t p1_row1(uint32_t kA, uint32_t kB) {
+  return p1_step(kInitGen.v[1], 19650218u, true, kA, kB);
 }
 __device__ __forceinline__ void p2_keys(uint64_t seed, uint32_t &kA, uint32_t &kB) {
   const uint32_t key0 = (uint32_t)seed, key1 = (uint32_t)(seed >> 32);
@@ -1852,96 +1908,70 @@ __device__ __forceinline__ void p2_keys(uint64_t seed, uint32_t &kA, uint32_t &k
   kB = key1 ? key1 + 1u : key0;
 }
 
-// P1a (seed blocks, wave 0) and P1b (draw-X blocks, wave 2): no LDS
-__device__ __forceinline__ void p2_p1a(const P2Args &a, int b0, int lane) {
-  const int b = b0 + lane;
-  const size_t nr = (size_t)a.nrow;
+// P1: all of init_by_array's pass 1 in registers (624 steps of four
+// dependent VALU operations; the table words by scalar loads a group of eight
+// ahead, so their wait is not in the chain).  No stream slot and no LDS: what
+// leaves is row 1's word after the 624th step (the only pass-1 word pass 2
+// cannot recompute from a neighbour: it closes the ring) and the episode tag.
+__device__ __forceinline__ void p2_p1(const P2Args &a, int b) {
   const int e = a.ep_in[b] + kP2Last;
   uint32_t kA, kB;
   p2_keys(episode_seed(a.seed_base, b, e), kA, kB);
   uint32_t prev = 19650218u;
-  mt_pass1_span(a.s_mt[0], b0, lane, nr, kA, kB, 1, kP1Split, prev);
-  a.p1h_w[b] = prev;
-  a.s_tag[0][b] = e * 8 + 1;
-}
-__device__ __forceinline__ void p2_p1b(const P2Args &a, int b0, int lane) {
-  const int b = b0 + lane;
-  const size_t nr = (size_t)a.nrow;
-  const int e = a.ep_in[b] + kP2Last - 1;
-  if (a.s_tag[1][b] != e * 8 + 1) return;
-  uint32_t kA, kB;
-  p2_keys(episode_seed(a.seed_base, b, e), kA, kB);
-  uint32_t prev = a.p1h_r[b];
-  const uint32_t *w = a.s_mt[1] + b;
-  const uint32_t row1 = w[nr];  // (P1a's step-1 word, read before any store of this wave)
-  mt_pass1_span(a.s_mt[1], b0, lane, nr, kA, kB, kP1Split, 617, prev);
-  const __amdgpu_buffer_rsrc_t rs = p2_slot_rsrc(a.s_mt[1], b0, nr);
-  const int row_bytes = __builtin_amdgcn_readfirstlane((int)(nr * 4));
+  uint32_t iv[8];
 #pragma unroll
-  for (int u = 0; u < 7; u++) {  // steps 617..623
-    const uint32_t v = (kInitGen.v[617 + u] ^ ((prev ^ (prev >> 30)) * 1664525U)) + ((u & 1) ? kB : kA);
-    __builtin_amdgcn_raw_buffer_store_b32(v, rs, lane * 4, (617 + u) * row_bytes, HZ_P2_AUX);
-    prev = v;
+  for (int u = 0; u < 8; u++) iv[u] = kInitGen.v[1 + u];
+#pragma unroll 1
+  for (int g = 1; g < 617; g += 8) {  // steps 1..616
+    uint32_t nx[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) nx[u] = kInitGen.v[p2_tab(g + 8 + u)];
+    // (the loads stay here: left to itself the scheduler sinks them to the
+    // group's end, next to their first use, and every group then waits a
+    // scalar-cache round trip: 12 us for the stage instead of 8)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < 8; u++) prev = p1_step(iv[u], prev, !(u & 1), kA, kB);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < 8; u++) iv[u] = nx[u];
   }
+#pragma unroll
+  for (int u = 0; u < 7; u++) prev = p1_step(iv[u], prev, !(u & 1), kA, kB);  // steps 617..623
   // mt[0] = mt[623]; the 624th step at i = 1 (key j = 623 % keylen -> kB)
-  __builtin_amdgcn_raw_buffer_store_b32((row1 ^ ((prev ^ (prev >> 30)) * 1664525U)) + kB, rs, lane * 4, row_bytes,
-                                        HZ_P2_AUX);
-  a.s_tag[1][b] = e * 8 + 2;
+  a.p1h_w[b] = p1_step(p1_row1(kA, kB), prev, false, kA, kB);
+  a.p1t_w[b] = e * 8 + 2;
 }
 
 // Pass 2 in three stages, P2a (steps 2-208), P2b (209-416) and P2c
-// (417-623 and the last step at i = 1), in one seed block on disjoint rows
-// of its [624][65] LDS array (the rows of three different episodes).  Every
-// step reads the next pass-1 word, too close ahead for an HBM round trip (a
-// chain reading the slot through a register ring stalled on the memory
-// counter: ~220 k cycles per half), so each chain first stages its third of
-// the pass-1 words into its own rows (all loads in flight at once), then
-// runs on LDS reads, storing each final word to the slot with a buffer store
-// (the row offset a scalar: no address arithmetic in the chain).  A chain
-// step costs ~70 cycles with one wave per SIMD (the four dependent VALU
-// operations of the recurrence plus the step's memory instructions; staging
-// transposed, four words per LDS access, changed nothing), so the chain is
-// cut into thirds rather than made cheaper per step.
+// (417-623 and the last step at i = 1), in one seed block (three different
+// episodes).  Every step reads the row's pass-1 word.  The stages once read
+// them from the stream slot (staged into LDS first: an HBM round trip per
+// step is far too slow); now each recomputes pass 1 over its own rows, a
+// group of eight ahead of its pass-2 chain, so the two recurrences are
+// independent instruction streams and interleave.  Each final word goes to
+// the slot with a buffer store (the row offset a scalar: no address
+// arithmetic in the chain).  The chain is cut into thirds rather than made
+// cheaper per step.
 constexpr int kP2aEnd = 209, kP2bEnd = 417;
 constexpr int kTwKeep = 397;  // P2c's final rows from here on stay in LDS (the twist reads rows 397-620)
-// Rows [R0, R1) of the wave's 64 boards staged from the slot into LDS, in
-// two halves: p2_load issues the 16-B loads (four boards of a row per lane,
-// four rows per instruction) into registers, p2_put writes them to LDS.  A
-// pass-2 stage stages its first piece, issues the next piece's loads and
-// runs its chain over the first piece while they land: two thirds of the
-// staging reads leave the launch's opening burst, where every stage's first
-// inputs arrive.
-template <int R0, int R1>
-struct P2Piece {
-  uint4 v[(R1 - R0 + 3) / 4];
+// pass 1 a group ahead of pass 2, at row g
+struct P2Ahead {
+  uint32_t cur[8];  // pass 1's words of rows [g, g + 8)
+  uint32_t iv[8];   // kInitGen's words of rows [g + 8, g + 16)
+  uint32_t last;    // pass 1's word of the last row pass 2 has consumed (the next stage starts from it)
 };
-template <int R0, int R1>
-__device__ __forceinline__ void p2_load(P2Piece<R0, R1> &pc, const uint32_t *__restrict__ slot, size_t nr, int b0,
-                                        int lane) {
-  constexpr int U = (R1 - R0 + 3) / 4;
-  const int c4 = (lane & 15) * 4;
+// q: pass 1's word of row G - 1
+template <int G>
+__device__ __forceinline__ void p2_ahead_init(P2Ahead &h, uint32_t q, uint32_t kA, uint32_t kB) {
 #pragma unroll
-  for (int u = 0; u < U; u++) {
-    const int r = R0 + 4 * u + (lane >> 4);
-    if (r < R1) pc.v[u] = p2_ld4(slot + (size_t)r * nr + b0 + c4);
+  for (int u = 0; u < 8; u++) {
+    q = p1_step(kInitGen.v[p2_tab(G + u)], q, (G + u) & 1, kA, kB);
+    h.cur[u] = q;
   }
-}
-template <int R0, int R1>
-__device__ __forceinline__ void p2_put(const P2Piece<R0, R1> &pc, int lane) {
-  constexpr int U = (R1 - R0 + 3) / 4;
-  const int c4 = (lane & 15) * 4;
 #pragma unroll
-  for (int u = 0; u < U; u++) {
-    const int r = R0 + 4 * u + (lane >> 4);
-    if (r < R1) {
-      uint32_t *d = hz_lds + r * kLdsStride + c4;
-      d[0] = pc.v[u].x;
-      d[1] = pc.v[u].y;
-      d[2] = pc.v[u].z;
-      d[3] = pc.v[u].w;
-    }
-  }
-  // (a wave's LDS operations execute in order: its later reads see these)
+  for (int u = 0; u < 8; u++) h.iv[u] = kInitGen.v[p2_tab(G + 8 + u)];
+  h.last = q;
 }
 // twist_word(cur, next, far) = far ^ twist_part(cur, next): the part of row
 // r's next-generation word that rows r and r + 1 decide
@@ -1950,64 +1980,72 @@ __device__ __forceinline__ uint32_t twist_part(uint32_t cur, uint32_t next) {
   return (y >> 1) ^ ((y & 1U) ? 0x9908b0dfU : 0U);
 }
 // What a pass-2 step stores: its final word to its row (kP2Final), the same
-// and over the pass-1 word in LDS (kP2Keep, P2c), or the previous row's
-// twist part (kP2Part: rows 2-223, which only the twist reads)
+// and to the row in LDS (kP2Keep, P2c), or the previous row's twist part
+// (kP2Part: rows 2-223, which only the twist reads)
 enum { kP2Final = 0, kP2Keep = 1, kP2Part = 2 };
-// steps [G0, G1) of pass 2 (G1 - G0 a multiple of 8) on the lane's LDS
-// column, pass-1 words read 8 steps ahead (rows below G1), stores to the
-// slot (buffer stores: voffset the lane, soffset the row) as Mode says (in
-// LDS in place: the read-ahead is always past the rows written), with
-// kP2Keep publishing progress every 8 steps
+// steps [G0, G1) of pass 2 (G1 - G0 a multiple of 8; h at row G0 on entry, at
+// G1 on return), while pass 1 runs over the next group's rows (past the
+// stage's last row its words are unused); stores to the slot (buffer stores:
+// voffset the lane, soffset the row) as Mode says, with kP2Keep publishing
+// progress every 8 steps
 template <int G0, int G1, int Mode>
-__device__ __forceinline__ void p2_span(int lane, __amdgpu_buffer_rsrc_t rs, int row_bytes, uint32_t &prev,
-                                        int *prog) {
+__device__ __forceinline__ void p2_span(int lane, __amdgpu_buffer_rsrc_t rs, int row_bytes, uint32_t &prev, P2Ahead &h,
+                                        uint32_t kA, uint32_t kB, int *prog) {
   constexpr bool KeepLds = Mode == kP2Keep;
   static_assert((G1 - G0) % 8 == 0, "groups of eight");
   uint32_t *l = hz_lds + lane;
   constexpr int S = kLdsStride;
-  uint32_t cur[8];
-#pragma unroll
-  for (int u = 0; u < 8; u++) cur[u] = l[(G0 + u) * S];
 #pragma unroll 2
   for (int g = G0; g < G1; g += 8) {
-    uint32_t nx[8];
+    uint32_t ivn[8], nx[8];
 #pragma unroll
-    for (int u = 0; u < 8; u++) nx[u] = l[(g + 8 + u < G1 ? g + 8 + u : G1 - 1) * S];
+    for (int u = 0; u < 8; u++) ivn[u] = kInitGen.v[p2_tab(g + 16 + u)];
     const uint32_t kneg = __builtin_amdgcn_readfirstlane(0u - (uint32_t)g);
     const int soff = __builtin_amdgcn_readfirstlane((Mode == kP2Part ? g - 1 : g) * row_bytes);
+    uint32_t q = h.cur[7];
 #pragma unroll
     for (int u = 0; u < 8; u++) {
       // (cur ^ p) - (g + u) as one v_xad_u32 with the offset in an SGPR
       const uint32_t p = (prev ^ (prev >> 30)) * 1566083941U;
       uint32_t v;
-      asm("v_xad_u32 %0, %1, %2, %3" : "=v"(v) : "v"(p), "v"(cur[u]), "s"(kneg - (uint32_t)u));
+      asm("v_xad_u32 %0, %1, %2, %3" : "=v"(v) : "v"(p), "v"(h.cur[u]), "s"(kneg - (uint32_t)u));
       __builtin_amdgcn_raw_buffer_store_b32(Mode == kP2Part ? twist_part(prev, v) : v, rs, lane * 4,
                                             soff + u * row_bytes, HZ_P2_AUX);
       if (KeepLds) l[(g + u) * S] = v;
       prev = v;
+      // pass 1, row g + 8 + u (the parity of G0 + u: g - G0 is a multiple of 8)
+      q = p1_step(h.iv[u], q, (G0 + u) & 1, kA, kB);
+      nx[u] = q;
     }
     if (KeepLds) p2_publish(prog, g + 8);  // rows [G0, g + 8) final in LDS
+    h.last = h.cur[7];
 #pragma unroll
-    for (int u = 0; u < 8; u++) cur[u] = nx[u];
+    for (int u = 0; u < 8; u++) {
+      h.cur[u] = nx[u];
+      h.iv[u] = ivn[u];
+    }
   }
 }
-// the last steps [G, G1) one by one
+// the last steps [G, G1) one by one (fewer than eight: h holds their pass-1 words)
 template <int G, int G1, int Mode>
-__device__ __forceinline__ void p2_tail(int lane, __amdgpu_buffer_rsrc_t rs, int row_bytes, uint32_t &prev) {
+__device__ __forceinline__ void p2_tail(int lane, __amdgpu_buffer_rsrc_t rs, int row_bytes, uint32_t &prev, P2Ahead &h) {
+  static_assert(G1 - G >= 1 && G1 - G <= 8, "within the group ahead");
 #pragma unroll
   for (int i = G; i < G1; i++) {
-    const uint32_t v = (hz_lds[i * kLdsStride + lane] ^ ((prev ^ (prev >> 30)) * 1566083941U)) - (uint32_t)i;
+    const uint32_t v = (h.cur[i - G] ^ ((prev ^ (prev >> 30)) * 1566083941U)) - (uint32_t)i;
     if (Mode == kP2Part) __builtin_amdgcn_raw_buffer_store_b32(twist_part(prev, v), rs, lane * 4, (i - 1) * row_bytes, HZ_P2_AUX);
     else __builtin_amdgcn_raw_buffer_store_b32(v, rs, lane * 4, i * row_bytes, HZ_P2_AUX);
     if (Mode == kP2Keep) hz_lds[i * kLdsStride + lane] = v;
     prev = v;
   }
+  h.last = h.cur[G1 - G - 1];
 }
 
 // P2a (seed blocks, wave 0): the seed blocks' P2a episode, whose pass 1
 // completed in the previous call; P2b (wave 1) the next older; P2c (wave 2,
 // with wave 3's twist) the one before.  Each hands (prev, pass 1's row-1
-// word, row 2's final word) to the next.  Rows 2-223 of the slot are read
+// word, row 2's final word, pass 1's word of its last row) to the next.
+// Rows 2-223 of the slot are read
 // only by the twist, which needs from each row r only its twist part
 // (rows r and r + 1's words): P2a and P2b store that instead of the final
 // word (one step late, when row r + 1 is known), so the twist is one xor
@@ -2019,76 +2057,52 @@ __device__ __forceinline__ void p2_third(const P2Args &a, int b0, int lane, int 
   const int b = b0 + lane;
   const bool act = b < a.n;
   const size_t nr = (size_t)a.nrow;
+  // (P2a's slot is a fresh one: whatever tag an older episode left on it goes)
+  if (K == 0 && act && !ok) a.s_tag[1][b] = -1;
   if (!__any(ok)) {
     if (K == 2) p2_publish(s_prog, kMT + 1);  // (the twist wave's waits end: nothing to twist)
     return;
   }
-  uint32_t *slot = a.s_mt[2 + K];
-#ifdef HZ_DIAG
-  const uint64_t tq = __builtin_amdgcn_s_memtime();
-#endif
-  // the stage's rows in three pieces, P0 staged now; each later piece's
-  // loads issued before the chain runs over the piece before it
-  constexpr int P0 = K == 0 ? 1 : K == 1 ? kP2aEnd : kP2bEnd;
-  constexpr int P1 = K == 0 ? 67 : K == 1 ? 289 : 481;
-  constexpr int P2 = K == 0 ? 139 : K == 1 ? 353 : 553;
-  constexpr int P3 = K == 0 ? kP2aEnd : K == 1 ? kP2bEnd : kMT;
-  {
-    P2Piece<P0, P1> pc;
-    p2_load(pc, slot, nr, b0, lane);
-    p2_put(pc, lane);
-  }
-  P2Piece<P1, P2> pc1;
-  p2_load(pc1, slot, nr, b0, lane);
-#ifdef HZ_DIAG
-  if (g_stamps && act) g_stamps[(size_t)b * kP2Stamps + 32 + K] = __builtin_amdgcn_s_memtime() - tq;  // staged
-#endif
-  uint32_t prev, first1, row2;
+  uint32_t *slot = a.s_mt[1 + K];
+  uint32_t kA, kB;
+  p2_keys(episode_seed(a.seed_base, b, e), kA, kB);
+  uint32_t prev, first1, row2, q;
   if (K == 0) {
-    first1 = hz_lds[1 * kLdsStride + lane];
+    first1 = act ? a.p1h_r[b] : 0u;
     prev = first1;
+    q = p1_row1(kA, kB);
   } else {
     const uint32_t *h = K == 1 ? a.p2h_r : a.p3h_r;
     prev = act ? h[b] : 0u;
     first1 = act ? h[nr + b] : 0u;
     row2 = act ? h[2 * nr + b] : 0u;
+    q = act ? h[3 * nr + b] : 0u;
   }
   const __amdgpu_buffer_rsrc_t rs = p2_slot_rsrc(slot, b0, nr);
   const int row_bytes = (int)(nr * 4);
-  P2Piece<P2, P3> pc2;
+  P2Ahead h;
   if constexpr (K == 0) {  // step 2: row 2's final word, handed on (row 1's part needs row 1, P2c's last step)
-    row2 = (hz_lds[2 * kLdsStride + lane] ^ ((prev ^ (prev >> 30)) * 1566083941U)) - 2U;
+    q = p1_step(kInitGen.v[2], q, false, kA, kB);
+    row2 = (q ^ ((prev ^ (prev >> 30)) * 1566083941U)) - 2U;
     prev = row2;
-    p2_span<3, P1, kP2Part>(lane, rs, row_bytes, prev, s_prog);  // parts of rows 2 ..
-    p2_put(pc1, lane);
-    p2_load(pc2, slot, nr, b0, lane);
-    p2_span<P1, P2, kP2Part>(lane, rs, row_bytes, prev, s_prog);
-    p2_put(pc2, lane);
-    constexpr int G = P2 + 8 * ((kP2aEnd - P2) / 8);
-    p2_span<P2, G, kP2Part>(lane, rs, row_bytes, prev, s_prog);
-    p2_tail<G, kP2aEnd, kP2Part>(lane, rs, row_bytes, prev);    // .. 207
+    p2_ahead_init<3>(h, q, kA, kB);
+    constexpr int G = 3 + 8 * ((kP2aEnd - 3) / 8);
+    p2_span<3, G, kP2Part>(lane, rs, row_bytes, prev, h, kA, kB, s_prog);  // parts of rows 2 ..
+    p2_tail<G, kP2aEnd, kP2Part>(lane, rs, row_bytes, prev, h);             // .. 207
   } else if constexpr (K == 1) {
     static_assert(kAheadTwist + 1 - kP2aEnd == 16, "P2b's part steps: two groups");
-    p2_span<kP2aEnd, kAheadTwist + 1, kP2Part>(lane, rs, row_bytes, prev, s_prog);  // parts of rows 208-223
+    p2_ahead_init<kP2aEnd>(h, q, kA, kB);
+    p2_span<kP2aEnd, kAheadTwist + 1, kP2Part>(lane, rs, row_bytes, prev, h, kA, kB, s_prog);  // parts of rows 208-223
     __builtin_amdgcn_raw_buffer_store_b32(prev, rs, lane * 4, kAheadTwist * row_bytes, HZ_P2_AUX);  // row 224's final word
-    p2_span<kAheadTwist + 1, P1, kP2Final>(lane, rs, row_bytes, prev, s_prog);
-    p2_put(pc1, lane);
-    p2_load(pc2, slot, nr, b0, lane);
-    p2_span<P1, P2, kP2Final>(lane, rs, row_bytes, prev, s_prog);
-    p2_put(pc2, lane);
-    p2_span<P2, kP2bEnd, kP2Final>(lane, rs, row_bytes, prev, s_prog);
+    p2_span<kAheadTwist + 1, kP2bEnd, kP2Final>(lane, rs, row_bytes, prev, h, kA, kB, s_prog);
   } else {
     // rows 0 and 1 of the next generation are P2c's own last words: their
     // far rows (397, 398: P2b's) loaded now, used after the chain
     const uint32_t f0 = act ? slot[(size_t)397 * nr + b] : 0u, f1 = act ? slot[(size_t)398 * nr + b] : 0u;
-    p2_span<kP2bEnd, P1, kP2Keep>(lane, rs, row_bytes, prev, s_prog);
-    p2_put(pc1, lane);
-    p2_load(pc2, slot, nr, b0, lane);
-    p2_span<P1, P2, kP2Keep>(lane, rs, row_bytes, prev, s_prog);
-    p2_put(pc2, lane);
-    constexpr int G = P2 + 8 * ((kMT - P2) / 8);
-    p2_span<P2, G, kP2Keep>(lane, rs, row_bytes, prev, s_prog);
-    p2_tail<G, kMT, kP2Keep>(lane, rs, row_bytes, prev);
+    p2_ahead_init<kP2bEnd>(h, q, kA, kB);
+    constexpr int G = kP2bEnd + 8 * ((kMT - kP2bEnd) / 8);
+    p2_span<kP2bEnd, G, kP2Keep>(lane, rs, row_bytes, prev, h, kA, kB, s_prog);
+    p2_tail<G, kMT, kP2Keep>(lane, rs, row_bytes, prev, h);
     p2_publish(s_prog, kMT);
     const uint32_t row1 = (first1 ^ ((prev ^ (prev >> 30)) * 1566083941U)) - 1U;  // the last step, at i = 1
     // mt[0] = 0x80000000 after init_by_array; row 1's next row is row 2
@@ -2097,14 +2111,15 @@ __device__ __forceinline__ void p2_third(const P2Args &a, int b0, int lane, int 
   }
   if (K < 2) {
     if (ok) {
-      uint32_t *h = K == 0 ? a.p2h_w : a.p3h_w;
-      h[b] = prev;
-      h[nr + b] = first1;
-      h[2 * nr + b] = row2;
-      a.s_tag[2 + K][b] = e * 8 + 3 + K;
+      uint32_t *ho = K == 0 ? a.p2h_w : a.p3h_w;
+      ho[b] = prev;
+      ho[nr + b] = first1;
+      ho[2 * nr + b] = row2;
+      ho[3 * nr + b] = h.last;
+      a.s_tag[1 + K][b] = e * 8 + 3 + K;
     }
   } else if (ok) {
-    a.s_tag[4][b] = e * 8 + 5;
+    a.s_tag[3][b] = e * 8 + 5;
   }
 }
 
@@ -2127,7 +2142,7 @@ __device__ __forceinline__ uint4 xor4(const uint4 &a, const uint4 &b) {
 __device__ __forceinline__ void p2_twist(const P2Args &a, int b0, int lane, bool any, int *s_prog) {
   if (!any) return;
   const size_t nr = (size_t)a.nrow;
-  uint32_t *slot = a.s_mt[4];
+  uint32_t *slot = a.s_mt[3];
   const int grp = lane >> 4, c4 = (lane & 15) * 4;
   uint32_t *col = slot + b0 + c4;
   auto row = [&](int r) { return p2_ld4(col + (size_t)r * nr); };
@@ -2187,8 +2202,8 @@ __device__ __forceinline__ void p2_seed(const P2Args &a, int blk) {
   // each stage's episode and decision (and P2c's for the twist wave), read
   // before the barrier, so before any wave rewrites a tag
   const int k = w < 3 ? w : 2;
-  const int e = act ? a.ep_in[b] + kP2Last - 2 - k : 0;
-  const bool ok = act && a.s_tag[2 + k][b] == e * 8 + 2 + k;
+  const int e = act ? a.ep_in[b] + kP2Last - 1 - k : 0;
+  const bool ok = act && (k == 0 ? a.p1t_r[b] : a.s_tag[1 + k][b]) == e * 8 + 2 + k;
   __syncthreads();
   if (w == 0) p2_third<0>(a, b0, lane, e, ok, &s_prog);
   else if (w == 1) p2_third<1>(a, b0, lane, e, ok, &s_prog);
@@ -2213,13 +2228,13 @@ __device__ __forceinline__ void p2_draw_stage(const P2Args &a, int b0, int lane,
 #endif
   const bool act = b < a.n;
   const size_t nr = (size_t)a.nrow;
-  const int d0 = kP2DCut[stage], d1 = stage == 3 ? a.draws : min(a.draws, kP2DCut[stage + 1]);
-  const int e = act ? a.ep_in[b] + kP2Last - 5 - stage : 0;
-  const uint32_t *slot = a.s_mt[5 + stage];
-  int32_t *cur = a.s_cur[5 + stage] + b;
+  const int d0 = a.dcut[stage], d1 = stage == kP2Draw - 1 ? a.draws : min(a.draws, a.dcut[stage + 1]);
+  const int e = act ? a.ep_in[b] + kP2Last - kP2SDraw - stage : 0;
+  const uint32_t *slot = a.s_mt[kP2SDraw + stage];
+  int32_t *cur = a.s_cur[kP2SDraw + stage] + b;
   const P2Draw &in = a.x_r[stage > 0 ? stage - 1 : 0];
-  const P2Draw &out = stage == 3 ? a.pl_w : a.x_w[stage];
-  bool ok = act && a.s_tag[5 + stage][b] == e * 8 + 5;
+  const P2Draw &out = stage == kP2Draw - 1 ? a.pl_w : a.x_w[stage < kP2Draw - 1 ? stage : 0];
+  bool ok = act && a.s_tag[kP2SDraw + stage][b] == e * 8 + 5;
   int k0 = 0, c0 = kMTAhead;
   uint64_t bag = initial_bag(), q[kAheadWords] = {0, 0, 0, 0};
   if (stage > 0 && act) {  // (one round trip: used only if the tag matches)
@@ -2290,29 +2305,28 @@ __device__ __forceinline__ void p2_draw_stage(const P2Args &a, int b0, int lane,
   p2_st(&out.tag[b], e * 8 + stage + 1);
 }
 
-// the rule hashes of D4's episode (read by the play stages in the next
-// kP2Play calls)
+// the rule hashes of the last draw stage's episode (read by the play stages
+// in the next kP2Play calls)
 __device__ __forceinline__ void p2_hashes(const P2Args &a, int b) {
   const size_t nr = (size_t)a.nrow;
-  const int e = a.ep_in[b] + kP2Last - 8;
+  const int e = a.ep_in[b] + kP2Last - (kP2SPlay - 1);
   const uint64_t rk = rule_key(episode_seed(a.seed_base, b, e));
 #pragma unroll 1
   for (int j = 0; j < kRulePlies; j++) p2_st(&a.h_w[(size_t)j * nr + b], rule_h32(rk, j));
   a.ht_w[b] = e;
 }
 
-// draw-X blocks: D1 (wave 0), D2 (wave 1), P1b (wave 2), the rule hashes
-// (wave 3); draw-Y blocks: D3, D4 (waves 0, 1), P1a (wave 2).  Each draw
-// wave stages its own window and reads only it.
-__device__ __forceinline__ void p2_draw(const P2Args &a, int blk, int y) {
+// a wave of a draw-X or draw-Y block that runs no play stage (kP2Wave):
+// a draw stage, which stages its own window (the wave's) and reads only it,
+// P1, or the rule hashes
+__device__ __forceinline__ void p2_draw(const P2Args &a, int blk, int code) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int b0 = blk * kBlock;
-  if (w < 2) {
-    p2_draw_stage(a, b0, lane, 2 * y + w, w * kP2WinRows * kLdsStride);
-  } else if (w == 2 && b0 + lane < a.n) {
-    if (y) p2_p1a(a, b0, lane);
-    else p2_p1b(a, b0, lane);
-  } else if (w == 3 && !y && b0 + lane < a.n) {
+  if (code < kP2Draw) {
+    p2_draw_stage(a, b0, lane, code, w * kP2WinRows * kLdsStride);
+  } else if (code == kWvP1 && b0 + lane < a.n) {
+    p2_p1(a, b0 + lane);
+  } else if (code == kWvHash && b0 + lane < a.n) {
     p2_hashes(a, b0 + lane);
   }
 }
@@ -2347,12 +2361,15 @@ __device__ __forceinline__ PlayDraw2 p2_mid_get(const P2Mid &m, size_t nr, int b
                    MTR(slot, (int)nr, fc >= 0 ? fc : 0), cur + (size_t)nd * nr};
 }
 
-// play blocks: wave 3 - st runs play stage st on episode ep + kP2Play - 1 -
-// st (the last stage, wave 0: the rest of episode ep, or all of it).  The
-// stages run one code path (st wave-uniform), so the block's four waves
-// share one copy of the ply loop in the instruction cache (one inlined copy
-// per stage, ~50 KB each, thrashed the cache the two CUs of a pair share).
-__device__ __forceinline__ void p2_play(const P2Args &a, int blk) {
+// Play stage st on episode ep + kP2Play - 1 - st (the last stage: the rest of
+// episode ep, or all of it).  In a play block (in_block) wave w runs stage
+// kP2Play - 1 - w, the last on wave 0 with its LDS fallback; with five stages,
+// stage 0 runs on a wave of a draw block (kWvPlay: it needs no LDS and joins
+// no barrier).  The stages run one code path (st wave-uniform), so a block's
+// waves share one copy of the ply loop in the instruction cache (one inlined
+// copy per stage, ~50 KB each, thrashed the cache the two CUs of a pair
+// share), and k_play2 calls this from one place.
+__device__ __forceinline__ void p2_play(const P2Args &a, int blk, int st, bool in_block) {
   __shared__ uint64_t s_lds_mask;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int b0 = blk * kBlock, b = b0 + lane;
@@ -2363,7 +2380,6 @@ __device__ __forceinline__ void p2_play(const P2Args &a, int blk) {
 #ifdef HZ_DIAG
   const uint64_t t0 = __builtin_amdgcn_s_memtime();
 #endif
-  const int st = __builtin_amdgcn_readfirstlane(kP2Play - 1 - w);  // 0 playA .. kP2Play - 1 the last
   const bool last = st == kP2Play - 1;
   bool lds_used = false;
   if (act) {
@@ -2371,9 +2387,9 @@ __device__ __forceinline__ void p2_play(const P2Args &a, int blk) {
     const P2Draw &pl = a.pl_r[st];
     const uint32_t *hsrc = a.h_r[st];
     const int32_t *htag = a.ht_r[st];
-    uint32_t *slot = a.s_mt[9 + st] + b;
-    const int32_t *cur = a.s_cur[9 + st] + b;
-    const int g_end = last ? a.max_plies : min(a.cut[st], a.max_plies);
+    uint32_t *slot = a.s_mt[kP2SPlay + st] + b;
+    const int32_t *cur = a.s_cur[kP2SPlay + st] + b;
+    const int g_end = last ? a.max_plies : min(a.cut[st < kP2Play - 1 ? st : 0], a.max_plies);
     const uint64_t sd = episode_seed(a.seed_base, b, e), rk = rule_key(sd);
     // every input's loads issued together (used only if the tags match)
     const int ptag = pl.tag[b], nd = pl.k[b];
@@ -2384,18 +2400,18 @@ __device__ __forceinline__ void p2_play(const P2Args &a, int blk) {
     PlayDraw2 draw = st == 0 ? PlayDraw2{pl.q[b], pl.q[nr + b], pl.q[2 * nr + b], pl.q[3 * nr + b], 0, nd, false,
                                          MTR(slot, (int)nr, 0), cur + (size_t)nd * nr}
                              : p2_mid_get(a.m_r[st - 1], nr, b, s, g, nd, slot, cur);
-    const bool prep = ptag == e * 8 + 4 && mtag == e;
+    const bool prep = ptag == e * 8 + kP2Draw && mtag == e;
     if (prep) {
       if (st == 0) {
         if (__all(nd >= 5)) draw.scripted_reset(s);
         else reset_state(s, draw);
       }
-      P2_PHASE(16 + 3 * st, t0);
+      P2_PHASE(16 + 2 * st, t0);
       g += p2_plies(s, draw, g, g_end, rk, hs, nr);
-      P2_PHASE(17 + 3 * st, t0);
+      P2_PHASE(17 + 2 * st, t0);
     }
     if (!last) {
-      const P2Mid &mo = a.m_w[st];
+      const P2Mid &mo = a.m_w[st < kP2Play - 1 ? st : 0];
       if (prep) p2_mid_put(mo, nr, b, s, draw, g, e);
       else mo.tag[b] = -1;
     } else {
@@ -2426,9 +2442,10 @@ __device__ __forceinline__ void p2_play(const P2Args &a, int blk) {
       if (a.steps_done) a.steps_done[b] = g;
     }
 #ifdef HZ_DIAG
-    if (g_stamps) g_stamps[(size_t)b * kP2Stamps + w] = __builtin_amdgcn_s_memtime() - t0;  // last .. playA
+    if (g_stamps && in_block) g_stamps[(size_t)b * kP2Stamps + w] = __builtin_amdgcn_s_memtime() - t0;  // last .. second
 #endif
   }
+  if (!in_block) return;
   if (w == 0) {
     const uint64_t lm = __ballot(lds_used);
     if (lane == 0) s_lds_mask = lm;
@@ -2439,24 +2456,29 @@ __device__ __forceinline__ void p2_play(const P2Args &a, int blk) {
 }
 
 // one 162 KB-LDS block per CU, so one wave per SIMD: every wave may use the
-// whole register file (the P2b twist wave keeps 57 rows in registers)
+// whole register file
 __global__ void __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) k_play2(P2Args a, int nblk) {
   const int blk = (int)blockIdx.x;
   const int role = blk / nblk;  // 0 play, 1 draw X, 2 draw Y, 3 seed blocks
   const int rb = blk - role * nblk;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int code = role == 1 || role == 2 ? kP2Wave[4 * (role - 1) + wv] : kWvIdle;
+  // the wave's play stage, if it runs one
+  const int st = role == 0 ? kP2Play - 1 - wv : code == kWvPlay ? 0 : -1;
 #ifdef HZ_DIAG
   if (g_role_only >= 0 && g_role_only != role) return;
   const uint64_t t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
 #endif
-  if (role == 0) p2_play(a, rb);
+  if (st >= 0) p2_play(a, rb, st, role == 0);
   else if (role == 3) p2_seed(a, rb);
-  else p2_draw(a, rb, role - 1);
+  else if (role != 0) p2_draw(a, rb, code);
 #ifdef HZ_DIAG
-  {  // wave durations per board, slot 4 role + wave: 0-3 play (D, C, B, A:
-     // stamped in p2_play, before its barrier), 4-7 draw X (D1, D2, P1b,
-     // hashes), 8-10 draw Y (D3, D4, P1a), 12-15 seed (P2a, P2b, P2c, twist)
+  {  // wave durations per board, slot 4 role + wave: 0-3 play (the last stage
+     // .. the second: stamped in p2_play, before its barrier), 4-7 draw X,
+     // 8-11 draw Y (kP2Wave says what each runs), 12-15 seed (P2a, P2b, P2c,
+     // twist)
     const int w = threadIdx.x >> 6, bb = rb * kBlock + (threadIdx.x & 63);
-    const bool idle = role == 2 && w == 3;
+    const bool idle = (role == 1 || role == 2) && code == kWvIdle;
     if (g_stamps && role > 0 && !idle && bb < a.n) g_stamps[(size_t)bb * kP2Stamps + 4 * role + w] = __builtin_amdgcn_s_memtime() - t0;
     // the wave's realtime (100 MHz) start and end and its clock cycles, per
     // (role, wave): slot 40 of the block's boards 16 role + 4 w + k
@@ -2642,7 +2664,9 @@ static int p2_clear_tags(hz_env *e) {
   auto c = [&](int32_t *t) { return hipMemsetAsync(t, 0xff, bytes, e->stream) != hipSuccess; };
   for (int k = 0; k < kP2Stream; k++)
     if (c(e->p2_s_tag[k])) return 1;
-  for (int k = 0; k < 3; k++)
+  for (int k = 0; k < 2; k++)
+    if (c(e->p2_p1t[k])) return 1;
+  for (int k = 0; k < kP2Draw - 1; k++)
     if (c(e->p2_x[k][0].tag) || c(e->p2_x[k][1].tag)) return 1;
   for (int k = 0; k < kP2Ring; k++)
     if (c(e->p2_pl[k].tag) || c(e->p2_h_tag[k])) return 1;
@@ -2651,8 +2675,8 @@ static int p2_clear_tags(hz_env *e) {
   return 0;
 }
 
-// allocated on first use: 14 stream slots of 2.5 KB per board plus ~1.9 KB
-// of hand-offs per board
+// allocated on first use: kP2Stream stream slots of 2.5 KB per board plus
+// ~2.3 KB of hand-offs per board
 static int alloc_p2(hz_env *e) {
   if (e->p2_s[0]) return 0;
   const size_t nr = e->nrow;
@@ -2669,7 +2693,7 @@ static int alloc_p2(hz_env *e) {
     o.get(d.bag, nr * 8);
     o.get(d.c, nr * 4);
   };
-  for (int k = 0; k < 3; k++) md(e->p2_x[k][0]), md(e->p2_x[k][1]);
+  for (int k = 0; k < kP2Draw - 1; k++) md(e->p2_x[k][0]), md(e->p2_x[k][1]);
   for (int k = 0; k < kP2Ring; k++) {
     md(e->p2_pl[k]);
     o.get(e->p2_h[k], kRulePlies * nr * 4);
@@ -2685,8 +2709,9 @@ static int alloc_p2(hz_env *e) {
     }
   for (int k = 0; k < 2; k++) {
     o.get(e->p2_p1h[k], nr * 4);
-    o.get(e->p2_p2h[k], 3 * nr * 4);
-    o.get(e->p2_p3h[k], 3 * nr * 4);
+    o.get(e->p2_p1t[k], nr * 4);
+    o.get(e->p2_p2h[k], 4 * nr * 4);
+    o.get(e->p2_p3h[k], 4 * nr * 4);
     o.get(e->p2_ep[k], nr * 4);
   }
   if (!o.ok || p2_clear_tags(e)) {
@@ -2698,10 +2723,12 @@ static int alloc_p2(hz_env *e) {
 }
 
 // one hz_play call of pipeline 2 (k_play2).  Call c uses stream slot
-// (c - s) % kP2Stream for stage s; the D1 -> D2 -> D3 -> D4 hand-offs, P1a ->
-// P1b and play stage st -> st + 1 by call parity; D4's script and the rule
-// hashes in rings of kP2Ring (read by play stage st st + 1 calls later).  Every slot written by call c is read by call c + 1 or later,
-// so launch order on the stream is the only synchronisation.
+// (c - s) % kP2Stream for stage s >= 1 (P1, stage 0, has none); the draw
+// stages' hand-offs, P1 -> P2a -> P2b -> P2c and play stage st -> st + 1 by
+// call parity; the last draw stage's script and the rule hashes in rings of
+// kP2Ring (read by play stage st st + 1 calls later).  Every slot written by
+// call c is read by call c + 1 or later, so launch order on the stream is the
+// only synchronisation.
 static int launch_play2(hz_env *e, int32_t max_plies, int32_t *games_done, int32_t *steps_done) {
   streams_touched(e);  // (may move or rewrite streams: PlyWin; hz_play checked e)
   if (alloc_p2(e)) return 1;
@@ -2725,6 +2752,7 @@ static int launch_play2(hz_env *e, int32_t max_plies, int32_t *games_done, int32
   a.err = e->wait_err;
   a.spin = e->spin_limit;
   for (int k = 0; k < kP2Play - 1; k++) a.cut[k] = e->p2_cut[k];
+  for (int k = 0; k <= kP2Draw; k++) a.dcut[k] = e->p2_dcut[k];
   a.seed_base = e->seed_base;
   a.nrow = (long)e->nrow;
   a.games_done = games_done;
@@ -2733,7 +2761,7 @@ static int launch_play2(hz_env *e, int32_t max_plies, int32_t *games_done, int32
   a.ep_in = e->p2_ep[w];
   a.ep_out = e->p2_ep[r];
   auto sl = [c](int s) { return ((c - s) % kP2Stream + kP2Stream) % kP2Stream; };
-  for (int s = 0; s < kP2Stages; s++) {
+  for (int s = 1; s < kP2Stages; s++) {
     a.s_mt[s] = e->p2_s[sl(s)];
     a.s_tag[s] = e->p2_s_tag[sl(s)];
     a.s_cur[s] = e->p2_s_cur[sl(s)];
@@ -2741,11 +2769,13 @@ static int launch_play2(hz_env *e, int32_t max_plies, int32_t *games_done, int32
   a.s_idx_last = sl(kP2Last);
   a.p1h_w = e->p2_p1h[r];
   a.p1h_r = e->p2_p1h[w];
+  a.p1t_w = e->p2_p1t[r];
+  a.p1t_r = e->p2_p1t[w];
   a.p2h_w = e->p2_p2h[r];
   a.p2h_r = e->p2_p2h[w];
   a.p3h_w = e->p2_p3h[r];
   a.p3h_r = e->p2_p3h[w];
-  for (int k = 0; k < 3; k++) {
+  for (int k = 0; k < kP2Draw - 1; k++) {
     a.x_w[k] = e->p2_x[k][r];
     a.x_r[k] = e->p2_x[k][w];
   }
@@ -2766,7 +2796,7 @@ static int launch_play2(hz_env *e, int32_t max_plies, int32_t *games_done, int32
   hipLaunchKernelGGL(k_play2, dim3(4 * nblk), dim3(kStageThreads), kResetLds, e->stream, a, nblk);
   if (int err = launch_err()) return err;
   e->lazy = 1;
-  e->calls2 = (c + 1) % (kP2Stream * kP2Ring * 2);  // (a multiple of every ring length)
+  e->calls2 = (c + 1) % (kP2Stream * kP2Ring * 2);  // (a multiple of every ring length: slots, script ring, parity)
   e->primed = 0;  // the other pipeline's episode prediction is stale now
   e->ar_primed = 0;
   return 0;
@@ -2820,13 +2850,25 @@ hz_env *hz_env_create(int32_t n_boards, uint64_t seed_base, void *stream) {
   e->ar_ahead = env_pick("HZ_AR_AHEAD", 0, 1);
   // hz_play's pipeline: 2 by default, HZ_PIPELINE=1 for the first (hz_env_set_pipeline)
   e->pipeline = env_pick("HZ_PIPELINE", 1, 2);
-  // HZ_P2_CUTS="a,b,c": pipeline 2's play stage boundaries (plies,
+  // HZ_P2_CUTS5="a,b,c,d": pipeline 2's play stage boundaries (plies,
   // increasing multiples of 4: whole turns; a stage that starts at player
-  // 1's turn plays single plies up to the next turn pair)
-  e->p2_cut[0] = 24;
-  e->p2_cut[1] = 40;
-  e->p2_cut[2] = 56;
-  env_cuts("HZ_P2_CUTS", e->p2_cut);
+  // 1's turn plays single plies up to the next turn pair).  HZ_P2_CUTS, the
+  // three boundaries of four play stages, is read only by a build with four.
+  for (int k = 0; k < kP2Play - 1; k++) e->p2_cut[k] = kP2PCut[k];
+  if constexpr (kP2Play == 4) env_cuts("HZ_P2_CUTS", e->p2_cut);
+  else if constexpr (kP2Play == 5) env_cuts_n("HZ_P2_CUTS5", e->p2_cut, kP2Play - 1, 4, 1 << 20);
+  // HZ_P2_DCUTS="a,b,c,d": the first draws of draw stages 2..5 (increasing,
+  // 1..23; stage 1 starts at draw 0; no stage more than kP2StageDraws draws,
+  // else the setting is ignored)
+  for (int k = 0; k < kP2Draw; k++) e->p2_dcut[k] = kP2DCut[k];
+  e->p2_dcut[kP2Draw] = kAheadDraws;
+  if constexpr (kP2Draw == 5) {
+    int dc[kP2Draw + 1];
+    for (int k = 0; k <= kP2Draw; k++) dc[k] = e->p2_dcut[k];
+    if (env_cuts_n("HZ_P2_DCUTS", dc + 1, kP2Draw - 1, 1, kAheadDraws - 1) &&
+        cuts_gaps_within(dc, kP2Draw + 1, kP2StageDraws))
+      for (int k = 0; k <= kP2Draw; k++) e->p2_dcut[k] = dc[k];
+  }
   e->mt_epoch = 1;
   e->wait_err = e->wait_err_own;
   e->spin_limit = kSpinLimitDefault;

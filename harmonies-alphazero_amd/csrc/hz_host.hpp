@@ -1,6 +1,6 @@
 // hz_host.hpp — the host layer the three .hip files share: no device code.
 //
-//   env_int / env_pick / env_clamped / env_cuts, Setting : the environment knobs
+//   env_int / env_pick / env_clamped / env_cuts(_n), Setting : the environment knobs
 //   DevBufsT<Dev>                                        : owner of device buffers
 //   streams_touched(e)                                   : the stream epoch
 //   launch_err(), lds_opt_in<Kernel>(bytes)              : launch helpers (HIP only)
@@ -49,6 +49,33 @@ inline void env_cuts(const char *name, int cut[3]) {
   if (e && sscanf(e, "%d,%d,%d", &c[0], &c[1], &c[2]) == 3 && c[0] > 0 && c[1] > c[0] && c[2] > c[1] &&
       c[0] % 4 == 0 && c[1] % 4 == 0 && c[2] % 4 == 0)
     for (int k = 0; k < 3; k++) cut[k] = c[k];
+}
+
+// "a,b,...": exactly n (1..8) increasing multiples of step in [step, hi],
+// comma-separated with nothing after them, replace cut[] and give true;
+// anything else (unset included) leaves cut[] as it is
+inline bool env_cuts_n(const char *name, int *cut, int n, int step, int hi) {
+  const char *e = getenv(name);
+  if (!e || n < 1 || n > 8 || step < 1) return false;
+  int c[8];
+  for (int k = 0; k < n; k++) {
+    if (*e < '0' || *e > '9') return false;  // (no sign, no blanks)
+    long v = 0;
+    for (; *e >= '0' && *e <= '9'; e++)
+      if ((v = v * 10 + (*e - '0')) > hi) return false;
+    if (v < step || v % step || (k && v <= c[k - 1])) return false;
+    c[k] = (int)v;
+    if (*e++ != (k + 1 < n ? ',' : '\0')) return false;
+  }
+  for (int k = 0; k < n; k++) cut[k] = c[k];
+  return true;
+}
+
+// whether no two neighbours of the n values are more than max_gap apart
+inline bool cuts_gaps_within(const int *cut, int n, int max_gap) {
+  for (int k = 0; k + 1 < n; k++)
+    if (cut[k + 1] - cut[k] > max_gap) return false;
+  return true;
 }
 
 // A process-wide knob that a setter of the ABI can override: env_int(name,

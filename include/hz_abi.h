@@ -152,8 +152,8 @@ int hz_play(hz_env *env, int32_t max_plies, int32_t auto_reset, uint64_t *traj_s
 int hz_env_set_seed_ahead(hz_env *env, int32_t draws);
 /* hz_play's pipeline: 2 (the default; HZ_PIPELINE=1 in the environment at
  * hz_env_create makes 1 the default) = every board's game spread over
- * thirteen consecutive calls, one stage per call (seeding pass 1 in two
- * stages, pass 2 in three, four draw stages, four play stages), all thirteen
+ * fourteen consecutive calls, one stage per call (seeding pass 1 in one
+ * stage, pass 2 in three, five draw stages, five play stages), all fourteen
  * running in each launch on different episodes; 1 = the chance-ahead
  * pipeline above.  Same results either way; pipeline 2 applies to calls with
  * auto_reset = 0, no trajectory outputs and max_plies >= 96 (others take

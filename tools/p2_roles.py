@@ -18,12 +18,13 @@ out = {}
 for pipe in (1, 2):
     env = BatchedEnv(n, device="cuda")
     env.set_pipeline(pipe)
-    names = ({0: "playD", 1: "playC", 2: "playB", 3: "playA", 4: "D1", 5: "D2", 6: "P1b", 7: "hashes", 8: "D3",
-              9: "D4", 10: "P1a", 12: "P2a", 13: "P2b", 14: "P2c", 15: "twist",
-              16: "playA_loaded", 17: "playA_plies", 19: "playB_loaded", 20: "playB_plies",
-              22: "playC_loaded", 23: "playC_plies", 25: "playD_loaded", 26: "playD_plies", 27: "playD_scored",
-              28: "D1_staged", 29: "D2_staged", 30: "D3_staged", 31: "D4_staged",
-              32: "P2a_staged", 33: "P2b_staged", 34: "P2c_staged",
+    # (the draw blocks' waves as hz_env.hip's default HZ_P2_WAVES places them)
+    names = ({0: "playE", 1: "playD", 2: "playC", 3: "playB", 4: "D1", 5: "D2", 6: "D5", 7: "hashes", 8: "D3",
+              9: "D4", 10: "P1", 11: "playA", 12: "P2a", 13: "P2b", 14: "P2c", 15: "twist",
+              16: "playA_loaded", 17: "playA_plies", 18: "playB_loaded", 19: "playB_plies",
+              20: "playC_loaded", 21: "playC_plies", 22: "playD_loaded", 23: "playD_plies",
+              24: "playE_loaded", 25: "playE_plies", 27: "playE_scored",
+              28: "D1_staged", 29: "D2_staged", 30: "D3_staged", 31: "D4_staged", 32: "D5_staged",
               35: "twist_go", 36: "twist_it1", 37: "twist_looped", 38: "twist_done_seen"} if pipe == 2 else
              {5: "play", 6: "draw2", 15: "draw1", 7: "seed"})
     for only in (-1, 0, 1, 2, 3) if pipe == 2 else (-1,):

@@ -38,7 +38,8 @@ if ROLE >= 0:
     torch.cuda.synchronize()
     L.hz_diag_set_role_only(-1)
 s = stamps[:, 40].cpu().numpy().astype(np.int64).reshape(-1, 64)  # [block][16 role + 4 w + k]
-names = {0: ["playD", "playC", "playB", "playA"], 1: ["D1", "D2", "P1b", "hashes"], 2: ["D3", "D4", "P1a", "idle"],
+# (the draw blocks' waves as hz_env.hip's default HZ_P2_WAVES places them)
+names = {0: ["playE", "playD", "playC", "playB"], 1: ["D1", "D2", "D5", "hashes"], 2: ["D3", "D4", "P1", "playA"],
          3: ["P2a", "P2b", "P2c", "twist"]}
 rs, re_, ts, te = (s[:, k::4] for k in range(4))  # [block][role * 4 + w]
 valid = rs > 0
@@ -87,8 +88,8 @@ out["cus_used"] = len(per_cu)
 # the last episode column's in-stage phases (cycles since the stage began;
 # tools/p2_roles.py's slot names)
 ph = stamps.cpu().numpy().astype(np.int64)
-pnames = {16: "playA_loaded", 17: "playA_plies", 25: "playD_loaded", 26: "playD_plies", 27: "playD_scored",
-          28: "D1_staged", 30: "D3_staged", 32: "P2a_staged", 33: "P2b_staged", 34: "P2c_staged",
+pnames = {16: "playA_loaded", 17: "playA_plies", 24: "playE_loaded", 25: "playE_plies", 27: "playE_scored",
+          28: "D1_staged", 30: "D3_staged", 32: "D5_staged",
           35: "twist_go", 36: "twist_it1", 37: "twist_looped"}
 out["phases_last_column"] = {nm: [float(ph[:, k].max()), float(np.median(ph[:, k]))] for k, nm in pnames.items()}
 out["longest"] = max((v["dur_max"], k) for k, v in waves.items())
