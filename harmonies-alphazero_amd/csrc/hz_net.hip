@@ -472,13 +472,19 @@ alignas(16) __constant__ int16_t kX6C4Row[9][16] = {
 // chain (8 states: ~175 k cycles, ~73 us, however few states are live), and
 // the arena's batches of a few dozen boards fill only a few CUs; one state
 // per group cuts each wave's chain to a third at 48/35 rows of waste.
-template <int NQ, bool Stem, int CS, int NCB>
+// Ord: the piece products kept are those with pa + pb <= Ord.  2 (all six:
+// fp32-exact products), 1 (hh, hm, mh: 3 * 2^-18 relative per product) or 0
+// (hh alone: plain bf16), in the same relative order (tap by tap, pa outer,
+// pb inner); a reduced form stages, loads and reads only the planes 0..Ord
+// (hz_conv3x3_xn_bias_act; the 1- and 8-state tower conv only).
+template <int NQ, bool Stem, int CS, int NCB, int Ord = 2>
 __global__ void __launch_bounds__((CS == 8 ? 2 : 1) * (8 / NCB) * 64, CS == 4 ? 2 : 1)
     k_conv3x3_x6(const float *__restrict__ x, const bf16x8 *__restrict__ wp, const float *__restrict__ bias,
                  const float *__restrict__ res, float *__restrict__ out, int32_t batch,
                  const int32_t *__restrict__ live) {
   static_assert(CS == 8 || CS == 4 || CS == 1, "8, 4 or 1 states per workgroup");
   static_assert(NCB == 2 || NCB == 1, "column blocks of 16 output channels per wave");
+  static_assert(Ord == 2 || (Ord >= 0 && Ord < 2 && !Stem && CS != 4), "reduced orders: the 1- and 8-state tower conv");
   constexpr int kRowsT = CS * 35;                  // output rows of the group
   constexpr int kRBT = CS == 1 ? 3 : 9;            // row blocks of 16 per wave
   constexpr int kCG = 8 / NCB;                     // column groups (waves per row group)
@@ -583,10 +589,12 @@ __global__ void __launch_bounds__((CS == 8 ? 2 : 1) * (8 / NCB) * 64, CS == 4 ? 
     split4(stg[it], h_, m_, l_);                                                          \
     char *d_ = lds + (buf) * kBufT + ldst[it];                                            \
     *(uint2 *)d_ = h_;                                                                    \
-    *(uint2 *)(d_ + 64) = m_;                                                             \
-    *(uint2 *)(d_ + 128) = l_;                                                            \
+    if constexpr (Ord >= 1) *(uint2 *)(d_ + 64) = m_;                                     \
+    if constexpr (Ord >= 2) *(uint2 *)(d_ + 128) = l_;                                    \
     pieces |= m_.x | m_.y | l_.x | l_.y;                                                  \
   }
+  // (Ord < 2: the planes past Ord are neither stored nor read, and split4's
+  // subtraction chain for the unused pieces goes with them)
   // the chunk's A pieces m, l are all zero (every staged value is a bf16
   // value: an encoder board's stem input): only the h plane's three products
   // are issued.  Workgroup-uniform; the tower always takes all six.
@@ -683,7 +691,7 @@ __global__ void __launch_bounds__((CS == 8 ? 2 : 1) * (8 / NCB) * 64, CS == 4 ? 
 
   bf16x8 b[3][NCB], bn[3][NCB];  // this K-step's B fragments, the next step's (loaded a step ahead)
 #pragma unroll
-  for (int p = 0; p < 3; p++)
+  for (int p = 0; p <= Ord; p++)
 #pragma unroll
     for (int cb = 0; cb < NCB; cb++) b[p][cb] = bload(0, p, cb);
 
@@ -699,11 +707,11 @@ __global__ void __launch_bounds__((CS == 8 ? 2 : 1) * (8 / NCB) * 64, CS == 4 ? 
       for (int tap = 0; tap < 9; tap++) {
         const int L = q * 9 + tap, Ln = L + 1 < 9 * NQ ? L + 1 : 9 * NQ - 1;
 #pragma unroll
-        for (int p = 0; p < 3; p++)
+        for (int p = 0; p <= Ord; p++)
 #pragma unroll
           for (int cb = 0; cb < NCB; cb++) bn[p][cb] = bload(Ln, p, cb);
 #pragma unroll
-        for (int pa = 0; pa < 3; pa++) {
+        for (int pa = 0; pa <= Ord; pa++) {
           if (Stem && pa >= npa) break;  // the chunk's A pieces m, l are zero (stem on encoder boards)
           bf16x8 a[kRBT];
 #pragma unroll
@@ -718,7 +726,7 @@ __global__ void __launch_bounds__((CS == 8 ? 2 : 1) * (8 / NCB) * 64, CS == 4 ? 
                                                     : *(const bf16x8 *)(lb - kNeg + cbase[rb] + d);
           }
 #pragma unroll
-          for (int pb = 0; pb < 3 - pa; pb++)
+          for (int pb = 0; pb <= Ord - pa; pb++)
 #pragma unroll
             for (int rb = 0; rb < kRBT; rb++)
               if ((kX6ClassTaps[H][rb] >> tap) & 1)
@@ -727,7 +735,7 @@ __global__ void __launch_bounds__((CS == 8 ? 2 : 1) * (8 / NCB) * 64, CS == 4 ? 
                   acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[rb], b[pb][cb], acc[rb][cb], 0, 0, 0);
         }
 #pragma unroll
-        for (int p = 0; p < 3; p++)
+        for (int p = 0; p <= Ord; p++)
 #pragma unroll
           for (int cb = 0; cb < NCB; cb++) b[p][cb] = bn[p][cb];
         __builtin_amdgcn_sched_barrier(0);  // taps stay in order (registers: no hoisting across)
@@ -800,19 +808,19 @@ __global__ void __launch_bounds__((CS == 8 ? 2 : 1) * (8 / NCB) * 64, CS == 4 ? 
       for (int tap = 0; tap < (packed ? 3 : 9); tap++) {
         const int L = q * 9 + tap, Ln = L + 1 < 9 * NQ ? L + 1 : 9 * NQ - 1;
   #pragma unroll
-        for (int p = 0; p < 3; p++)
+        for (int p = 0; p <= Ord; p++)
   #pragma unroll
           for (int cb = 0; cb < NCB; cb++) bn[p][cb] = bload(Ln, p, cb);
-        // plane a of A against the planes b with a + b <= 2
+        // plane a of A against the planes b with a + b <= Ord (2: all six)
   #pragma unroll
-        for (int pa = 0; pa < 3; pa++) {
+        for (int pa = 0; pa <= Ord; pa++) {
           if (pa >= npa) break;
           bf16x8 a[kRBT];
   #pragma unroll
           for (int rb = 0; rb < kRBT; rb++)
             a[rb] = *(const bf16x8 *)(lb + (packed ? aoff_tp(rb, tap) : aoff(rb, tap)) + 64 * pa);
   #pragma unroll
-          for (int pb = 0; pb < 3 - pa; pb++) {
+          for (int pb = 0; pb <= Ord - pa; pb++) {
   #pragma unroll
             for (int rb = 0; rb < kRBT; rb++)
   #pragma unroll
@@ -821,7 +829,7 @@ __global__ void __launch_bounds__((CS == 8 ? 2 : 1) * (8 / NCB) * 64, CS == 4 ? 
           }
         }
   #pragma unroll
-        for (int p = 0; p < 3; p++)
+        for (int p = 0; p <= Ord; p++)
   #pragma unroll
           for (int cb = 0; cb < NCB; cb++) b[p][cb] = bn[p][cb];
       }
@@ -1455,12 +1463,12 @@ __global__ void __launch_bounds__(256, 1)
 #undef HZ_STAMP
 #undef HZ_STAMP_RT
 
-template <int NQ, bool Stem, int CS, int NCB>
+template <int NQ, bool Stem, int CS, int NCB, int Ord = 2>
 static int launch_x6_cs(const float *x, const void *wpack6, const float *bias, const float *res, float *out,
                         int32_t batch, const int32_t *live, void *stream) {
   const size_t lds = 2 * (size_t)((CS * 35 * kX6Cell + 255) / 256 * 256 + kX6Zero);
-  if (lds_opt_in<k_conv3x3_x6<NQ, Stem, CS, NCB>>(lds)) return 1;
-  hipLaunchKernelGGL((k_conv3x3_x6<NQ, Stem, CS, NCB>), dim3((batch + CS - 1) / CS),
+  if (lds_opt_in<k_conv3x3_x6<NQ, Stem, CS, NCB, Ord>>(lds)) return 1;
+  hipLaunchKernelGGL((k_conv3x3_x6<NQ, Stem, CS, NCB, Ord>), dim3((batch + CS - 1) / CS),
                      dim3((CS == 8 ? 2 : 1) * (8 / NCB) * 64), lds, (hipStream_t)stream, x, (const bf16x8 *)wpack6,
                      bias, res, out, batch, live);
   return hipGetLastError() == hipSuccess ? 0 : 1;
@@ -1565,6 +1573,29 @@ extern "C" int hz_conv3x3_x6_bias_act(const float *x, const void *wpack6, const 
   if (((uintptr_t)x | (uintptr_t)wpack6 | (uintptr_t)out | (uintptr_t)res) & 15) return -1;
   if (batch == 0) return 0;
   return launch_x6<4, false>(x, wpack6, bias, res, out, batch, live, stream);
+}
+
+// The tower conv keeping only the piece products of order <= Ord, always in
+// the k_conv3x3_x6 forms: 8 waves of 16 channels up to x6_tiny_max() rows,
+// 4 waves of 32 up to x6_small_max(), eight states per workgroup above
+template <int Ord>
+static int launch_xn(const float *x, const void *wpack6, const float *bias, const float *res, float *out,
+                     int32_t batch, const int32_t *live, void *stream) {
+  if (batch <= x6_tiny_max()) return launch_x6_cs<4, false, 1, 1, Ord>(x, wpack6, bias, res, out, batch, live, stream);
+  return batch <= x6_small_max() ? launch_x6_cs<4, false, 1, 2, Ord>(x, wpack6, bias, res, out, batch, live, stream)
+                                 : launch_x6_cs<4, false, 8, 2, Ord>(x, wpack6, bias, res, out, batch, live, stream);
+}
+
+extern "C" int hz_conv3x3_xn_bias_act(const float *x, const void *wpack6, const float *bias, const float *res,
+                                      float *out, int32_t batch, const int32_t *live, int32_t products,
+                                      void *stream) {
+  if (products != 1 && products != 3 && products != 6) return -1;
+  if (products == 6) return hz_conv3x3_x6_bias_act(x, wpack6, bias, res, out, batch, live, stream);
+  if (!x || !wpack6 || !bias || !out || batch < 0) return -1;
+  if (((uintptr_t)x | (uintptr_t)wpack6 | (uintptr_t)out | (uintptr_t)res) & 15) return -1;
+  if (batch == 0) return 0;
+  return products == 3 ? launch_xn<1>(x, wpack6, bias, res, out, batch, live, stream)
+                       : launch_xn<0>(x, wpack6, bias, res, out, batch, live, stream);
 }
 
 // One residual block of the tower (model.py:287-299): out = relu(conv2(
@@ -1699,6 +1730,9 @@ constexpr int kTRAhead = 4;                                // K-steps of B fragm
 static_assert(35 * kX6Cell <= kTRZero && kTRZero + 255 + 128 + 16 <= kTRChunk, "cells and zero region fit");
 static_assert(36 % kTRAhead == 0, "the B ring's slots repeat every conv");
 
+// Ord as k_conv3x3_x6's: the products with pa + pb <= Ord, planes 0..Ord
+// staged, requested and read (hz_tower_xn_resident)
+template <int Ord = 2>
 __global__ void __launch_bounds__(512, 1)
     k_tower_x6_resident(const float *__restrict__ x0, const bf16x8 *__restrict__ wp,
                         const float *__restrict__ bias, float *__restrict__ out, int32_t nconv, int32_t batch,
@@ -1727,8 +1761,8 @@ __global__ void __launch_bounds__(512, 1)
     split4(v, h, m, l);
     char *d = lds + (part >> 3) * kTRChunk + cell * kX6Cell + 8 * (part & 7);
     *(uint2 *)d = h;
-    *(uint2 *)(d + 64) = m;
-    *(uint2 *)(d + 128) = l;
+    if constexpr (Ord >= 1) *(uint2 *)(d + 64) = m;
+    if constexpr (Ord >= 2) *(uint2 *)(d + 128) = l;
     *(f32x4 *)(skip + 4 * f) = v;
   }
 
@@ -1762,7 +1796,7 @@ __global__ void __launch_bounds__(512, 1)
     const int q2 = L / 9, t2 = L - 9 * q2;
     const bf16x8 *src = wl + (size_t)l * kTRConvW + (t2 * 4 + q2) * 3 * 512;
 #pragma unroll
-    for (int p = 0; p < 3; p++) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst[p]) : "v"(src + p * 512));
+    for (int p = 0; p <= Ord; p++) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst[p]) : "v"(src + p * 512));
   };
   // the B ring: K-step L of any conv in slot L % kTRAhead
   bf16x8 bq[kTRAhead][3];
@@ -1770,6 +1804,10 @@ __global__ void __launch_bounds__(512, 1)
   for (int L = 0; L < kTRAhead - 1; L++) bissue(bq[L], 0, L);
   __syncthreads();
 
+  // one copy of the conv loop's body: the ring's registers hold loads in
+  // flight across the back edge, which the compiler takes for values; a
+  // peeled or unrolled copy would move them between registers
+#pragma unroll 1
   for (int l = 0; l < nconv; l++) {
     const char *lb = lds + (l & 1) * kTRBuf;
     char *ob = lds + ((l + 1) & 1) * kTRBuf;
@@ -1785,17 +1823,23 @@ __global__ void __launch_bounds__(512, 1)
         else
           bissue(bq[Lf % kTRAhead], l + 1, Lf - 36);
         // this step's fragments have landed: only the 3 (kTRAhead - 1)
-        // requested after them may be outstanding (vmcnt counts in order)
+        // requested after them may be outstanding (vmcnt counts in order;
+        // Ord + 1 planes per step)
         bf16x8 *b = bq[L % kTRAhead];
-        asm volatile("s_waitcnt vmcnt(%3)" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]) : "n"(3 * (kTRAhead - 1)));
+        if constexpr (Ord == 2)
+          asm volatile("s_waitcnt vmcnt(%3)" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]) : "n"(3 * (kTRAhead - 1)));
+        else if constexpr (Ord == 1)
+          asm volatile("s_waitcnt vmcnt(%2)" : "+v"(b[0]), "+v"(b[1]) : "n"(2 * (kTRAhead - 1)));
+        else
+          asm volatile("s_waitcnt vmcnt(%1)" : "+v"(b[0]) : "n"(kTRAhead - 1));
 #pragma unroll
-        for (int pa = 0; pa < 3; pa++) {
+        for (int pa = 0; pa <= Ord; pa++) {
           bf16x8 a[3];
 #pragma unroll
           for (int rb = 0; rb < 3; rb++)
             a[rb] = *(const bf16x8 *)(lb + q * kTRChunk + aoff[rb][tap] + 64 * pa);
 #pragma unroll
-          for (int pb = 0; pb < 3 - pa; pb++)
+          for (int pb = 0; pb <= Ord - pa; pb++)
 #pragma unroll
             for (int rb = 0; rb < 3; rb++)
               acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[rb], b[pb], acc[rb], 0, 0, 0);
@@ -1826,12 +1870,27 @@ __global__ void __launch_bounds__(512, 1)
         const uint32_t lo = bf16_bits(r1 - bf16_value(mb));
         char *d = od + r * kX6Cell;
         *(uint16_t *)d = (uint16_t)hb;
-        *(uint16_t *)(d + 64) = (uint16_t)mb;
-        *(uint16_t *)(d + 128) = (uint16_t)lo;
+        if constexpr (Ord >= 1) *(uint16_t *)(d + 64) = (uint16_t)mb;
+        if constexpr (Ord >= 2) *(uint16_t *)(d + 128) = (uint16_t)lo;
       }
     __syncthreads();  // the output buffer is the next conv's input
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the ring's requests past the last conv
+  // the ring's requests past the last conv.  The reduced forms' wait names
+  // every ring register: the compiler peels their last conv off the loop,
+  // where the three steps requested past it have no reader, and without this
+  // use it hands their registers to the epilogue's store addresses while the
+  // loads are still in flight
+  static_assert(kTRAhead == 4, "the final wait names the ring's four slots");
+  if constexpr (Ord == 2)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  else if constexpr (Ord == 1)
+    asm volatile("s_waitcnt vmcnt(0)"
+                 : "+v"(bq[0][0]), "+v"(bq[0][1]), "+v"(bq[1][0]), "+v"(bq[1][1]), "+v"(bq[2][0]), "+v"(bq[2][1]),
+                   "+v"(bq[3][0]), "+v"(bq[3][1])
+                 :
+                 : "memory");
+  else
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(bq[0][0]), "+v"(bq[1][0]), "+v"(bq[2][0]), "+v"(bq[3][0]) : : "memory");
 }
 }  // namespace
 
@@ -1840,10 +1899,32 @@ extern "C" int hz_tower_x6_resident(const float *x0, const void *wpack6, const f
   if (!x0 || !wpack6 || !bias || !out || batch < 0 || nconv < 2 || nconv > kTRMaxConv || (nconv & 1)) return -1;
   if (((uintptr_t)x0 | (uintptr_t)wpack6 | (uintptr_t)out) & 15) return -1;
   if (batch == 0) return 0;
-  if (lds_opt_in<k_tower_x6_resident>(kTRLds + kTRMaxConv * 128 * 4)) return 1;
-  hipLaunchKernelGGL(k_tower_x6_resident, dim3(batch), dim3(512), kTRLds + nconv * 128 * 4, (hipStream_t)stream, x0,
+  if (lds_opt_in<k_tower_x6_resident<>>(kTRLds + kTRMaxConv * 128 * 4)) return 1;
+  hipLaunchKernelGGL(k_tower_x6_resident<>, dim3(batch), dim3(512), kTRLds + nconv * 128 * 4, (hipStream_t)stream, x0,
                      (const bf16x8 *)wpack6, bias, out, nconv, batch, live);
   return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+template <int Ord>
+static int launch_resident_xn(const float *x0, const void *wpack6, const float *bias, float *out, int32_t nconv,
+                              int32_t batch, const int32_t *live, void *stream) {
+  if (lds_opt_in<k_tower_x6_resident<Ord>>(kTRLds + kTRMaxConv * 128 * 4)) return 1;
+  hipLaunchKernelGGL(k_tower_x6_resident<Ord>, dim3(batch), dim3(512), kTRLds + nconv * 128 * 4, (hipStream_t)stream,
+                     x0, (const bf16x8 *)wpack6, bias, out, nconv, batch, live);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+// hz_tower_x6_resident keeping only the piece products of order <= Ord
+extern "C" int hz_tower_xn_resident(const float *x0, const void *wpack6, const float *bias, float *out,
+                                    int32_t nconv, int32_t batch, const int32_t *live, int32_t products,
+                                    void *stream) {
+  if (products != 1 && products != 3 && products != 6) return -1;
+  if (products == 6) return hz_tower_x6_resident(x0, wpack6, bias, out, nconv, batch, live, stream);
+  if (!x0 || !wpack6 || !bias || !out || batch < 0 || nconv < 2 || nconv > kTRMaxConv || (nconv & 1)) return -1;
+  if (((uintptr_t)x0 | (uintptr_t)wpack6 | (uintptr_t)out) & 15) return -1;
+  if (batch == 0) return 0;
+  return products == 3 ? launch_resident_xn<1>(x0, wpack6, bias, out, nconv, batch, live, stream)
+                       : launch_resident_xn<0>(x0, wpack6, bias, out, nconv, batch, live, stream);
 }
 
 // Split tower for the smallest batches (config 1's one-board predict): the

@@ -80,16 +80,24 @@ def _conv3x3_act(x, wpack, b, res=None, live=None):
     return out
 
 
-def _tower_resident(x, allw, allb, live=None):
+def _tower_resident(x, allw, allb, live=None, products=6):
     """The whole x6 tower in one HIP launch (hz_tower_x6_resident): allw
     [nconv] pack_conv3x3_x6 layouts, allb [nconv][128]; bit-identical to the
-    per-conv _conv3x3_x6_act chain."""
+    per-conv _conv3x3_x6_act chain.  products 3 or 1: hz_tower_xn_resident,
+    bit-identical to the _conv3x3_xn_act chain with the same products."""
     if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)
             and x.shape[1:] == (128, 5, 7)):
         raise NativeError("hz_tower_x6_resident needs a CUDA fp32 channels_last [B,128,5,7] activation")
     if not (allw.is_contiguous() and allb.is_contiguous() and allb.shape == (allw.shape[0], 128)):
         raise NativeError("hz_tower_x6_resident: weights/biases of the wrong layout")
     out = torch.empty_like(x, memory_format=torch.channels_last)
+    if products != 6:
+        rc = lib().hz_tower_xn_resident(x.data_ptr(), allw.data_ptr(), allb.data_ptr(), out.data_ptr(),
+                                        allw.shape[0], x.shape[0], _live_ptr(live), products,
+                                        torch.cuda.current_stream(x.device).cuda_stream)
+        if rc != 0:
+            raise NativeError(f"hz_tower_xn_resident failed ({rc})")
+        return out
     rc = lib().hz_tower_x6_resident(x.data_ptr(), allw.data_ptr(), allb.data_ptr(), out.data_ptr(), allw.shape[0],
                                     x.shape[0], _live_ptr(live), torch.cuda.current_stream(x.device).cuda_stream)
     if rc != 0:
@@ -206,6 +214,69 @@ def _conv3x3_x6_act(x, wpack6, b, res=None, live=None):
     if rc != 0:
         raise NativeError(f"hz_conv3x3_x6_bias_act failed ({rc})")
     return out
+
+
+def _conv3x3_xn_act(x, wpack6, b, res=None, live=None, products=6):
+    """_conv3x3_x6_act keeping only the piece products of order <= {1: 0,
+    3: 1, 6: 2} (hz_conv3x3_xn_bias_act; emulate_conv3x3 is its arithmetic
+    definition): 3 = hh + hm + mh at half the MFMAs, 1 = plain bf16 at a
+    sixth; 6 is _conv3x3_x6_act itself."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)
+            and x.shape[1:] == (128, 5, 7)):
+        raise NativeError("hz_conv3x3_xn_bias_act needs a CUDA fp32 channels_last [B,128,5,7] activation")
+    if res is not None and (res.shape != x.shape or res.stride() != x.stride()):
+        raise NativeError("hz_conv3x3_xn_bias_act: residual layout differs from the activation")
+    out = torch.empty_like(x, memory_format=torch.channels_last)
+    rc = lib().hz_conv3x3_xn_bias_act(x.data_ptr(), wpack6.data_ptr(), b.data_ptr(),
+                                      res.data_ptr() if res is not None else None, out.data_ptr(), x.shape[0],
+                                      _live_ptr(live), products, torch.cuda.current_stream(x.device).cuda_stream)
+    if rc != 0:
+        raise NativeError(f"hz_conv3x3_xn_bias_act failed ({rc})")
+    return out
+
+
+PRODUCT_ORDER = {1: 0, 3: 1, 6: 2}  # products kept -> the largest pa + pb
+
+
+def emulate_conv3x3(x, w, products):
+    """The arithmetic definition of the `products`-product tower conv, in
+    float64 on any device: both operands (taken as fp32) split into their
+    bf16 pieces (split3_bf16), then the sum of conv2d(x_i, w_j) over
+    i + j <= {1: 0, 3: 1, 6: 2}[products].  No bias, no ReLU."""
+    order = PRODUCT_ORDER[products]
+    xp, wp = split3_bf16(x).double(), split3_bf16(w).double()
+    out = None
+    for i in range(order + 1):
+        for j in range(order + 1 - i):
+            y = F.conv2d(xp[i], wp[j], None, padding=1)
+            out = y if out is None else out + y
+    return out
+
+
+@torch.no_grad()
+def emulate_folded(fnet, board, glob, products):
+    """The whole folded network in float64 with emulate_conv3x3 in the tower
+    (the stem and the heads exact, as the x6 stem and the fp32 heads are to
+    well below the modes' error); every block input and intermediate
+    activation is rounded to fp32 first, as the kernels store it.
+    -> (logits [B,143], value [B,1]) in float64."""
+    d = torch.float64
+    w, b = fnet.stem
+    x = F.conv2d(board.to(d), w.to(d), b.to(d), padding=1).relu_()
+    for (w1, b1), (w2, b2) in fnet.blocks:
+        x = x.float()
+        y = (emulate_conv3x3(x, w1, products) + b1.to(d).view(1, -1, 1, 1)).relu_().float()
+        x = (emulate_conv3x3(y, w2, products) + b2.to(d).view(1, -1, 1, 1) + x.to(d)).relu_()
+    x = x.float().to(d)
+    g = glob.to(d)
+    w, b = fnet.pconv
+    p = F.conv2d(x, w.to(d), b.to(d)).relu_().flatten(1)
+    logits = F.linear(torch.cat((p, g), 1), fnet.pfc[0].to(d), fnet.pfc[1].to(d))
+    w, b = fnet.vconv
+    v = F.conv2d(x, w.to(d), b.to(d)).relu_().flatten(1)
+    v = F.linear(torch.cat((v, g), 1), fnet.vfc1[0].to(d), fnet.vfc1[1].to(d)).relu_()
+    v = torch.tanh(F.linear(v, fnet.vfc2[0].to(d), fnet.vfc2[1].to(d)))
+    return logits, v
 
 
 def _resblock_x6(x, p1, b1, p2, b2, live=None):
@@ -376,8 +447,15 @@ class FoldedNet(nn.Module):
 
     # stem + tower conv kernels: "x6" = bf16 MFMA with fp32-exact products
     # (bf16x6 split: hz_stem3x3_x6_bias_act, hz_conv3x3_x6_bias_act), "f32" =
-    # the f32 MFMA (hz_stem3x3_bias_act, hz_conv3x3_bias_act)
-    TOWER_MFMA = ("x6", "f32")
+    # the f32 MFMA (hz_stem3x3_bias_act, hz_conv3x3_bias_act).  "x3" and "x1"
+    # are the opt-in reduced modes: the x6 stem and packed weights, the tower
+    # keeping 3 (hh, hm, mh) or 1 (hh: plain bf16) of the six piece products
+    # (hz_tower_xn_resident up to resident_max rows, two
+    # hz_conv3x3_xn_bias_act per block above; never the split tower or the
+    # fused block/tower forms).  tower=None reads HZ_TOWER (default "x6") at
+    # construction.
+    TOWER_MFMA = ("x6", "x3", "x1", "f32")
+    TOWER_PRODUCTS = {"x6": 6, "x3": 3, "x1": 1}
     # batches of at most this many boards run the x6 tower as one resident
     # launch (hz_tower_x6_resident; 0 = always layered).  Measured per
     # predict (tools/resident_bench.py): 262 vs 402 us at 1 board, 986 vs
@@ -396,10 +474,12 @@ class FoldedNet(nn.Module):
     # games/s (profiles/r05/tower)
     tower_loop = int(os.environ.get("HZ_TOWER_LOOP", "1"))
 
-    def __init__(self, net, epilogue=None, native_conv=True, tower="x6", fused_head=True):
+    def __init__(self, net, epilogue=None, native_conv=True, tower=None, fused_head=True):
         super().__init__()
+        if tower is None:
+            tower = os.environ.get("HZ_TOWER", "x6")
         if tower not in self.TOWER_MFMA:
-            raise ValueError(f"tower must be one of {self.TOWER_MFMA}")
+            raise ValueError(f"tower must be one of {self.TOWER_MFMA}, not {tower!r}")
         self.src = net
         self.tower = tower
         self.fused_head = fused_head
@@ -407,9 +487,30 @@ class FoldedNet(nn.Module):
         self.native_conv = native_conv and epilogue is None
         self.refresh()
 
+    @property
+    def products(self):
+        """Piece products per fp32 product in the tower (None: the f32 MFMA)."""
+        return self.TOWER_PRODUCTS.get(self.tower)
+
+    def set_tower(self, kind):
+        """Switch the tower mode.  Among "x6", "x3", "x1" nothing is re-folded
+        or re-packed (they share the packed weights); `generation` is bumped
+        either way, so a captured graph of this network is re-captured."""
+        if kind not in self.TOWER_MFMA:
+            raise ValueError(f"tower must be one of {self.TOWER_MFMA}, not {kind!r}")
+        if kind == self.tower:
+            return
+        repack = (kind == "f32") != (self.tower == "f32")
+        self.tower = kind
+        if repack:
+            self.refresh()
+        else:
+            self.generation += 1
+
     @torch.no_grad()
     def refresh(self):
         n = self.src
+        x6 = self.tower != "f32"  # the bf16 MFMA modes share the x6 stem and the packed planes
         # bumped on every re-fold: a captured HIP graph of this network's
         # kernels (BatchedMCTS's cached simulation) is valid for one generation
         self.generation = getattr(self, "generation", -1) + 1
@@ -419,12 +520,12 @@ class FoldedNet(nn.Module):
         # (conv + bias + skip + ReLU); other widths use MIOpen + hz_bias_act
         self.stem_packed = None
         if self.native_conv and self.stem[0].shape == (128, 38, 3, 3):
-            self.stem_packed = pack_stem_x6(self.stem[0]) if self.tower == "x6" else pack_stem(self.stem[0])
+            self.stem_packed = pack_stem_x6(self.stem[0]) if x6 else pack_stem(self.stem[0])
         self.packed = None
         self.resident = None
         if self.native_conv and self.blocks and self.blocks[0][0][0].shape[:2] == (128, 128):
-            pk = pack_conv3x3_x6 if self.tower == "x6" else pack_conv3x3
-            if self.tower == "x6":
+            pk = pack_conv3x3_x6 if x6 else pack_conv3x3
+            if x6:
                 # all convs back to back (hz_tower_x6_resident); the per-conv
                 # packs are views of it
                 allw = torch.stack([pk(w) for blk in self.blocks for (w, _) in blk])
@@ -478,18 +579,26 @@ class FoldedNet(nn.Module):
     def _run(self, board, glob, live, probs):
         ep = self.epilogue
         w, b = self.stem
+        products = self.products
         if self.stem_packed is None or self.packed is None:
             live = None
         if self.stem_packed is not None:  # reads the NCHW board directly
-            x = (_stem_x6_act if self.tower == "x6" else _stem_act)(board, self.stem_packed, b, live)
+            x = (_stem_x6_act if products else _stem_act)(board, self.stem_packed, b, live)
         else:
             x = ep(_nhwc(F.conv2d(board.contiguous(memory_format=torch.channels_last), w, None, padding=1)), b)
         B = board.shape[0]
         xs = None
-        if self.resident is not None and B <= min(self.split_max, split_max_batch(board.device)):
+        if products == 6 and self.resident is not None and B <= min(self.split_max, split_max_batch(board.device)):
             xs = _tower_split(x, *self.resident, live)
         if xs is not None:
             x = xs
+        elif products in (3, 1) and self.packed is not None:
+            if self.resident is not None and B <= self.resident_max:
+                x = _tower_resident(x, *self.resident, live, products)
+            else:
+                for ((_, b1), (_, b2)), (p1, p2) in zip(self.blocks, self.packed):
+                    y = _conv3x3_xn_act(x, p1, b1, None, live, products)
+                    x = _conv3x3_xn_act(y, p2, b2, x, live, products)
         elif self.resident is not None and B <= max(self.resident_max, min(self.split_max, 32)):
             x = _tower_resident(x, *self.resident, live)
         elif self.packed is not None and self.tower == "x6":

@@ -15,6 +15,7 @@ load (training_config force_lr_reset_on_load / new_forced_lr, with the StepLR
 re-initialisation at last_epoch = iteration - iteration % step_size) follows
 model.py:198-236.
 """
+import os
 from pathlib import Path
 
 import torch
@@ -62,6 +63,10 @@ class ModelManager:
         self.policy_loss_weight = training_config["policy_loss_weight"]
         self._folded = None
         self._folded_sig = None
+        # the folded network's tower mode (FoldedNet.TOWER_MFMA); None: the
+        # FoldedNet default (HZ_TOWER, else "x6")
+        self.inference_tower = None
+        self.set_inference_tower(training_config.get("inference_tower"))
 
     # -- inference -------------------------------------------------------------
     def _fast(self):
@@ -80,12 +85,26 @@ class ModelManager:
             from .infer import FoldedNet
             self.model.eval()
             if self._folded is None:
-                self._folded = FoldedNet(self.model)
+                self._folded = FoldedNet(self.model, tower=self.inference_tower)
             else:
                 self._folded.refresh()
             self._folded_sig = sig
         f = self._folded
         return f if f.stem_packed is not None and f.packed is not None else None
+
+    def set_inference_tower(self, kind):
+        """Switch the folded network's tower mode: "x6" (fp32-exact products,
+        the default), "x3" or "x1" (3 or 1 of the six bf16 piece products:
+        faster, less accurate), "f32", or None for the FoldedNet default.
+        Among the x modes nothing is re-folded: the mode changes and the
+        folded net's `generation` is bumped, so a cached graph of its kernels
+        (the drop-in MCTS's) is re-captured."""
+        from .infer import FoldedNet
+        if kind is not None and kind not in FoldedNet.TOWER_MFMA:
+            raise ValueError(f"inference tower must be one of {FoldedNet.TOWER_MFMA}, not {kind!r}")
+        self.inference_tower = kind
+        if self._folded is not None:
+            self._folded.set_tower(kind if kind is not None else os.environ.get("HZ_TOWER", "x6"))
 
     def predict(self, board_tensor, global_features_tensor):
         """model.py:81-110: eval mode, softmax over all 143 logits."""

@@ -359,11 +359,13 @@ class BatchedPredictor:
     """ModelManager.predict (model.py:81-110) for a whole batch: eval mode,
     no grad, softmax over all 143 logits (illegal moves are not masked).
     Called by BatchedMCTS with the device row count (device_rows): the
-    folded net's HIP kernels compute only the live rows."""
+    folded net's HIP kernels compute only the live rows.
+    tower: the folded net's tower mode (FoldedNet.TOWER_MFMA; None: HZ_TOWER,
+    else "x6")."""
 
     device_rows = True
 
-    def __init__(self, model, dtype=None, fold=True):
+    def __init__(self, model, dtype=None, fold=True, tower=None):
         self.model = model
         self.dtype = dtype
         # eval-mode BatchNorm folded into the convs (hzamd.infer): same fp32
@@ -371,7 +373,7 @@ class BatchedPredictor:
         self.fast = None
         if fold and hasattr(model, "residual_blocks"):
             from .infer import FoldedNet
-            self.fast = FoldedNet(model)
+            self.fast = FoldedNet(model, tower=tower)
         # the folded fp32 path is HIP kernels + PyTorch ops only: it can be
         # captured in a HIP graph (BatchedMCTS.search(graph=True))
         self.capturable = self.fast is not None and (dtype is None or dtype == torch.float32)

@@ -91,8 +91,8 @@ class Trainer:
         t0 = time.time()
         n = int(self.self_play_config["num_games_per_iter"])
         base = self.seed_base + (self.iteration * self.world + self.rank) * n
-        sp = SelfPlay(n, BatchedPredictor(data_generating_manager.model), self.mcts_config, seed_base=base,
-                      device=self.device)
+        pred = BatchedPredictor(data_generating_manager.model, tower=data_generating_manager.inference_tower)
+        sp = SelfPlay(n, pred, self.mcts_config, seed_base=base, device=self.device)
         packed, rec = sp.iteration(self.replay_buffer)
         self.last_self_play = {"examples": int(packed.shape[0]), "games": n * self.world,
                                "plies": rec["plies"], "seconds": time.time() - t0}
@@ -122,8 +122,9 @@ class Trainer:
         the promotion decision is the same on every rank; the barrier before
         the reload is unconditional on all ranks whenever it is taken."""
         c = self.self_play_config
-        res = arena.evaluate_model(BatchedPredictor(self.model_manager.model),
-                                   BatchedPredictor(self.best_model_manager.model),
+        res = arena.evaluate_model(BatchedPredictor(self.model_manager.model, tower=self.model_manager.inference_tower),
+                                   BatchedPredictor(self.best_model_manager.model,
+                                                    tower=self.best_model_manager.inference_tower),
                                    n_games=c["eval_episodes"], threshold=c["eval_win_rate_threshold"],
                                    mcts_config=self.eval_mcts_config,
                                    seed_base=self.seed_base + 10**9 + self.iteration * c["eval_episodes"],

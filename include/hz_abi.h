@@ -320,6 +320,17 @@ int hz_conv3x3_bias_act(const float *x, const float *wpack, const float *bias, c
 int hz_conv3x3_x6_bias_act(const float *x, const void *wpack6, const float *bias, const float *res, float *out,
                            int32_t batch, const int32_t *live, void *stream);
 
+/* hz_conv3x3_x6_bias_act keeping only the piece products of order
+ * <= {1:0, 3:1, 6:2}; products = 6 is hz_conv3x3_x6_bias_act itself.
+ * products = 3 keeps h*h, h*m, m*h (|error| <= 3 * 2^-18 |x||w| per product,
+ * half the MFMAs), products = 1 keeps h*h (plain bf16 operands, a sixth of
+ * them).  wpack6 is the same pack_conv3x3_x6 layout (the unused planes are
+ * not read); the kept products are accumulated in hz_conv3x3_x6_bias_act's
+ * order, always by its generic one- and eight-state kernels.  Any other
+ * `products` returns -1 with nothing enqueued. */
+int hz_conv3x3_xn_bias_act(const float *x, const void *wpack6, const float *bias, const float *res,
+                           float *out, int32_t batch, const int32_t *live, int32_t products, void *stream);
+
 /* One residual block of the tower (model.py:376-393, ResidualBlock.forward
  * with BN folded): out = relu(conv2(relu(conv1(x) + b1)) + b2 + x), w1/w2
  * packed as for hz_conv3x3_x6_bias_act; x, out NHWC [batch][5][7][128] (out
@@ -379,6 +390,12 @@ int hz_stem3x3_x6_bias_act(const float *board, const void *wpack6, const float *
  * resident in LDS; bit-identical to nconv hz_conv3x3_x6_bias_act calls. */
 int hz_tower_x6_resident(const float *x0, const void *wpack6, const float *bias, float *out, int32_t nconv,
                          int32_t batch, const int32_t *live, void *stream);
+/* hz_tower_x6_resident with hz_conv3x3_xn_bias_act's `products` (1, 3 or 6;
+ * 6 is hz_tower_x6_resident itself): activations between the convs are kept
+ * as the planes the mode reads.  Bit-identical to nconv
+ * hz_conv3x3_xn_bias_act calls with the same `products`. */
+int hz_tower_xn_resident(const float *x0, const void *wpack6, const float *bias, float *out, int32_t nconv,
+                         int32_t batch, const int32_t *live, int32_t products, void *stream);
 /* hz_tower_x6_resident for batch <= 32 with 24 (batch <= 10) or 8
  * workgroups per state (16 output channels each) exchanging each conv's
  * output through HBM in-launch: xch = scratch of 2 * batch * 35 * 128
