@@ -28,6 +28,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hz_initgen.hpp"
+
 namespace hz {
 
 constexpr int kCells = 23;
@@ -487,7 +489,7 @@ using WinMT12 = WinGMT<12>;
 // [624][65] words (word i of lane l at i*65 + l).  Addressing through this
 // __shared__ symbol keeps every access a 32-bit LDS address.
 constexpr int kLdsStride = 65;
-extern __shared__ uint32_t hz_lds[];
+extern __shared__ __attribute__((aligned(16))) uint32_t hz_lds[];
 
 // A board's stream resident in LDS (k_reset / k_rollout).  Draws scan the
 // next <= 24 twisted words in place, branch-free; prefetch() twists ahead
@@ -530,20 +532,9 @@ struct LdsMT {
 constexpr int kAheadTwist = 224;
 constexpr int kMTAhead = 0 | (kAheadTwist << 16);
 
-// init_genrand(19650218) (_randommodule.c), the starting array of
-// init_by_array: the same for every seed, so it is a constant table read
-// through the scalar cache instead of a per-step multiply chain.
-struct InitGen { uint32_t v[kMT]; };
-constexpr InitGen make_init_gen() {
-  InitGen g{};
-  uint32_t x = 19650218u;
-  g.v[0] = x;
-  for (int i = 1; i < kMT; i++) {
-    x = 1812433253u * (x ^ (x >> 30)) + (uint32_t)i;
-    g.v[i] = x;
-  }
-  return g;
-}
+// init_genrand(19650218), the starting array of init_by_array, padded for
+// the seeding loops' read-ahead (hz_initgen.hpp)
+static_assert(kInitGenRows == kMT, "the table's rows");
 __constant__ InitGen kInitGen = make_init_gen();
 
 // random.seed(int) for 0 <= seed < 2^64 (_randommodule.c random_seed +
@@ -825,14 +816,14 @@ __device__ __forceinline__ void sample3_raw(M& m, uint32_t n, int k, uint32_t j[
 // where they are written, ahead of the branch that may leave the scan,
 // instead of sinking them to their first use.
 typedef __attribute__((address_space(3))) const volatile uint32_t LdsVolatileWord;
-template <bool Clamp>
+template <bool Clamp, int Stride = kLdsStride>
 __device__ __forceinline__ uint32_t scan_word(const LdsMT& m, int t) {
   LdsVolatileWord* lds = (LdsVolatileWord*)hz_lds;
   if (Clamp) {
     int i = m.pos + t < kMT ? m.pos + t : kMT - 1;
-    return lds[i * kLdsStride + m.lane];
+    return lds[i * Stride + m.lane];
   }
-  return lds[(m.pos + t) * kLdsStride + m.lane];
+  return lds[(m.pos + t) * Stride + m.lane];
 }
 
 // the top 14 bits of temper(y): its last step (y ^= y >> 18) leaves them
@@ -875,7 +866,7 @@ __device__ __forceinline__ uint32_t temper_top14(uint32_t y) {
 // method (n <= 21): pick i keeps a value < n - i, read with bit_length(n - i)
 // bits.  Returns the picks in draw order in p0, p1, p2 and the count made;
 // fewer than three when the window ran out (rare; serial continuation).
-template <bool Clamp, bool Pool>
+template <bool Clamp, bool Pool, int Stride = kLdsStride>
 __device__ __forceinline__ int scan3(LdsMT& m, uint32_t n, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
   int avail = m.tw - m.pos;
   uint32_t lim = n;
@@ -885,14 +876,14 @@ __device__ __forceinline__ int scan3(LdsMT& m, uint32_t n, uint32_t& p0, uint32_
   TemperMasks tk;
   uint32_t w[4], nx[4];
 #pragma unroll
-  for (int u = 0; u < 4; u++) nx[u] = scan_word<Clamp>(m, u);
+  for (int u = 0; u < 4; u++) nx[u] = scan_word<Clamp, Stride>(m, u);
 #pragma unroll
   for (int seg = 0; seg < 6; seg++) {
 #pragma unroll
     for (int u = 0; u < 4; u++) w[u] = nx[u];
     if (seg < 5) {
 #pragma unroll
-      for (int u = 0; u < 4; u++) nx[u] = scan_word<Clamp>(m, 4 * seg + 4 + u);
+      for (int u = 0; u < 4; u++) nx[u] = scan_word<Clamp, Stride>(m, 4 * seg + 4 + u);
     }
 #pragma unroll
     for (int u = 0; u < 4; u++) {
@@ -953,13 +944,18 @@ __device__ __forceinline__ void sample3_raw(LdsMT& m, uint32_t n, int k, uint32_
 // returns words that keep changing: the set method redraws while a pick
 // repeats an earlier one, so a constant there (it was 0) could repeat a pick
 // of 0 for ever.
+// A window's rows are kWinStride words apart: a multiple of four, so the
+// four words of a row that a lane stages (four boards) are one aligned 16-byte
+// LDS store; the windows have their own region, so the resident streams'
+// kLdsStride is not theirs.
+constexpr int kWinStride = 68;
 struct WinMT : LdsMT {
   int lim;
   __device__ __forceinline__ WinMT(int l, int cursor, int rows) : LdsMT(l, cursor), lim(rows) {}
   __device__ __forceinline__ void prefetch() {}
   __device__ __forceinline__ uint32_t next() {
     const int i = pos++;
-    return i < lim ? temper(hz_lds[i * kLdsStride + lane]) : 0x9E3779B9u * (uint32_t)(i + 1);
+    return i < lim ? temper(hz_lds[i * kWinStride + lane]) : 0x9E3779B9u * (uint32_t)(i + 1);
   }
 };
 __device__ __forceinline__ void sample3_raw(WinMT& m, uint32_t n, int k, uint32_t j[3]) {
@@ -970,10 +966,10 @@ __device__ __forceinline__ void sample3_raw(WinMT& m, uint32_t n, int k, uint32_
   uint32_t j0, j1, j2;
   int got;
   LdsMT& lm = m;
-  if (__all(n > 21)) got = scan3<false, false>(lm, n, j0, j1, j2);
-  else if (__all(n <= 21)) got = scan3<false, true>(lm, n, j0, j1, j2);
-  else if (n > 21) got = scan3<false, false>(lm, n, j0, j1, j2);
-  else got = scan3<false, true>(lm, n, j0, j1, j2);
+  if (__all(n > 21)) got = scan3<false, false, kWinStride>(lm, n, j0, j1, j2);
+  else if (__all(n <= 21)) got = scan3<false, true, kWinStride>(lm, n, j0, j1, j2);
+  else if (n > 21) got = scan3<false, false, kWinStride>(lm, n, j0, j1, j2);
+  else got = scan3<false, true, kWinStride>(lm, n, j0, j1, j2);
   j[0] = j0; j[1] = j1; j[2] = j2;
   if (got < k) sample3_serial(m, n, k, j, got);
 }

@@ -1566,8 +1566,8 @@ __global__ void __launch_bounds__(kStageThreads) k_rollout(uint64_t *__restrict_
 //   s = 0  P1    seeding pass 1, all 624 steps, in     draw-Y blocks, wave 2
 //                registers: only its last word leaves
 //   s = 1  P2a   pass 2, steps 2-208                  seed blocks, wave 0
-//   s = 2  P2b   pass 2, steps 209-416                seed blocks, wave 1
-//   s = 3  P2c   pass 2, steps 417-624; rows 0-223    seed blocks, wave 2
+//   s = 2  P2b   pass 2, steps 209-432                seed blocks, wave 1
+//   s = 3  P2c   pass 2, steps 433-624; rows 0-223    seed blocks, wave 2
 //                of the next generation twisted       (twist: wave 3)
 //   s = 4  D1    pile draws [dcut0 = 0, dcut1)        draw-X blocks, wave 0
 //   s = 5  D2    draws [dcut1, dcut2)                 draw-X blocks, wave 1
@@ -1620,9 +1620,11 @@ constexpr int kP2WinRows = kP2Win + 24;  // LDS rows per window (a scan reads up
 // the draw stages' first draws (run time: HZ_P2_DCUTS).  Later draws take
 // longer, so the early stages take more of them: with four stages of six, D3
 // ran 13.8 us against D1's 10.5, and the cuts became 0, 7, 13, 18
-// (profiles/r05/p2_dcut); five stages: profiles/r07.
+// (profiles/r05/p2_dcut); five stages: profiles/r07, and profiles/r09 since
+// the first stage loads its window in its first round trip and takes a sixth
+// draw from the last.
 #if HZ_P2_NDRAW == 5
-#define HZ_P2_DCUT 0, 5, 10, 14, 18
+#define HZ_P2_DCUT 0, 6, 11, 15, 19
 #elif HZ_P2_NDRAW == 4
 #define HZ_P2_DCUT 0, 7, 13, 18
 #endif
@@ -1688,7 +1690,7 @@ constexpr int kP2Stamps = 48;  // stamp slots per board in k_play2 (tools/p2_rol
   do {                     \
   } while (0)
 #endif
-static_assert(4 * kP2WinRows * kLdsStride * 4 <= (int)kResetLds, "a window per wave of a draw block");
+static_assert(4 * kP2WinRows * kWinStride * 4 <= (int)kResetLds, "a window per wave of a draw block");
 
 struct P2Args {
   uint64_t *st;
@@ -1897,7 +1899,6 @@ __device__ __forceinline__ void p2_st(T *p, T v) {
 __device__ __forceinline__ uint32_t p1_step(uint32_t t, uint32_t q, bool odd, uint32_t kA, uint32_t kB) {
   return (t ^ ((q ^ (q >> 30)) * 1664525U)) + (odd ? kA : kB);
 }
-__device__ __forceinline__ int p2_tab(int i) { return i < kMT ? i : kMT - 1; }  // (a read-ahead past the table's end)
 // pass 1's row-1 word (its first step, from init_genrand's mt[0])
 __device__ __forceinline__ uint32_t p1_row1(uint32_t kA, uint32_t kB) {
   return p1_step(kInitGen.v[1], 19650218u, true, kA, kB);
@@ -1909,42 +1910,70 @@ __device__ __forceinline__ void p2_keys(uint64_t seed, uint32_t &kA, uint32_t &k
 }
 
 // P1: all of init_by_array's pass 1 in registers (624 steps of four
-// dependent VALU operations; the table words by scalar loads a group of eight
-// ahead, so their wait is not in the chain).  No stream slot and no LDS: what
-// leaves is row 1's word after the 624th step (the only pass-1 word pass 2
-// cannot recompute from a neighbour: it closes the ring) and the episode tag.
+// dependent VALU operations).  No stream slot and no LDS: what leaves is row
+// 1's word after the 624th step (the only pass-1 word pass 2 cannot recompute
+// from a neighbour: it closes the ring) and the episode tag.
+// The wave is alone on its SIMD, so every instruction it issues, scalar ones
+// included, costs an issue slot: the loop is kept to the chain plus one
+// scalar load and one wait per eight steps.  The table words come a group of
+// eight ahead, in two register sets that alternate (a trip is sixteen steps),
+// so no set is copied; the padded table needs no clamp, so a group is one
+// s_load_dwordx8 from the loop's one table address.
+// The loads and their waits are written out: the compiler moves a plain
+// table read to wherever it likes (both groups' loads to the top of the trip,
+// or each next to its first use, where every group then waits a scalar-cache
+// round trip: 12 us for the stage instead of 8) and copies the words between
+// the sets.  Scalar loads return out of order, so a wait is for all that are
+// out: a group's wait comes before the next group's load is issued, behind
+// the eight steps that ran meanwhile.
+typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+// rows [1 + off / 4 + Imm / 4, + 8) of the table (tab: row 1's address)
+template <int Imm>
+__device__ __forceinline__ u32x8 p1_load8(const uint32_t *tab, uint32_t off) {
+  u32x8 t;
+  asm volatile("s_load_dwordx8 %0, %1, %2 offset:%3" : "=&s"(t) : "s"(tab), "s"(off), "n"(Imm));
+  return t;
+}
+__device__ __forceinline__ void p1_arrived(u32x8 &t) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(t)); }
+__device__ __forceinline__ uint32_t p1_steps8(const u32x8 &t, uint32_t prev, uint32_t kA, uint32_t kB) {
+#pragma unroll
+  for (int u = 0; u < 8; u++) prev = p1_step(t[u], prev, !(u & 1), kA, kB);  // (groups start at odd rows)
+  return prev;
+}
 __device__ __forceinline__ void p2_p1(const P2Args &a, int b) {
   const int e = a.ep_in[b] + kP2Last;
   uint32_t kA, kB;
   p2_keys(episode_seed(a.seed_base, b, e), kA, kB);
   uint32_t prev = 19650218u;
-  uint32_t iv[8];
-#pragma unroll
-  for (int u = 0; u < 8; u++) iv[u] = kInitGen.v[1 + u];
+  const uint32_t *tab = kInitGen.v + 1;
+  static_assert(38 * 16 + 1 == 609 && 617 + 8 <= kMT + kInitGenPad, "the last group's read (rows 617-624) within the table's padding");
+  u32x8 ta = p1_load8<0>(tab, 0), tb;
+  p1_arrived(ta);
 #pragma unroll 1
-  for (int g = 1; g < 617; g += 8) {  // steps 1..616
-    uint32_t nx[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) nx[u] = kInitGen.v[p2_tab(g + 8 + u)];
-    // (the loads stay here: left to itself the scheduler sinks them to the
-    // group's end, next to their first use, and every group then waits a
-    // scalar-cache round trip: 12 us for the stage instead of 8)
+  for (uint32_t off = 0; off < 38 * 64; off += 64) {  // steps 1..608, sixteen per trip
+    tb = p1_load8<32>(tab, off);
     __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < 8; u++) prev = p1_step(iv[u], prev, !(u & 1), kA, kB);
+    prev = p1_steps8(ta, prev, kA, kB);
     __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < 8; u++) iv[u] = nx[u];
+    p1_arrived(tb);
+    ta = p1_load8<64>(tab, off);
+    __builtin_amdgcn_sched_barrier(0);
+    prev = p1_steps8(tb, prev, kA, kB);
+    __builtin_amdgcn_sched_barrier(0);
+    p1_arrived(ta);
   }
+  tb = p1_load8<0>(tab, (617 - 1) * 4);  // (its eighth word is padding)
+  prev = p1_steps8(ta, prev, kA, kB);  // steps 609..616
+  p1_arrived(tb);
 #pragma unroll
-  for (int u = 0; u < 7; u++) prev = p1_step(iv[u], prev, !(u & 1), kA, kB);  // steps 617..623
+  for (int u = 0; u < 7; u++) prev = p1_step(tb[u], prev, !(u & 1), kA, kB);  // steps 617..623
   // mt[0] = mt[623]; the 624th step at i = 1 (key j = 623 % keylen -> kB)
   a.p1h_w[b] = p1_step(p1_row1(kA, kB), prev, false, kA, kB);
   a.p1t_w[b] = e * 8 + 2;
 }
 
-// Pass 2 in three stages, P2a (steps 2-208), P2b (209-416) and P2c
-// (417-623 and the last step at i = 1), in one seed block (three different
+// Pass 2 in three stages, P2a (steps 2-208), P2b (209-432) and P2c
+// (433-623 and the last step at i = 1), in one seed block (three different
 // episodes).  Every step reads the row's pass-1 word.  The stages once read
 // them from the stream slot (staged into LDS first: an HBM round trip per
 // step is far too slow); now each recomputes pass 1 over its own rows, a
@@ -1953,55 +1982,102 @@ __device__ __forceinline__ void p2_p1(const P2Args &a, int b) {
 // the slot with a buffer store (the row offset a scalar: no address
 // arithmetic in the chain).  The chain is cut into thirds rather than made
 // cheaper per step.
-constexpr int kP2aEnd = 209, kP2bEnd = 417;
-constexpr int kTwKeep = 397;  // P2c's final rows from here on stay in LDS (the twist reads rows 397-620)
+#ifndef HZ_P2_BEND
+// P2b's end (A/B builds: 225 + 8 k).  The twist follows P2c's progress and
+// ends ~1.5 us after it (its last stores' write-through), so P2c gets the
+// fewest rows: the rows r + 397 below this row the twist holds in registers
+// from the start (kTwHbm, P2b's of the call before, from HBM), the rest it
+// reads from P2c's LDS rows as they appear.
+#define HZ_P2_BEND 433
+#endif
+constexpr int kP2aEnd = 209, kP2bEnd = HZ_P2_BEND;
+static_assert(kP2bEnd > 399 && kP2bEnd + 64 < kMT && (kP2bEnd - kAheadTwist - 1) % 8 == 0, "P2b's final steps in groups of eight; rows 397, 398 P2b's");
 // pass 1 a group ahead of pass 2, at row g
 struct P2Ahead {
   uint32_t cur[8];  // pass 1's words of rows [g, g + 8)
   uint32_t iv[8];   // kInitGen's words of rows [g + 8, g + 16)
   uint32_t last;    // pass 1's word of the last row pass 2 has consumed (the next stage starts from it)
 };
+// The table's address as a pass-2 stage holds it: in one scalar register
+// pair from the stage's start, its groups' loads at immediate offsets (the
+// compiler, knowing the address, makes it again from the program counter for
+// every group: three scalar instructions each).
+typedef __attribute__((address_space(4))) const uint32_t ConstWord;
+__device__ __forceinline__ ConstWord *p2_table() {
+  ConstWord *t = (ConstWord *)kInitGen.v;
+  asm volatile("" : "+s"(t));
+  return t;
+}
 // q: pass 1's word of row G - 1
 template <int G>
-__device__ __forceinline__ void p2_ahead_init(P2Ahead &h, uint32_t q, uint32_t kA, uint32_t kB) {
+__device__ __forceinline__ void p2_ahead_init(ConstWord *tab, P2Ahead &h, uint32_t q, uint32_t kA, uint32_t kB) {
 #pragma unroll
   for (int u = 0; u < 8; u++) {
-    q = p1_step(kInitGen.v[p2_tab(G + u)], q, (G + u) & 1, kA, kB);
+    q = p1_step(tab[G + u], q, (G + u) & 1, kA, kB);
     h.cur[u] = q;
   }
 #pragma unroll
-  for (int u = 0; u < 8; u++) h.iv[u] = kInitGen.v[p2_tab(G + 8 + u)];
+  for (int u = 0; u < 8; u++) h.iv[u] = tab[G + 8 + u];
   h.last = q;
 }
 // twist_word(cur, next, far) = far ^ twist_part(cur, next): the part of row
-// r's next-generation word that rows r and r + 1 decide
+// r's next-generation word that rows r and r + 1 decide.  Four operations:
+// the select of cur's top bit into next (v_bfi_b32), the shift, next's low
+// bit spread (v_bfe_i32), and "and, xor" in one v_bitop3_b32.  (The select
+// is written out: from every source form of it the compiler makes v_and_b32
+// and v_and_or_b32.)
 __device__ __forceinline__ uint32_t twist_part(uint32_t cur, uint32_t next) {
-  const uint32_t y = (cur & 0x80000000U) | (next & 0x7fffffffU);
-  return (y >> 1) ^ ((y & 1U) ? 0x9908b0dfU : 0U);
+  uint32_t y;  // (cur & 0x80000000) | (next & 0x7fffffff)
+  asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(y) : "s"(0x7fffffffU), "v"(next), "v"(cur));
+  return (y >> 1) ^ ((next & 1U) ? 0x9908b0dfU : 0U);
 }
 // What a pass-2 step stores: its final word to its row (kP2Final), the same
 // and to the row in LDS (kP2Keep, P2c), or the previous row's twist part
 // (kP2Part: rows 2-223, which only the twist reads)
 enum { kP2Final = 0, kP2Keep = 1, kP2Part = 2 };
+// A stage's store addresses, made once: the slot's buffer, the byte offsets
+// of the lane's column in eight consecutive rows (a store's voffset; the
+// group's first row is its scalar offset: one scalar instruction per group of
+// eight stores, none per store), and the lane's LDS byte address.
+typedef __attribute__((address_space(3))) uint32_t LdsWord;
+struct P2Out {
+  __amdgpu_buffer_rsrc_t rs;
+  int row_bytes;
+  int vo[8];
+  uint32_t lds;
+  __device__ __forceinline__ P2Out(__amdgpu_buffer_rsrc_t r, int rb, int lane) : rs(r), row_bytes(rb) {
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+      vo[u] = lane * 4 + u * rb;
+      asm volatile("" : "+v"(vo[u]));  // (kept: not made again at every store)
+    }
+    lds = (uint32_t)(uintptr_t)(LdsWord *)(hz_lds + lane);
+  }
+  // word v to column `lane` of row g + u (g wave-uniform, soff = g * row_bytes)
+  __device__ __forceinline__ void put(uint32_t v, int soff, int u) const {
+    __builtin_amdgcn_raw_buffer_store_b32(v, rs, vo[u], soff, HZ_P2_AUX);
+  }
+};
 // steps [G0, G1) of pass 2 (G1 - G0 a multiple of 8; h at row G0 on entry, at
 // G1 on return), while pass 1 runs over the next group's rows (past the
-// stage's last row its words are unused); stores to the slot (buffer stores:
-// voffset the lane, soffset the row) as Mode says, with kP2Keep publishing
-// progress every 8 steps
+// stage's last row its words are unused); stores to the slot as Mode says,
+// with kP2Keep publishing progress every 8 steps.  kP2Keep's LDS rows: one
+// address per group, the group's rows at immediate offsets.
 template <int G0, int G1, int Mode>
-__device__ __forceinline__ void p2_span(int lane, __amdgpu_buffer_rsrc_t rs, int row_bytes, uint32_t &prev, P2Ahead &h,
-                                        uint32_t kA, uint32_t kB, int *prog) {
+__device__ __forceinline__ void p2_span(ConstWord *tab, const P2Out &o, uint32_t &prev, P2Ahead &h, uint32_t kA, uint32_t kB, int *prog) {
   constexpr bool KeepLds = Mode == kP2Keep;
   static_assert((G1 - G0) % 8 == 0, "groups of eight");
-  uint32_t *l = hz_lds + lane;
+  static_assert(G1 + 15 < kMT + kInitGenPad, "the table's read-ahead within its padding");
   constexpr int S = kLdsStride;
+  uint32_t lg = o.lds + G0 * S * 4;
 #pragma unroll 2
   for (int g = G0; g < G1; g += 8) {
     uint32_t ivn[8], nx[8];
 #pragma unroll
-    for (int u = 0; u < 8; u++) ivn[u] = kInitGen.v[p2_tab(g + 16 + u)];
+    for (int u = 0; u < 8; u++) ivn[u] = tab[g + 16 + u];
     const uint32_t kneg = __builtin_amdgcn_readfirstlane(0u - (uint32_t)g);
-    const int soff = __builtin_amdgcn_readfirstlane((Mode == kP2Part ? g - 1 : g) * row_bytes);
+    const int soff = __builtin_amdgcn_readfirstlane((Mode == kP2Part ? g - 1 : g) * o.row_bytes);
+    if (KeepLds) asm volatile("" : "+v"(lg));  // (one register for the group, not an address per row)
     uint32_t q = h.cur[7];
 #pragma unroll
     for (int u = 0; u < 8; u++) {
@@ -2009,15 +2085,17 @@ __device__ __forceinline__ void p2_span(int lane, __amdgpu_buffer_rsrc_t rs, int
       const uint32_t p = (prev ^ (prev >> 30)) * 1566083941U;
       uint32_t v;
       asm("v_xad_u32 %0, %1, %2, %3" : "=v"(v) : "v"(p), "v"(h.cur[u]), "s"(kneg - (uint32_t)u));
-      __builtin_amdgcn_raw_buffer_store_b32(Mode == kP2Part ? twist_part(prev, v) : v, rs, lane * 4,
-                                            soff + u * row_bytes, HZ_P2_AUX);
-      if (KeepLds) l[(g + u) * S] = v;
+      o.put(Mode == kP2Part ? twist_part(prev, v) : v, soff, u);
+      if (KeepLds) *(LdsWord *)(uintptr_t)(lg + u * S * 4) = v;
       prev = v;
       // pass 1, row g + 8 + u (the parity of G0 + u: g - G0 is a multiple of 8)
       q = p1_step(h.iv[u], q, (G0 + u) & 1, kA, kB);
       nx[u] = q;
     }
-    if (KeepLds) p2_publish(prog, g + 8);  // rows [G0, g + 8) final in LDS
+    if (KeepLds) {
+      p2_publish(prog, g + 8);  // rows [G0, g + 8) final in LDS
+      lg += 8 * S * 4;
+    }
     h.last = h.cur[7];
 #pragma unroll
     for (int u = 0; u < 8; u++) {
@@ -2028,13 +2106,13 @@ __device__ __forceinline__ void p2_span(int lane, __amdgpu_buffer_rsrc_t rs, int
 }
 // the last steps [G, G1) one by one (fewer than eight: h holds their pass-1 words)
 template <int G, int G1, int Mode>
-__device__ __forceinline__ void p2_tail(int lane, __amdgpu_buffer_rsrc_t rs, int row_bytes, uint32_t &prev, P2Ahead &h) {
+__device__ __forceinline__ void p2_tail(const P2Out &o, int lane, uint32_t &prev, P2Ahead &h) {
   static_assert(G1 - G >= 1 && G1 - G <= 8, "within the group ahead");
+  const int soff = __builtin_amdgcn_readfirstlane((Mode == kP2Part ? G - 1 : G) * o.row_bytes);
 #pragma unroll
   for (int i = G; i < G1; i++) {
     const uint32_t v = (h.cur[i - G] ^ ((prev ^ (prev >> 30)) * 1566083941U)) - (uint32_t)i;
-    if (Mode == kP2Part) __builtin_amdgcn_raw_buffer_store_b32(twist_part(prev, v), rs, lane * 4, (i - 1) * row_bytes, HZ_P2_AUX);
-    else __builtin_amdgcn_raw_buffer_store_b32(v, rs, lane * 4, i * row_bytes, HZ_P2_AUX);
+    o.put(Mode == kP2Part ? twist_part(prev, v) : v, soff, i - G);
     if (Mode == kP2Keep) hz_lds[i * kLdsStride + lane] = v;
     prev = v;
   }
@@ -2079,30 +2157,32 @@ __device__ __forceinline__ void p2_third(const P2Args &a, int b0, int lane, int 
     q = act ? h[3 * nr + b] : 0u;
   }
   const __amdgpu_buffer_rsrc_t rs = p2_slot_rsrc(slot, b0, nr);
-  const int row_bytes = (int)(nr * 4);
+  const int row_bytes = __builtin_amdgcn_readfirstlane((int)(nr * 4));
+  const P2Out o(rs, row_bytes, lane);
+  ConstWord *tab = p2_table();
   P2Ahead h;
   if constexpr (K == 0) {  // step 2: row 2's final word, handed on (row 1's part needs row 1, P2c's last step)
     q = p1_step(kInitGen.v[2], q, false, kA, kB);
     row2 = (q ^ ((prev ^ (prev >> 30)) * 1566083941U)) - 2U;
     prev = row2;
-    p2_ahead_init<3>(h, q, kA, kB);
+    p2_ahead_init<3>(tab, h, q, kA, kB);
     constexpr int G = 3 + 8 * ((kP2aEnd - 3) / 8);
-    p2_span<3, G, kP2Part>(lane, rs, row_bytes, prev, h, kA, kB, s_prog);  // parts of rows 2 ..
-    p2_tail<G, kP2aEnd, kP2Part>(lane, rs, row_bytes, prev, h);             // .. 207
+    p2_span<3, G, kP2Part>(tab, o, prev, h, kA, kB, s_prog);  // parts of rows 2 ..
+    p2_tail<G, kP2aEnd, kP2Part>(o, lane, prev, h);             // .. 207
   } else if constexpr (K == 1) {
     static_assert(kAheadTwist + 1 - kP2aEnd == 16, "P2b's part steps: two groups");
-    p2_ahead_init<kP2aEnd>(h, q, kA, kB);
-    p2_span<kP2aEnd, kAheadTwist + 1, kP2Part>(lane, rs, row_bytes, prev, h, kA, kB, s_prog);  // parts of rows 208-223
+    p2_ahead_init<kP2aEnd>(tab, h, q, kA, kB);
+    p2_span<kP2aEnd, kAheadTwist + 1, kP2Part>(tab, o, prev, h, kA, kB, s_prog);  // parts of rows 208-223
     __builtin_amdgcn_raw_buffer_store_b32(prev, rs, lane * 4, kAheadTwist * row_bytes, HZ_P2_AUX);  // row 224's final word
-    p2_span<kAheadTwist + 1, kP2bEnd, kP2Final>(lane, rs, row_bytes, prev, h, kA, kB, s_prog);
+    p2_span<kAheadTwist + 1, kP2bEnd, kP2Final>(tab, o, prev, h, kA, kB, s_prog);
   } else {
     // rows 0 and 1 of the next generation are P2c's own last words: their
     // far rows (397, 398: P2b's) loaded now, used after the chain
     const uint32_t f0 = act ? slot[(size_t)397 * nr + b] : 0u, f1 = act ? slot[(size_t)398 * nr + b] : 0u;
-    p2_ahead_init<kP2bEnd>(h, q, kA, kB);
+    p2_ahead_init<kP2bEnd>(tab, h, q, kA, kB);
     constexpr int G = kP2bEnd + 8 * ((kMT - kP2bEnd) / 8);
-    p2_span<kP2bEnd, G, kP2Keep>(lane, rs, row_bytes, prev, h, kA, kB, s_prog);
-    p2_tail<G, kMT, kP2Keep>(lane, rs, row_bytes, prev, h);
+    p2_span<kP2bEnd, G, kP2Keep>(tab, o, prev, h, kA, kB, s_prog);
+    p2_tail<G, kMT, kP2Keep>(o, lane, prev, h);
     p2_publish(s_prog, kMT);
     const uint32_t row1 = (first1 ^ ((prev ^ (prev >> 30)) * 1566083941U)) - 1U;  // the last step, at i = 1
     // mt[0] = 0x80000000 after init_by_array; row 1's next row is row 2
@@ -2125,10 +2205,11 @@ __device__ __forceinline__ void p2_third(const P2Args &a, int b0, int lane, int 
 
 // The twist (seed blocks, wave 3): rows [0, kAheadTwist) of the next
 // generation into P2c's slot (the stream at cursor kMTAhead): row r's new
-// word is the far row r + 397 (P2b's below row 417, from HBM; P2c's from
+// word is the far row r + 397 (P2b's below row kP2bEnd, from HBM; P2c's from
 // LDS) xor row r's twist part, which P2a and P2b left in the slot (rows
 // 2-223).  Lane: four boards, rows grp + 4 i, grp = lane / 16, so iteration
-// i needs P2c's rows up to 4 i + 400 and follows P2c's progress (s_prog),
+// i needs P2c's rows up to 4 i + 400 (from iteration 9 on: the rows below
+// kP2bEnd are in registers) and follows P2c's progress (s_prog),
 // two iterations per publish of P2c's; rows 0 and 1 (from row 1, P2c's last
 // step, and row 2's final word) are P2c's own.  All its loads precede its
 // stores.  (Before the parts, the wave shuffled each row's
@@ -2237,6 +2318,27 @@ __device__ __forceinline__ void p2_draw_stage(const P2Args &a, int b0, int lane,
   bool ok = act && a.s_tag[kP2SDraw + stage][b] == e * 8 + 5;
   int k0 = 0, c0 = kMTAhead;
   uint64_t bag = initial_bag(), q[kAheadWords] = {0, 0, 0, 0};
+  // the window: rows [r0, r0 + kP2Win), 16-B loads (four boards of a row per
+  // lane), all in flight, and one 16-B LDS store each
+  constexpr int U = kP2Win / 4;
+  const int c4 = (lane & 15) * 4;
+  uint4 v[U];
+  auto win_load = [&](int r0) {
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int r = r0 + 4 * u + (lane >> 4);
+      v[u] = p2_ld4(slot + (size_t)r * nr + b0 + c4);
+    }
+  };
+  auto win_store = [&]() {
+#pragma unroll
+    for (int u = 0; u < U; u++)
+      *reinterpret_cast<uint4 *>(hz_lds + base + (4 * u + (lane >> 4)) * kWinStride + c4) = v[u];
+  };
+  // the first stage's window starts at row 0 whatever its tags say (every
+  // start cursor is kMTAhead): its loads go out with the tag's, one round
+  // trip instead of two (rows of another episode are never read: !ok)
+  if (stage == 0) win_load(0);
   if (stage > 0 && act) {  // (one round trip: used only if the tag matches)
     const int itag = in.tag[b];
     k0 = in.k[b];
@@ -2248,23 +2350,9 @@ __device__ __forceinline__ void p2_draw_stage(const P2Args &a, int b0, int lane,
   }
   const bool draws = ok && k0 >= d0 && d0 < d1;
   const int r0 = wave_min_i(draws ? (c0 & 0xFFFF) : kAheadTwist) & ~3;
-  if (r0 < kAheadTwist) {  // the window: rows [r0, r0 + kP2Win), 16-B loads (four boards of a row per lane), all in flight
-    constexpr int U = kP2Win / 4;
-    const int c4 = (lane & 15) * 4;
-    uint4 v[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const int r = r0 + 4 * u + (lane >> 4);
-      v[u] = p2_ld4(slot + (size_t)r * nr + b0 + c4);
-    }
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      uint32_t *dd = hz_lds + base + (4 * u + (lane >> 4)) * kLdsStride + c4;
-      dd[0] = v[u].x;
-      dd[1] = v[u].y;
-      dd[2] = v[u].z;
-      dd[3] = v[u].w;
-    }
+  if (r0 < kAheadTwist) {
+    if (stage > 0) win_load(r0);
+    win_store();
   }
   P2_PHASE(28 + stage, t0);  // window staged
   if (!act) return;
@@ -2276,7 +2364,7 @@ __device__ __forceinline__ void p2_draw_stage(const P2Args &a, int b0, int lane,
   int k = k0, cc = c0;
   if (draws) {  // every earlier draw is done: continue in the window
     const int lim = min(r0 + kP2Win, kAheadTwist);
-    StreamDraw<WinMT> d{WinMT(base - r0 * kLdsStride + lane, c0, lim)};
+    StreamDraw<WinMT> d{WinMT(base - r0 * kWinStride + lane, c0, lim)};
 #pragma unroll 1
     for (int i = d0; i < d1; i++) {
       if (d.m.pos >= lim) break;
@@ -2323,7 +2411,7 @@ __device__ __forceinline__ void p2_draw(const P2Args &a, int blk, int code) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int b0 = blk * kBlock;
   if (code < kP2Draw) {
-    p2_draw_stage(a, b0, lane, code, w * kP2WinRows * kLdsStride);
+    p2_draw_stage(a, b0, lane, code, w * kP2WinRows * kWinStride);
   } else if (code == kWvP1 && b0 + lane < a.n) {
     p2_p1(a, b0 + lane);
   } else if (code == kWvHash && b0 + lane < a.n) {
