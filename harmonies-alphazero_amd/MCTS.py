@@ -107,10 +107,13 @@ class _FoldedRows:
 
     device_rows = True
     capturable = True  # HIP kernels + PyTorch ops only: one simulation is replayed as a HIP graph
-    row_independent = True  # each row computed on its own (arrival-order leaf batches are fine)
 
     def __init__(self, folded):
         self.f = folded
+
+    @property
+    def row_independent(self):  # each row computed on its own (arrival-order leaf batches are fine)
+        return self.f.row_independent
 
     @property
     def graph_key(self):  # the captured simulation stays valid for this network generation

@@ -492,6 +492,16 @@ class FoldedNet(nn.Module):
         """Piece products per fp32 product in the tower (None: the f32 MFMA)."""
         return self.TOWER_PRODUCTS.get(self.tower)
 
+    @property
+    def row_independent(self):
+        """True where every stage is one of the HIP kernels, which sum a row
+        in one order whatever batch it is in (so its result is the same bits
+        in any batch).  The unfused head's F.linear (a value-head width other
+        than 256) and the MIOpen convs (other filter counts) choose their
+        algorithm by the batch size: measured on a 128x20 net with hidden 512,
+        a row's value differed in the last bits between a batch of 1 and of 803."""
+        return self.stem_packed is not None and (self.packed is not None or not self.blocks) and self.fc is not None
+
     def set_tower(self, kind):
         """Switch the tower mode.  Among "x6", "x3", "x1" nothing is re-folded
         or re-packed (they share the packed weights); `generation` is bumped

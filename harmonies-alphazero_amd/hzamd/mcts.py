@@ -379,8 +379,9 @@ class BatchedPredictor:
         self.capturable = self.fast is not None and (dtype is None or dtype == torch.float32)
         # the folded kernels compute every row on its own, in one summation
         # order whatever the batch (test_predict_rows_do_not_depend_on_batch_size);
-        # the PyTorch/MIOpen path makes no such promise
-        self.row_independent = self.capturable
+        # the PyTorch/MIOpen path makes no such promise, nor do the unfused
+        # head's F.linear layers (FoldedNet.row_independent)
+        self.row_independent = self.capturable and self.fast.row_independent
 
     def refresh(self):
         """Re-fold after the model's weights changed."""

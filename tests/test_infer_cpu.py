@@ -1,7 +1,9 @@
 """FoldedNet (BatchNorm folded into the convs, NHWC; its HIP epilogue
 restated in torch here) computes the eval-mode
 reference network up to fp32 rounding: max |diff| <= 1e-4 on logits and
-values (non-trivial BatchNorm statistics, default 128x8 architecture)."""
+values (non-trivial BatchNorm statistics; the default 128x8 architecture,
+the tiny one, and 128-filter nets of other depths and value-head widths)."""
+import pytest
 import torch
 
 from hzamd.infer import FoldedNet
@@ -48,6 +50,29 @@ def test_folded_matches_eval_default():
 
 def test_folded_matches_eval_tiny():
     _check(TINY, 64)
+
+
+# (num_res_blocks, value_head_hidden_dim) other than the default 8 x 256, all
+# with 128 filters (the widths FoldedNet sends to the HIP kernels on a GPU):
+# no tower, one block, an odd depth with a narrow value head, past the
+# one-launch tower's 16 blocks with a wide one, the resident tower's last
+# depth (64 convs) and the first past it.  tests/test_net_shapes_gpu.py runs
+# the same shapes through the kernels.
+NET_SHAPES = [(0, 256), (1, 256), (3, 64), (20, 512), (32, 256), (33, 256)]
+
+
+@pytest.mark.parametrize("blocks,hidden", NET_SHAPES)
+def test_folded_matches_eval_other_depths_and_head_widths(blocks, hidden):
+    """The BN folding per block and the head split for a hidden width other
+    than 256 (the heads' linear layers are snapshots, not folded)."""
+    _check(dict(num_res_blocks=blocks, value_head_hidden_dim=hidden), 8)
+
+
+def test_torch_path_claims_no_row_independence():
+    """FoldedNet.row_independent is the HIP kernels' promise (a row's bits do
+    not depend on its batch); the PyTorch convs and linear layers make none."""
+    assert not FoldedNet(HarmoniesNet(TINY).eval(), torch_epilogue).row_independent
+    assert not FoldedNet(HarmoniesNet().eval(), torch_epilogue).row_independent
 
 
 def test_refresh_tracks_weight_updates():
