@@ -104,13 +104,11 @@ struct hz_env {
   int32_t *ar_ep[2];         // [n] episode counter at the start of an auto-reset call, by call parity
   int ar_calls, ar_primed;
   // per-ply draw windows (k_step / k_ply; see PlyWin): 12 stream words per
-  // board saved by the ply before a turn end, tagged with the cursor and
-  // the stream epoch, which every other entry point that can move or
-  // rewrite streams bumps
+  // board saved by the ply before a turn end, tagged with the cursor; every
+  // other entry point that can move or rewrite streams sets the tags to
+  // none in stream order (its kernel, or touch)
   uint32_t *pw_words;        // [kPlyWin][nrow]
   int32_t *pw_tag;           // [nrow] cursor the words start at (-1: none)
-  int32_t *pw_ep;            // [nrow] stream epoch of the words
-  uint32_t mt_epoch;         // moved by streams_touched alone
   // pipeline 2 (hz_env_set_pipeline(e, 2); see k_play2): every board's game
   // spread over kP2Stages consecutive hz_play calls, one stage per call
   int pipeline;              // 1: chance-ahead (k_rollout's roles), 2: k_play2
@@ -306,36 +304,36 @@ __global__ void __launch_bounds__(kBlock) k_legal(const uint64_t *__restrict__ s
 // first placement twists the stream ahead until 12 words past the cursor
 // are twisted; the ply that makes the second saves those 12 words in the
 // board's slot (word-major, so the turn-ending ply loads them coalesced,
-// with its state, in the same round trip), tagged with the cursor and the
-// env's stream epoch.  The turn-ending ply draws from the slot when both
-// tags match (WinGMT's window, marked fresh: no load), from memory
-// otherwise.  The words are the stream's own and every other entry point
-// that can move or rewrite a stream bumps the epoch, so results never
-// depend on the slot.
+// with its state, in the same round trip), tagged with the cursor.  The
+// turn-ending ply draws from the slot when the tag is its cursor (WinGMT's
+// window, marked fresh: no load), from memory otherwise.  The words are the
+// stream's own, and every other entry point that can move or rewrite a
+// stream voids the tags on the device, in stream order: hz_rollout's and
+// hz_play's kernels store -1 to the tag of every board they play (with its
+// cursor), the others fill every tag with -1 first (touch, below).  A
+// captured call does so again at every replay and a replayed ply reads the
+// tags current, so results never depend on the slot.
 constexpr int kPlyWin = 12;
 static_assert(kPlyWin == 12, "WinMT12's window");
 struct PlyWin {
   uint32_t *w;   // [kPlyWin][nrow]
   int32_t *tag;  // [nrow]
-  int32_t *ep;   // [nrow]
   long nrow;
-  int32_t epoch;
 };
 struct PlyWinIn {  // a board's slot, loaded with its state
   uint32_t q[kPlyWin];
-  int32_t tag, ep;
+  int32_t tag;
 };
 __device__ __forceinline__ PlyWinIn win_load(const PlyWin &pw, int b) {
   PlyWinIn in;
 #pragma unroll
   for (int j = 0; j < kPlyWin; j++) in.q[j] = pw.w[(size_t)j * pw.nrow + b];
   in.tag = pw.tag[b];
-  in.ep = pw.ep[b];
   return in;
 }
 // the turn-ending ply: draw from the saved words when they are this cursor's
-__device__ __forceinline__ void win_take(const PlyWin &pw, const PlyWinIn &in, WinMT12 &m, int cursor) {
-  if (in.tag == cursor && in.ep == pw.epoch) {
+__device__ __forceinline__ void win_take(const PlyWinIn &in, WinMT12 &m, int cursor) {
+  if (in.tag == cursor) {
 #pragma unroll
     for (int j = 0; j < kPlyWin; j++) m.q[j] = in.q[j];
     m.left = kPlyWin;
@@ -366,7 +364,6 @@ __device__ __forceinline__ void win_prepare(const PlyWin &pw, WinMT12 &m, int b,
   for (int j = 0; j < kPlyWin; j++)
     pw.w[(size_t)j * pw.nrow + b] = sh == 0 ? f[j] : sh == 1 ? f[j + 1] : sh == 2 ? f[j + 2] : f[j + 3];
   pw.tag[b] = m.cursor();
-  pw.ep[b] = pw.epoch;
 }
 
 // the same masks unpacked to one byte per action (bool [n][143], what
@@ -414,7 +411,7 @@ __global__ void __launch_bounds__(kBlock) k_step(uint64_t *__restrict__ st, uint
   // (the compiler would sink these loads past the no-op branch: a second
   // round trip; naming them here keeps all of them in the first)
   asm volatile("" ::"v"(s.pl[0]), "v"(s.pl[1]), "v"(s.pl[2]), "v"(s.pl[3]), "v"(s.piles), "v"(s.misc), "v"(c0),
-               "v"(win.tag), "v"(win.ep), "v"(win.q[0]), "v"(win.q[1]), "v"(win.q[2]), "v"(win.q[3]), "v"(win.q[4]),
+               "v"(win.tag), "v"(win.q[0]), "v"(win.q[1]), "v"(win.q[2]), "v"(win.q[3]), "v"(win.q[4]),
                "v"(win.q[5]), "v"(win.q[6]), "v"(win.q[7]), "v"(win.q[8]), "v"(win.q[9]), "v"(win.q[10]),
                "v"(win.q[11]));
   if (a < 0) {
@@ -422,7 +419,7 @@ __global__ void __launch_bounds__(kBlock) k_step(uint64_t *__restrict__ st, uint
     return;
   }
   StreamDraw<WinMT12> d{WinMT12(mt + (size_t)b * kMT, c0)};
-  if (phase_of(s.misc) == PH_P3) win_take(pw, win, d.m, c0);
+  if (phase_of(s.misc) == PH_P3) win_take(win, d.m, c0);
   int r = step_state(s, a, d);
   if (r == ST_OK) {
     store_state(st, n, b, s);
@@ -504,7 +501,7 @@ __global__ void __launch_bounds__(kBlock) k_ply(uint64_t *__restrict__ st, uint3
   // the twist it may need) fetched now, under the legal-mask and rule work
   const bool early = phase_of(s.misc) == PH_P3 && !game_done(s.misc);
   if (early) {
-    win_take(pw, win, d.m, c0);
+    win_take(win, d.m, c0);
     d.m.prefetch();  // (a no-op after win_take)
   }
   uint64_t m[3];
@@ -1147,7 +1144,7 @@ __global__ void __launch_bounds__(kStageThreads) k_rollout(uint64_t *__restrict_
                                                     const int32_t *__restrict__ prep_ep, Ring rs, Ring r1,
                                                     Ring r2, long nrow, const uint32_t *__restrict__ ahead_rule,
                                                     uint32_t *__restrict__ prep_rule, int32_t *__restrict__ mt_src,
-                                                    int src_slot, ArArgs ar) {
+                                                    int src_slot, ArArgs ar, int32_t *__restrict__ win_tag) {
 #ifdef HZ_DIAG
   uint64_t role_t0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -1530,6 +1527,7 @@ __global__ void __launch_bounds__(kStageThreads) k_rollout(uint64_t *__restrict_
     else if (draw.fell) pos[b] = draw.gm.cursor();
     else pos[b] = cur_b[(size_t)draw.d * n];
     mt_src[b] = lds_used ? -1 : src_b;
+    win_tag[b] = -1;  // the board's saved draw window (PlyWin): none, its stream has moved
     ply[b] = g_ply;
     seed[b] = sd;
 #if defined(HZ_DIAG) && !defined(HZ_DIAG_ROLES_ONLY)
@@ -1703,6 +1701,7 @@ struct P2Args {
   uint64_t seed_base;
   long nrow;
   int32_t *games_done, *steps_done, *mt_src;
+  int32_t *win_tag;           // [nrow] PlyWin's tags: the last play stage sets its board's to none
   const int32_t *ep_in;
   int32_t *ep_out;
   uint32_t *s_mt[kP2Stages];  // the stream slot of each stage this call ([0], P1: none)
@@ -2522,6 +2521,7 @@ __device__ __forceinline__ void p2_play(const P2Args &a, int blk, int st, bool i
       store_state(a.st, a.n, b, s);
       a.pos[b] = cursor;
       a.mt_src[b] = src;
+      a.win_tag[b] = -1;
       a.ply[b] = g;
       a.seed[b] = sd;
       a.ep_out[b] = e + 1;
@@ -2719,14 +2719,14 @@ __global__ void __launch_bounds__(64) k_mt_materialize_ar(uint32_t *__restrict__
   if (lane == 0) mt_src[b] = -1;
 }
 
-// (the device side keeps the epoch as int32: only ever compared for equality)
-static PlyWin ply_win(hz_env *e) {
-  return PlyWin{e->pw_words, e->pw_tag, e->pw_ep, (long)e->nrow, (int32_t)e->mt_epoch};
-}
+static PlyWin ply_win(hz_env *e) { return PlyWin{e->pw_words, e->pw_tag, (long)e->nrow}; }
+
+// the saved draw windows voided on e's stream (streams_touched, hz_host.hpp):
+// 0, or 1 if the fill could not be enqueued
+static int touch(hz_env *e) { return streams_touched<HipDev>(e) ? 0 : 1; }
 
 static int materialize(hz_env *e) {
-  if (!e->lazy) return 0;
-  streams_touched(e);  // streams rewritten (PlyWin's saved words are stale)
+  if (!e->lazy) return 0;  // (a lazy board's PlyWin window was voided by the kernel that moved its stream)
   if (e->ar_mt)
     hipLaunchKernelGGL(k_mt_materialize_ar, dim3(e->n), dim3(64), 0, e->stream, e->mt, e->ar_mt, e->mt_src, e->n);
   hipLaunchKernelGGL(k_mt_materialize, dim3(e->n), dim3(64), 0, e->stream, e->mt, e->ahead_mt[0], e->ahead_mt[1],
@@ -2818,8 +2818,7 @@ static int alloc_p2(hz_env *e) {
 // call c is read by call c + 1 or later, so launch order on the stream is the
 // only synchronisation.
 static int launch_play2(hz_env *e, int32_t max_plies, int32_t *games_done, int32_t *steps_done) {
-  streams_touched(e);  // (may move or rewrite streams: PlyWin; hz_play checked e)
-  if (alloc_p2(e)) return 1;
+  if (alloc_p2(e)) return 1;  // (k_play2 voids PlyWin's window of every board it finishes; hz_play checked e)
   const int c = e->calls2, r = c & 1, w = r ^ 1;
   if (!e->primed2) {
     if (hipMemcpyAsync(e->p2_ep[w], e->episode, (size_t)e->n * sizeof(int32_t), hipMemcpyDeviceToDevice,
@@ -2846,6 +2845,7 @@ static int launch_play2(hz_env *e, int32_t max_plies, int32_t *games_done, int32
   a.games_done = games_done;
   a.steps_done = steps_done;
   a.mt_src = e->mt_src;
+  a.win_tag = e->pw_tag;
   a.ep_in = e->p2_ep[w];
   a.ep_out = e->p2_ep[r];
   auto sl = [c](int s) { return ((c - s) % kP2Stream + kP2Stream) % kP2Stream; };
@@ -2932,7 +2932,6 @@ hz_env *hz_env_create(int32_t n_boards, uint64_t seed_base, void *stream) {
   }
   o.get(e->pw_words, nr * kPlyWin * sizeof(uint32_t));
   o.get(e->pw_tag, nr * i32, 0xff);
-  o.get(e->pw_ep, nr * i32, 0);
   o.get(e->wait_err_own, i32, 0);
   e->seed_ahead = kAheadDraws;
   e->ar_ahead = env_pick("HZ_AR_AHEAD", 0, 1);
@@ -2957,7 +2956,6 @@ hz_env *hz_env_create(int32_t n_boards, uint64_t seed_base, void *stream) {
         cuts_gaps_within(dc, kP2Draw + 1, kP2StageDraws))
       for (int k = 0; k <= kP2Draw; k++) e->p2_dcut[k] = dc[k];
   }
-  e->mt_epoch = 1;
   e->wait_err = e->wait_err_own;
   e->spin_limit = kSpinLimitDefault;
   if (!o.ok || hipDeviceSynchronize() != hipSuccess) {
@@ -3012,14 +3010,20 @@ int hz_env_set_stream(hz_env *e, void *stream) {
 
 uint64_t *hz_env_state_ptr(hz_env *e) { return e ? e->state : nullptr; }
 uint32_t *hz_env_mt_ptr(hz_env *e) {  // the streams are made current first (materialize)
-  if (!e || materialize(e)) return nullptr;
-  streams_touched(e);  // the caller may move or rewrite streams (PlyWin)
+  if (!e || materialize(e) || touch(e)) return nullptr;  // the caller may move or rewrite streams (PlyWin)
   return e->mt;
 }
 int32_t *hz_env_mt_pos_ptr(hz_env *e) {
-  if (!e) return nullptr;
-  streams_touched(e);
+  if (!e || touch(e)) return nullptr;
   return e->pos;
+}
+int hz_env_stream_ptrs(hz_env *e, uint32_t **mt, int32_t **mt_pos, int32_t **win_tag) {
+  if (!e || !mt || !mt_pos || !win_tag) return -1;
+  if (int err = materialize(e)) return err;
+  *mt = e->mt;
+  *mt_pos = e->pos;
+  *win_tag = e->pw_tag;
+  return 0;
 }
 int32_t *hz_env_ply_ptr(hz_env *e) { return e ? e->ply : nullptr; }
 uint64_t *hz_env_seed_ptr(hz_env *e) { return e ? e->seed : nullptr; }
@@ -3038,7 +3042,7 @@ int hz_env_set_seed_ahead(hz_env *e, int32_t draws) {
 
 int hz_reset(hz_env *e, const uint8_t *sel, const uint64_t *seeds) {
   if (!e) return -1;
-  streams_touched(e);  // (may move or rewrite streams: PlyWin)
+  if (touch(e)) return 1;  // (may move or rewrite streams: PlyWin)
   if (int err = materialize(e)) return err;  // unselected boards keep their streams
   e->primed = 0;  // episode counters move outside hz_play's plan
   e->primed2 = 0;
@@ -3099,7 +3103,7 @@ int hz_rule_actions(hz_env *e, const uint64_t *mask, const int32_t *count, int16
 
 int hz_greedy_actions(hz_env *e, const uint8_t *sel, int16_t *action) {
   if (!e || !action) return -1;
-  streams_touched(e);  // (may move or rewrite streams: PlyWin)
+  if (touch(e)) return 1;  // (may move or rewrite streams: PlyWin)
   if (int err = materialize(e)) return err;
   hipLaunchKernelGGL(k_greedy, dim3(e->n), dim3(64), 0, e->stream, e->state, e->mt, e->pos, e->n, sel, action);
   return launch_err();
@@ -3140,8 +3144,7 @@ static int alloc_ar(hz_env *e) {
 // ep_final from the counters.
 static int launch_rollout(hz_env *e, int32_t max_plies, int32_t auto_reset, int reset_first, uint64_t *traj_state,
                           uint64_t *traj_mask, int16_t *traj_action, int32_t *games_done, int32_t *steps_done) {
-  if (!e || max_plies < 0) return -1;
-  streams_touched(e);  // (may move or rewrite streams: PlyWin)
+  if (!e || max_plies < 0) return -1;  // (k_rollout voids PlyWin's window of every board it plays)
   e->primed2 = 0;  // (pipeline 2's episode prediction is stale after this launch)
   // hz_rollout continues the current games on their streams; hz_play starts
   // every board's next game (its old stream is dead)
@@ -3209,7 +3212,7 @@ static int launch_rollout(hz_env *e, int32_t max_plies, int32_t auto_reset, int 
                      traj_mask, traj_action, games_done, steps_done, ahead_mt, ahead_tag, ahead_pile, ahead_cur,
                      e->seed_ahead, ep_final, nblk, e->ahead_mt[w], e->ahead_tag[w], e->ahead_pile[w],
                      e->ahead_cur[w], e->ep_final[w], ring(c3), ring((c3 + 2) % kRing), ring((c3 + 1) % kRing),
-                     (long)e->nrow, ahead_rule, e->ahead_rule[w], e->mt_src, ahead_mt ? r : -1, ar);
+                     (long)e->nrow, ahead_rule, e->ahead_rule[w], e->mt_src, ahead_mt ? r : -1, ar, e->pw_tag);
   int err = launch_err();
   if (err) return err;
   if (ahead_mt) e->lazy = 1;
@@ -3255,7 +3258,7 @@ int hz_export_state(hz_env *e, uint64_t *state, uint32_t *mt, int32_t *mt_index)
 
 int hz_import_state(hz_env *e, const uint64_t *state, const uint32_t *mt, const int32_t *mt_index) {
   if (!e) return -1;
-  streams_touched(e);  // (may move or rewrite streams: PlyWin)
+  if (touch(e)) return 1;  // (may move or rewrite streams: PlyWin)
   if ((mt == nullptr) != (mt_index == nullptr)) return -2;
   size_t n = (size_t)e->n;
   if (state && hipMemcpyAsync(e->state, state, n * 6 * sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream))
@@ -3271,7 +3274,7 @@ int hz_import_state(hz_env *e, const uint64_t *state, const uint32_t *mt, const 
 
 int hz_replenish(hz_env *e, const uint8_t *sel) {
   if (!e) return -1;
-  streams_touched(e);  // (may move or rewrite streams: PlyWin)
+  if (touch(e)) return 1;  // (may move or rewrite streams: PlyWin)
   if (int err = materialize(e)) return err;
   hipLaunchKernelGGL(k_turn_op, dim3(grid_for(e->n)), dim3(kBlock), 0, e->stream, e->state, e->mt, e->pos, e->n, sel,
                      0);
@@ -3280,7 +3283,7 @@ int hz_replenish(hz_env *e, const uint8_t *sel) {
 
 int hz_end_turn(hz_env *e, const uint8_t *sel) {
   if (!e) return -1;
-  streams_touched(e);  // (may move or rewrite streams: PlyWin)
+  if (touch(e)) return 1;  // (may move or rewrite streams: PlyWin)
   if (int err = materialize(e)) return err;
   hipLaunchKernelGGL(k_turn_op, dim3(grid_for(e->n)), dim3(kBlock), 0, e->stream, e->state, e->mt, e->pos, e->n, sel,
                      1);

@@ -2,7 +2,7 @@
 //
 //   env_int / env_pick / env_clamped / env_cuts(_n), Setting : the environment knobs
 //   DevBufsT<Dev>                                        : owner of device buffers
-//   streams_touched(e)                                   : the stream epoch
+//   streams_touched<Dev>(e)                              : voids the saved draw windows
 //   launch_err(), lds_opt_in<Kernel>(bytes)              : launch helpers (HIP only)
 //
 // Everything above the HIP section compiles with a plain C++17 compiler
@@ -143,15 +143,20 @@ struct DevBufsT {
   }
 };
 
-// ------------------------------------------------------------ stream epoch
-// The one place an env's stream epoch moves (PlyWin, hz_env.hip): every entry
-// point that can move or rewrite a board's stream calls this once it knows e
-// is not null.  Unsigned: it is bumped per launch and may wrap.
-// (Not done here: clearing pw_tag on the device so that a replayed graph
-// cannot trust a stale window; that changes kernels.)
-template <class Env>
-inline void streams_touched(Env *e) {
-  e->mt_epoch++;
+// ----------------------------------------------------------- stream windows
+// The one place an env's saved draw windows (PlyWin, hz_env.hip) are voided:
+// every entry point that can move or rewrite a board's stream calls this once
+// it knows e is not null, before it enqueues its own work, unless its kernel
+// stores -1 to the tag of each board whose cursor it writes (hz_rollout,
+// hz_play, the search's expansion: launch-bound paths).  Every board's
+// window tag goes to -1 (none) by a fill in stream order, so a captured call
+// voids the windows again at every replay, and a replayed per-ply launch
+// reads the tags that the calls enqueued before it left: whether a window is
+// trusted never depends on a value the host passed at launch.  False if the
+// fill could not be enqueued.
+template <class Dev, class Env>
+inline bool streams_touched(Env *e) {
+  return Dev::fill_async(e->pw_tag, 0xff, e->nrow * sizeof(*e->pw_tag), (void *)e->stream);
 }
 
 }  // namespace hz_host

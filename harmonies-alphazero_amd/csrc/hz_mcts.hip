@@ -674,7 +674,8 @@ static_assert(sizeof(uint64_t) * kChildLds * 6 >= sizeof(uint32_t) * kMT, "the s
 // mix (:308-327).  noise[b*69 + i] is the i-th legal move's Dirichlet sample.
 // (board b, one wave; the kernel below adds the next simulation's select)
 __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts &m, uint32_t *__restrict__ mtw,
-                                                    int32_t *__restrict__ mtcur, const float *__restrict__ policy,
+                                                    int32_t *__restrict__ mtcur, int32_t *__restrict__ wtag,
+                                                    const float *__restrict__ policy,
                                                     const float *__restrict__ value,
                                                     const double *__restrict__ noise, double eps,
                                                     float one_minus_eps, int testing,
@@ -764,7 +765,10 @@ __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts 
         if (npiles_of(ls.piles) == 4 && bag > 21) {
           // one pile per child, random.sample's set method: the wave-parallel form
           const int cur = turn_end_draws_parallel(L.mt, mtcur[b], ls.misc, nl, lane, L.script, L.acc);
-          if (lane == 0) mtcur[b] = cur;
+          if (lane == 0) {
+            mtcur[b] = cur;
+            wtag[b] = -1;  // the env's saved draw window of this board: none (hz_env_stream_ptrs)
+          }
         } else if (lane == 0) {  // fewer piles or the pool method: one lane, serially
           StreamDraw<MT> draw{MT(L.mt, mtcur[b])};
           for (int c = 0; c < nl; c++) {
@@ -772,6 +776,7 @@ __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts 
             L.script[c] = replenish(tmp, draw);
           }
           mtcur[b] = draw.m.cursor();
+          wtag[b] = -1;
         }
         wave_lds_sync();
         HZ_XSTAMP(9)
@@ -1107,6 +1112,7 @@ __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts 
 template <int Waves, bool Sel, bool Gather = false, int BPW = 1, bool WaveSlot = false>  // Waves: minimum waves per SIMD the register allocation must allow (3: none forced)
 __global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_eu(Waves, 8))) k_expand_backup(hz_mcts m, uint32_t *__restrict__ mtw,
                                                          int32_t *__restrict__ mtcur,
+                                                         int32_t *__restrict__ wtag,
                                                          const float *__restrict__ policy,
                                                          const float *__restrict__ value,
                                                          const double *__restrict__ noise, double eps,
@@ -1126,7 +1132,7 @@ __global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_e
   const int b = (int)blockIdx.x * BPW + w;
   const bool live = BPW == 1 || b < m.n;
   if (live)
-    expand_backup_board(L, m, mtw, mtcur, policy, value, noise, eps, one_minus_eps, testing, row_of, prio, b, lane,
+    expand_backup_board(L, m, mtw, mtcur, wtag, policy, value, noise, eps, one_minus_eps, testing, row_of, prio, b, lane,
                         Sel);
   if (Sel) {
     __builtin_amdgcn_s_setprio(0);
@@ -1307,6 +1313,47 @@ __global__ void __launch_bounds__(kWave) k_path_edges(hz_mcts m, unsigned long l
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, kWave);
   if (lane == 0 && acc) atomicAdd(out, acc);
 }
+
+// canon_key_child against canon_key (hz_key_check): for every legal action of
+// every given state, the child's key built from its parent's equals the key
+// built from the child's state, in both key forms.  One thread per (state,
+// action); turn-ending children draw piles from a per-pair script.
+__global__ void __launch_bounds__(256) k_key_check(const uint64_t *__restrict__ st, int n,
+                                                   unsigned long long *__restrict__ out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)n * kActions) return;
+  const int b = (int)(i / kActions), a = (int)(i % kActions);
+  State s;
+  for (int k = 0; k < 4; k++) s.pl[k] = st[(size_t)k * n + b];
+  s.piles = st[(size_t)4 * n + b];
+  s.misc = st[(size_t)5 * n + b];
+  if (game_done(s.misc)) return;
+  uint64_t mk[3];
+  legal_mask(s, mk);
+  if (!((mk[a >> 6] >> (a & 63)) & 1)) return;
+  unsigned long long bad = 0;
+  for (int py = 0; py < 2; py++) {
+    State ch = s;
+    // a pile script of valid tiles (three tiles per pile, 0..5)
+    uint64_t z = mix64(((uint64_t)b << 8) ^ (uint64_t)a), script = 0;
+    for (int q = 0; q < 5; q++) {
+      uint64_t p9 = (z % 6) | ((z / 6) % 6) << 3 | ((z / 36) % 6) << 6;
+      script |= p9 << (9 * q);
+      z = mix64(z);
+    }
+    ScriptDraw sd{script};
+    if (step_state(ch, a, sd) != ST_OK) {
+      bad |= 4;
+      continue;
+    }
+    const CKey want = canon_key(ch, py), pk = canon_key(s, py);
+    const CKey got = canon_key_child(pk, s, ch, a, py);
+    if (!key_eq(want, got)) bad |= 1ull << py;
+  }
+  atomicAdd(&out[0], 1ull);
+  if (bad) atomicAdd(&out[1], 1ull);
+  if (bad & 4) atomicAdd(&out[2], 1ull);
+}
 }  // namespace
 
 extern "C" {
@@ -1453,13 +1500,14 @@ static int expand_backup(hz_mcts *m, hz_env *env, const float *policy, const flo
   // HZ_EXPAND_PRIO=0: the turn-end waves keep the default issue priority (A/B)
   static const int prio = env_pick("HZ_EXPAND_PRIO", 0, 1);
   static const bool wave_slot = env_pick("HZ_SLOT_WAVE", 1, 0);
-  // the env's streams made current (materialize) and its epoch moved, once per call
-  uint32_t *const mt = hz_env_mt_ptr(env);
-  int32_t *const mt_pos = hz_env_mt_pos_ptr(env);
-  if (!mt || !mt_pos) return 1;
+  // the env's streams made current (materialize), once per call; the kernel
+  // voids the saved draw window of every board whose stream it moves
+  uint32_t *mt = nullptr;
+  int32_t *mt_pos = nullptr, *win_tag = nullptr;
+  if (hz_env_stream_ptrs(env, &mt, &mt_pos, &win_tag)) return 1;
 #define HZ_EXPAND_LAUNCH(W, S, G, BP, ...)                                                                      \
   hipLaunchKernelGGL((k_expand_backup<W, S, G, BP, ##__VA_ARGS__>), dim3((m->n + (BP) - 1) / (BP)), dim3(kWave * (BP)), \
-                     0, m->stream, *m, mt, mt_pos, policy, value, noise, eps, ome, testing, slot, prio, active, cpuct, \
+                     0, m->stream, *m, mt, mt_pos, win_tag, policy, value, noise, eps, ome, testing, slot, prio, active, cpuct, \
                      board, glob, rows, count_out, count_prev, add_prev)
   const bool gat = sel && count_out;
   if (waves == 4) {
@@ -1535,6 +1583,15 @@ int hz_mcts_diag_stamps(uint64_t *host) {
 int hz_mcts_path_edges(hz_mcts *m, int64_t *out) {
   if (!m || !out) return -1;
   hipLaunchKernelGGL(k_path_edges, dim3(m->n), dim3(kWave), 0, m->stream, *m, (unsigned long long *)out);
+  return launch_err();
+}
+
+int hz_key_check(const uint64_t *states, int32_t n, int64_t *out, void *stream) {
+  if (!states || !out || n < 0 || (long long)n * kActions > 0x7fffffffLL * 256) return -1;
+  if (n == 0) return 0;
+  const long long pairs = (long long)n * kActions;
+  hipLaunchKernelGGL(k_key_check, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, states, n,
+                     (unsigned long long *)out);
   return launch_err();
 }
 

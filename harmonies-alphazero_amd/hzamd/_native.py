@@ -25,6 +25,7 @@ _SIGS = {
     "hz_env_state_ptr": ([_vp], _vp),
     "hz_env_mt_ptr": ([_vp], _vp),
     "hz_env_mt_pos_ptr": ([_vp], _vp),
+    "hz_env_stream_ptrs": ([_vp, _vp, _vp, _vp], _c.c_int),
     "hz_env_ply_ptr": ([_vp], _vp),
     "hz_env_seed_ptr": ([_vp], _vp),
     "hz_reset": ([_vp, _vp, _vp], _c.c_int),
@@ -70,6 +71,7 @@ _SIGS = {
     "hz_mcts_stats": ([_vp, _vp], _c.c_int),
     "hz_mcts_leaf_ptrs": ([_vp, _vp, _vp], _c.c_int),
     "hz_mcts_path_edges": ([_vp, _vp], _c.c_int),
+    "hz_key_check": ([_vp, _c.c_int32, _vp, _vp], _c.c_int),
     "hz_bias_act": ([_vp, _vp, _vp, _c.c_int64, _c.c_int32, _vp], _c.c_int),
     "hz_conv3x3_bias_act": ([_vp, _vp, _vp, _vp, _vp, _c.c_int32, _vp, _vp], _c.c_int),
     "hz_heads": ([_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int32, _vp, _vp], _c.c_int),

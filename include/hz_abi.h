@@ -54,8 +54,17 @@ int32_t hz_env_size(const hz_env *env);
 int hz_env_set_stream(hz_env *env, void *stream);
 /* device pointers of the handle's own buffers (for zero-copy views) */
 uint64_t *hz_env_state_ptr(hz_env *env);     /* [6][n]            */
+/* The two stream pointers are for a caller that may move or rewrite the
+ * streams: each call first voids, in stream order, the draw words that
+ * hz_step / hz_rule_ply keep per board between plies (one small fill). */
 uint32_t *hz_env_mt_ptr(hz_env *env);        /* [n][624]          */
 int32_t *hz_env_mt_pos_ptr(hz_env *env);     /* [n]               */
+/* The same two pointers without that fill, for a kernel launched once per
+ * simulation (hz_mcts_expand_backup*): the streams are made current, and the
+ * caller's kernel must itself store -1 to win_tag[b] ([n], the board's saved
+ * draw window: none) for every board b whose stream words or cursor it
+ * writes, in the launch that writes them.  0 on success. */
+int hz_env_stream_ptrs(hz_env *env, uint32_t **mt, int32_t **mt_pos, int32_t **win_tag);
 int32_t *hz_env_ply_ptr(hz_env *env);        /* [n] plies played in the current game */
 uint64_t *hz_env_seed_ptr(hz_env *env);      /* [n] seed of the current game */
 
@@ -130,7 +139,18 @@ int hz_greedy_actions(hz_env *env, const uint8_t *sel, int16_t *action);
  * starting its next game (auto_reset != 0).  Optional per-ply records
  * (NULL = off): traj_state[(ply*6 + w)*n + b], traj_mask[(ply*n + b)*3 + w],
  * traj_action[ply*n + b] (-1 after the game ended).  games_done[b] counts
- * games finished during the call, steps_done[b] env steps taken. */
+ * games finished during the call, steps_done[b] env steps taken.
+ * A stuck board (no legal move although the game is not over; no play from
+ * hz_reset reaches one, hz_import_state can bring one in) is defined API
+ * behaviour with no reference counterpart (MCTS.py only logs the case):
+ * hz_rollout and hz_play stop such a board for the rest of the call, with
+ * auto_reset on or off: no step and no game counted from there on, and its
+ * state, stream, ply count, seed and episode stay as they are; the other
+ * boards are not affected.  On the per-ply surface the same board gets an
+ * empty mask and count 0 (hz_legal_mask, hz_legal_actions), action -1
+ * (hz_rule_actions, hz_greedy_actions, neither drawing from its stream) and
+ * HZ_ST_NOOP from hz_step / hz_rule_ply; a search leaves its root without
+ * visits (hz_mcts_result all zero, 1 node, 0 edges). */
 int hz_rollout(hz_env *env, int32_t max_plies, int32_t auto_reset, uint64_t *traj_state,
                uint64_t *traj_mask, int16_t *traj_action, int32_t *games_done,
                int32_t *steps_done);
@@ -290,6 +310,16 @@ int hz_mcts_stats(hz_mcts *mcts, int32_t *counts);
  * back_fill, MCTS.py:220-266, visits every edge of its path once): the
  * path-walk term of the tree kernels' algorithmic bytes (bench.py). */
 int hz_mcts_path_edges(hz_mcts *mcts, int64_t *out);
+/* Test entry point: the transposition keys the search builds incrementally
+ * (canon_key_child, from the parent's key) against keys built from the child's
+ * state (canon_key).  states: device [6][n] state words (hz_export_state's
+ * layout).  For every legal action a of every unfinished state, the child is
+ * made by the step rule (a turn-ending child draws its piles from a script
+ * fixed by (b, a)) and both keys are built in both key forms (exact and
+ * Python-hash).  Adds to the device counters out[0..2]: pairs checked, pairs
+ * with a key mismatch or a failed step, pairs whose step failed.  One launch
+ * enqueued on `stream` (hipStream_t, NULL = null stream); no synchronisation. */
+int hz_key_check(const uint64_t *states, int32_t n, int64_t *out, void *stream);
 /* host pointers to the device arrays leaf[n] / leaf_gidx[n] (debugging) */
 int hz_mcts_leaf_ptrs(hz_mcts *mcts, int32_t **leaf, int32_t **leaf_gidx);
 

@@ -69,6 +69,9 @@ def lib():
         L.or_play_rule_auto.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_int64,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         L.or_play_rule_auto.restype = ctypes.c_int64
+        L.or_play_rule_from.argtypes = [ctypes.c_void_p, P(MT), ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64,
+                                        ctypes.c_void_p, ctypes.c_void_p]
+        L.or_play_rule_from.restype = ctypes.c_int64
         L.or_replay_actions.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         L.or_replay_actions.restype = ctypes.c_int64
@@ -186,6 +189,34 @@ def play_rule_auto(n, seed_base, plies, ep0=0, nthreads=0):
     total = lib().or_play_rule_auto(n, ctypes.c_uint64(seed_base), int(ep0), int(plies), _p(finals), _p(games),
                                     _p(ep), nthreads)
     return total, finals, games, ep
+
+
+def play_rule_from(st, m, rule_seed, first_ply, max_plies):
+    """hz_rollout (no auto-reset) on one board of an imported batch: up to
+    max_plies rule-driven steps from state st on the stream m (advanced in
+    place), the rule keyed by (rule_seed, first_ply + k).  A stuck board (no
+    legal move, game not over) ends the call where it is.  Returns (final
+    state [78], steps taken, stuck flag)."""
+    st = np.ascontiguousarray(st, np.int16)
+    final = np.zeros(REFSTATE, np.int16)
+    stuck = ctypes.c_int32(0)
+    steps = lib().or_play_rule_from(_p(st), ctypes.byref(m), ctypes.c_uint64(rule_seed), int(first_ply),
+                                    int(max_plies), _p(final), ctypes.byref(stuck))
+    return final, int(steps), bool(stuck.value)
+
+
+def stuck_state(seed):
+    """A stuck board (no legal move, game not over), which play from a reset
+    never reaches: HarmoniesGameState() after random.seed(seed), pile 0 taken
+    (phase place_tile_1, three tiles in hand), then every cell of the mover's
+    board set to three stones (stack code 9: nothing may be placed on it).
+    Returns (state [78], the stream after the step)."""
+    m = mt_seed(seed)
+    r, st = step(reset(m), 0, m)
+    assert r == 0 and st[73] == 1 and st[65] == 3
+    p = int(st[72])
+    st[23 * p:23 * p + 23] = 9
+    return st, m
 
 
 def replay_actions(seeds, actions, nthreads=0):

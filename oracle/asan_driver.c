@@ -83,6 +83,24 @@ int main(void) {
     h = mix(h, (uint64_t)or_step(st, a, &m));
     h = mix(h, (uint64_t)or_step(st, 142, &m) + 1);  /* usually illegal: a status, the board unchanged */
   }
+  /* rule play from a given state: part of a game, its rest, and a stuck board
+   * (pile 0 taken, then the mover's board full of three-stone stacks) */
+  {
+    int16_t mid[OR_REFSTATE], fin[OR_REFSTATE];
+    int32_t stuck = 0;
+    or_mt_seed(&g, 4242);
+    or_reset(&g, st);
+    int64_t k = or_play_rule_from(st, &g, 4242, 0, 11, mid, &stuck);
+    h = mix(h, (uint64_t)k + 3 * (uint64_t)stuck);
+    k += or_play_rule_from(mid, &g, 4242, k, 1000, fin, &stuck);
+    h = mix(h, (uint64_t)k + 3 * (uint64_t)stuck + 5 * (uint64_t)or_is_game_over(fin));
+    for (int i = 0; i < OR_REFSTATE; i++) h = mix(h, (uint64_t)fin[i]);
+    or_reset(&g, st);
+    h = mix(h, (uint64_t)or_step(st, 0, &g));
+    for (int c = 0; c < 23; c++) st[23 * st[72] + c] = 9;
+    k = or_play_rule_from(st, &g, 4242, 1, 200, fin, &stuck);
+    h = mix(h, (uint64_t)k + 3 * (uint64_t)stuck + 7 * (uint64_t)or_legal(fin, mask));
+  }
   for (int i = 0; i < 4; i++) h = mix(h, or_randbelow(&m, 1 + 37u * (uint32_t)i));
   int32_t smp[8];
   or_sample(&m, 40, 8, smp);

@@ -678,6 +678,41 @@ int64_t or_play_rule_auto(int n, uint64_t seed_base, int ep0, int64_t plies, int
   return total;
 }
 
+/* Rule play from a given state (hz_rollout without auto-reset on one board
+ * of an imported batch): up to max_plies rule-driven steps from st_in on the
+ * stream m, the rule keyed by (rule_seed, first_ply + steps so far).  Stops
+ * when the game is over, and on a stuck board (no legal move, game not over)
+ * exactly as or_play_rule_auto does: the board is left as it is for the rest
+ * of the call, its stream untouched.  The reference has no such rule
+ * (MCTS.py only logs the case); it is this build's defined behaviour.
+ * final: the last state; *stuck: 1 if the call ended on a stuck board.
+ * Returns the steps taken. */
+int64_t or_play_rule_from(const int16_t *st_in, or_mt *m, uint64_t rule_seed, int64_t first_ply, int64_t max_plies,
+                          int16_t *final, int32_t *stuck) {
+  geom_init();
+  ostate s;
+  from_ref(st_in, &s);
+  int64_t left = max_plies, steps = 0;
+  int was_stuck = 0;
+  uint8_t mask[143];
+  while (left > 0 && !(s.game_over && s.winner != -2)) {
+    int L = legal_of(&s, mask);
+    if (!L) {
+      was_stuck = 1;
+      left = 0;
+      break;
+    }
+    uint64_t z = or_rule(rule_seed, (uint64_t)(first_ply + steps));
+    int k = (int)(((z >> 32) * (uint64_t)L) >> 32);
+    step_state(&s, kth_legal(mask, k), m);
+    steps++;
+    left--;
+  }
+  if (final) to_ref(&s, final);
+  if (stuck) *stuck = was_stuck;
+  return steps;
+}
+
 /* A caller's own moves replayed: board b starts HarmoniesGameState() after
  * random.seed(seeds[b]) (harmonies_engine.py:66-79) and applies
  * actions[p * n + b] for p < plies with apply_move (:210-298; a negative

@@ -58,6 +58,12 @@ int64_t or_play_rule_games_ep(int n, uint64_t seed_base, int episode, int16_t *f
  * ep0's reset, each ended game followed by the board's next episode. */
 int64_t or_play_rule_auto(int n, uint64_t seed_base, int ep0, int64_t plies, int16_t *finals, int32_t *games,
                           int32_t *episode_out, int nthreads);
+/* Rule play of one board from a given state and stream: up to max_plies steps,
+ * the rule keyed by (rule_seed, first_ply + k).  A stuck board (no legal move,
+ * game not over) ends the call as in or_play_rule_auto: *stuck = 1, state and
+ * stream as they were.  Returns the steps taken. */
+int64_t or_play_rule_from(const int16_t *st_in, or_mt *m, uint64_t rule_seed, int64_t first_ply, int64_t max_plies,
+                          int16_t *final, int32_t *stuck);
 /* a caller's own moves replayed from random.seed(seeds[b]) resets (the api_caller leg's check) */
 int64_t or_replay_actions(int n, const uint64_t *seeds, int plies, const int16_t *actions, int16_t *finals,
                           int32_t *rejected, int nthreads);

@@ -240,24 +240,35 @@ static void test_bufs() {
   delete h;
 }
 
-// ------------------------------------------------------------------ epoch
+// --------------------------------------------------------- stream windows
 struct FakeEnv {
-  uint32_t mt_epoch;
+  int32_t *pw_tag;
+  size_t nrow;
+  void *stream;
 };
-static void test_epoch() {
-  FakeEnv e{0xFFFFFFFEu};
-  streams_touched(&e);
-  CHECK(e.mt_epoch == 0xFFFFFFFFu);
-  streams_touched(&e);  // wraps: no report from UBSan
-  CHECK(e.mt_epoch == 0u);
-  CHECK((int32_t)e.mt_epoch == 0);
+static void test_windows_voided() {
+  FakeDev::reset(0, 0);
+  FakeEnv e{nullptr, 128, nullptr};
+  int32_t *guard = nullptr;
+  void *raw = nullptr;
+  CHECK(FakeDev::alloc(&raw, (e.nrow + 1) * sizeof(int32_t)));
+  e.pw_tag = static_cast<int32_t *>(raw);
+  guard = e.pw_tag + e.nrow;
+  for (size_t b = 0; b <= e.nrow; b++) e.pw_tag[b] = (int32_t)b;
+  CHECK(streams_touched<FakeDev>(&e));
+  for (size_t b = 0; b < e.nrow; b++) CHECK(e.pw_tag[b] == -1);  // every row's tag: none
+  CHECK(*guard == (int32_t)e.nrow);                              // and nothing past them
+  FakeDev::reset(0, 1);
+  CHECK(!streams_touched<FakeDev>(&e));  // a fill that cannot be enqueued is reported
+  FakeDev::free(raw);
+  CHECK(FakeDev::bad_frees == 0 && FakeDev::live.empty());
 }
 
 int main() {
   test_knobs();
   test_settings();
   test_bufs();
-  test_epoch();
+  test_windows_voided();
   if (g_fail) {
     printf("host driver: %d checks failed\n", g_fail);
     return 1;

@@ -576,15 +576,57 @@ def test_auto_reset_then_per_ply_steps_continue_the_streams(Env):
         assert torch.equal(a, b)
 
 
+def _twisted_streams(Env, n, seed_base):
+    """CPython-form streams (every word of the generation twisted) and their
+    indices: another env's export right after its reset."""
+    src = Env(n, seed_base=seed_base, device=DEV)
+    src.reset()
+    _, mt, idx = src.export_state(with_mt=True)
+    mt, idx = mt.clone(), idx.clone()
+    src.close()
+    return mt, idx
+
+
+def _assert_window_tags_collide(mt_pre, idx_pre, mt_now, idx_now):
+    """The windows saved so far carry the cursor the mid-turn import will
+    write (index | 624 << 16): the exported streams are word for word the
+    fully twisted generation imported before the first ply (an export
+    twists, i.e. rewrites, whatever the cursor's twist position had left
+    below 624, and a generation's end rewrites all of it), and every index
+    moved on inside it with the 12 words of a window to spare."""
+    assert torch.equal(mt_now, mt_pre)
+    assert bool((idx_now > idx_pre).all()) and bool((idx_now <= 624 - 12).all())
+
+
+def _check_imported_plies_vs_oracle(seed_base, boards, st, mt2, idx, got, mt, mi):
+    """The oracle from the imported state and stream (rule seed seed_base + b,
+    plies 7 to 18): board b's state and next MT word."""
+    for b in boards:
+        s = unpack_ref(st[:, b])
+        m = oracle.mt_from_words(mt2[b], idx[b])
+        for p in range(7, 19):
+            if oracle.is_game_over(s):
+                break
+            mask = oracle.legal(s)
+            L = int(mask.sum())
+            act = np.flatnonzero(mask)[((oracle.rule(seed_base + b, p) >> 32) * L) >> 32]
+            s = oracle.step(s, int(act), m)[1]
+        assert (got[b] == s).all(), b
+        assert oracle.mt_next32(oracle.mt_from_words(mt[b], mi[b])) == oracle.mt_next32(m), b
+
+
 @pytest.mark.parametrize("fused", [True, False])
 def test_ply_window_slots_never_change_results(Env, fused):
     """hz_rule_ply / hz_step keep 12 stream words per board from the ply
-    before a turn end (PlyWin, tagged with the cursor and the stream epoch
-    that every stream-rewriting entry point bumps).  Boards whose streams are
+    before a turn end (PlyWin, tagged with the cursor; every stream-rewriting
+    entry point voids the tags on the device).  Boards whose streams are
     replaced mid-turn by hz_import_state at the same CPython index, then
-    played on, match a fresh env given the same states and streams: every
-    state and stream after 12 more plies; and a run that crosses turn ends
-    uninterrupted matches the oracle's rule games."""
+    played on, match the oracle given the same states and streams: every
+    state and stream after 12 more plies.  Every board plays on a fully
+    twisted stream from the first ply on, so the saved tags equal the cursor
+    that the import writes (asserted): only the voiding keeps the stale words
+    from being drawn.  And a run that crosses turn ends uninterrupted matches
+    the oracle's rule games."""
     n = 300
 
     def ply(env):
@@ -596,31 +638,22 @@ def test_ply_window_slots_never_change_results(Env, fused):
 
     a = Env(n, seed_base=5, device=DEV)
     a.reset()
+    mt_pre, idx_pre = _twisted_streams(Env, n, 33)
+    a.import_state(a.export_state(), mt_pre, idx_pre)
     for _ in range(7):  # plies 0-6: windows saved after plies 2 and 6 (turn ends at 3, 7)
         ply(a)
-    st, _, idx = a.export_state(with_mt=True)
-    other = Env(n, seed_base=91, device=DEV)
-    other.reset()
-    _, mt2, _ = other.export_state(with_mt=True)
-    a.import_state(st, mt2, idx)  # other words at the same cursors
+    st, mt_now, idx = a.export_state(with_mt=True)
+    _assert_window_tags_collide(mt_pre, idx_pre, mt_now, idx)
+    mt2, _ = _twisted_streams(Env, n, 91)
+    assert not bool((mt2 == mt_now).all(dim=1).any())
+    a.import_state(st, mt2, idx)  # other words at the same cursors: exactly the exported indices
     for _ in range(12):
         ply(a)
     got = states_of(a)
     _, mt, mi = a.export_state(with_mt=True)
     mt, mi = mt.cpu().numpy().view(np.uint32), mi.cpu().numpy()
     st, mt2, idx = st.cpu().numpy(), mt2.cpu().numpy().view(np.uint32), idx.cpu().numpy()
-    for b in range(0, n, 7):  # the oracle from the imported state and stream (rule seed 5 + b, ply 7)
-        s = unpack_ref(st[:, b])
-        m = oracle.mt_from_words(mt2[b], idx[b])
-        for p in range(7, 19):
-            if oracle.is_game_over(s):
-                break
-            mask = oracle.legal(s)
-            L = int(mask.sum())
-            act = np.flatnonzero(mask)[((oracle.rule(5 + b, p) >> 32) * L) >> 32]
-            s = oracle.step(s, int(act), m)[1]
-        assert (got[b] == s).all(), b
-        assert oracle.mt_next32(oracle.mt_from_words(mt[b], mi[b])) == oracle.mt_next32(m), b
+    _check_imported_plies_vs_oracle(5, range(0, n, 7), st, mt2, idx, got, mt, mi)
     # uninterrupted: whole rule games, turn ends drawing from saved words
     d = Env(n, seed_base=17, device=DEV)
     d.reset()
@@ -633,6 +666,264 @@ def test_ply_window_slots_never_change_results(Env, fused):
     for b in range(n):
         assert (got[b] == finals[b]).all(), b
         assert oracle.mt_next32(oracle.mt_from_words(mt[b], mi[b])) == nxt[b], b
+
+
+@pytest.mark.parametrize("fused", [True, False])
+def test_ply_window_slots_through_a_replayed_graph(Env, fused):
+    """The same scenario with the ply captured once and replayed: a replayed
+    launch repeats the arguments it was captured with, so whether a saved
+    window is trusted must rest on device state that the eager
+    hz_import_state between the replays changes.  130 boards (a partial third
+    block); one captured hz_rule_ply, or the three launches hz_legal_mask,
+    hz_rule_actions, hz_step, on preallocated buffers; replayed 7 times, the
+    streams replaced eagerly at the exported indices (the saved tags equal the
+    cursors the import writes: asserted), replayed 12 times.  Every seventh
+    board's state and next MT word equal the oracle's from the imported state
+    and stream, and every board equals an env that played all 19 plies and the
+    import eagerly."""
+    n, base = 130, 5
+    mt_pre, idx_pre = _twisted_streams(Env, n, 33)
+    mt2, _ = _twisted_streams(Env, n, 91)
+
+    def buffers():
+        return (torch.zeros(n, 3, dtype=torch.int64, device=DEV), torch.zeros(n, dtype=torch.int32, device=DEV),
+                torch.zeros(n, dtype=torch.int16, device=DEV), torch.zeros(n, dtype=torch.int32, device=DEV))
+
+    def ply_of(env, bufs):
+        mask, count, action, status = bufs
+
+        def ply():
+            if fused:
+                env.rule_ply(mask, count, action, status)
+            else:
+                env.legal_mask(mask, count)
+                env.rule_actions(mask, count, action)
+                env.step(action, status)
+        return ply
+
+    def start(env):
+        env.reset()
+        env.import_state(env.export_state(), mt_pre, idx_pre)
+
+    # the kernels loaded by an eager ply of a throwaway env, then one ply
+    # captured on a side stream (bench.py's graph_of)
+    warm = Env(n, seed_base=base, device=DEV)
+    start(warm)
+    ply_of(warm, buffers())()
+    torch.cuda.synchronize()
+    warm.close()
+
+    a = Env(n, seed_base=base, device=DEV)
+    start(a)
+    ply_a = ply_of(a, buffers())
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream(DEV)
+    side.wait_stream(torch.cuda.current_stream(DEV))
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(g, stream=side):
+            ply_a()
+    torch.cuda.current_stream(DEV).wait_stream(side)
+
+    for _ in range(7):
+        g.replay()
+    st, mt_now, idx = a.export_state(with_mt=True)
+    _assert_window_tags_collide(mt_pre, idx_pre, mt_now, idx)
+    assert not bool((mt2 == mt_now).all(dim=1).any())
+    a.import_state(st, mt2, idx)  # eager: no replayed launch carries it
+    for _ in range(12):
+        g.replay()
+    got_st, got_mt, got_idx = (t.cpu() for t in a.export_state(with_mt=True))
+    got = states_of(a)
+
+    f = Env(n, seed_base=base, device=DEV)
+    start(f)
+    ply_f = ply_of(f, buffers())
+    for _ in range(7):
+        ply_f()
+    st_f, mt_f, idx_f = f.export_state(with_mt=True)
+    assert torch.equal(st_f, st) and torch.equal(mt_f, mt_now) and torch.equal(idx_f, idx)
+    f.import_state(st_f, mt2, idx_f)
+    for _ in range(12):
+        ply_f()
+    want_st, want_mt, want_idx = (t.cpu() for t in f.export_state(with_mt=True))
+
+    _check_imported_plies_vs_oracle(base, range(0, n, 7), st.cpu().numpy(), mt2.cpu().numpy().view(np.uint32),
+                                    idx.cpu().numpy(), got, got_mt.numpy().view(np.uint32), got_idx.numpy())
+    bad = (got_st != want_st).any(dim=0) | (got_mt != want_mt).any(dim=1) | (got_idx != want_idx)
+    assert not bool(bad.any()), bad.nonzero().flatten().tolist()[:8]
+    a.close()
+    f.close()
+
+
+def test_ply_window_voided_by_a_fused_play_between_plies(Env):
+    """The fused kernels void the saved windows themselves (no fill in front
+    of their launches).  Seven plies of a board's first game leave a window
+    saved for the turn end at ply 7; hz_play(max_plies=7) then starts the
+    second game and plays its first seven plies in one launch, which as a
+    rule draw as many words as the first game's did: most boards arrive at
+    the saved cursor with another stream under it.  Played on ply by ply,
+    every board finishes the oracle's second game, state and next stream
+    word, as does an env whose first game was never played ply by ply."""
+    n, base = 130, 23
+    a = Env(n, seed_base=base, device=DEV)
+    a.reset()
+    for _ in range(7):
+        a.rule_ply()
+    f = Env(n, seed_base=base, device=DEV)
+    f.reset()
+    for env in (a, f):
+        env.rollout(7, reset=True)
+        for _ in range(96):
+            env.rule_ply()
+        env.check_errors()
+    _, finals, _, nxt = oracle.play_rule_games(n, base, nthreads=8, episode=1)
+    out = []
+    for env in (a, f):
+        got = states_of(env)
+        st, mt, mi = env.export_state(with_mt=True)
+        out.append((st.cpu(), mt.cpu(), mi.cpu()))
+        mt, mi = mt.cpu().numpy().view(np.uint32), mi.cpu().numpy()
+        bad = [b for b in range(n) if not ((got[b] == finals[b]).all()
+                                           and oracle.mt_next32(oracle.mt_from_words(mt[b], mi[b])) == nxt[b])]
+        assert not bad, bad[:8]
+        env.close()
+    for x, y in zip(*out):
+        assert torch.equal(x, y)
+
+
+# ---------------------------------------------------------------- stuck boards
+# A stuck board (no legal move, game not over) cannot be reached from a reset;
+# the kernels leave such a board alone (include/hz_abi.h, hz_rollout).  Boards
+# 0, 63, 64 and 129 of a 130-board mid-game batch are made stuck: the first and
+# the last lane of a wave, the first board of the second wave, and the last
+# board of a partial wave.
+STUCK = (0, 63, 64, 129)
+STUCK_N, STUCK_BASE, STUCK_PLIES = 130, 606, 9
+
+
+def _device_view(ptr, n, typestr):
+    """A torch view of n elements of device memory at ptr (the env's own
+    counters, hz_env_ply_ptr / hz_env_seed_ptr)."""
+    class Raw:
+        __cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+    return torch.as_tensor(Raw(), device=DEV)
+
+
+def _ply_and_seed(env):
+    import hzamd._native as nat
+    torch.cuda.synchronize()
+    ply = _device_view(nat.lib().hz_env_ply_ptr(env.handle), env.n, "<i4").cpu().numpy().copy()
+    seed = _device_view(nat.lib().hz_env_seed_ptr(env.handle), env.n, "<i8").cpu().numpy().copy()
+    return ply, seed
+
+
+def _stuck_batch(Env):
+    """130 boards nine rule plies into their first games, boards STUCK
+    replaced by stuck states (oracle.stuck_state) through export, edit and
+    hz_import_state(state): streams, ply counts and seeds are kept.  Returns
+    the env and its (state words [6, n], streams, indices) as exported."""
+    env = Env(STUCK_N, seed_base=STUCK_BASE, device=DEV)
+    env.reset()
+    for _ in range(STUCK_PLIES):
+        env.rule_ply()
+    words = env.export_state().cpu().numpy().copy()
+    for b in STUCK:
+        st = oracle.stuck_state(STUCK_BASE + b)[0]
+        assert oracle.legal(st).sum() == 0 and not oracle.is_game_over(st)
+        words[:, b] = words_to_array([pack_ref(st)])[0]
+    env.import_state(torch.from_numpy(words))
+    st, mt, idx = (t.cpu().numpy() for t in env.export_state(with_mt=True))
+    assert (st == words).all()
+    return env, st, mt.view(np.uint32), idx
+
+
+def _next_words(mt, idx, boards):
+    return [oracle.mt_next32(oracle.mt_from_words(mt[b], idx[b])) for b in boards]
+
+
+def test_stuck_boards_per_ply_surface(Env):
+    """On a stuck board hz_legal_mask gives an empty mask and count 0,
+    hz_rule_actions -1, hz_step with that action HZ_ST_NOOP (7) and the state
+    unchanged; hz_rule_ply writes what the three calls write and leaves
+    state, stream and ply count as they were; hz_greedy_actions gives -1 and
+    leaves the stream alone.  Every other board of the batch moves on, the
+    same way through both forms."""
+    stuck = list(STUCK)
+    a, st0, mt0, idx0 = _stuck_batch(Env)
+    b, _, _, _ = _stuck_batch(Env)
+    ply0, seed0 = _ply_and_seed(a)
+    assert (ply0 == STUCK_PLIES).all() and (seed0 == STUCK_BASE + np.arange(STUCK_N)).all()
+    mask, count = a.legal_mask()
+    action = a.rule_actions(mask, count)
+    status = a.step(action)
+    assert not mask[stuck].any() and not count[stuck].any()
+    assert (action[stuck] == -1).all() and (status[stuck] == 7).all()
+    others = [i for i in range(STUCK_N) if i not in STUCK]
+    assert (count[others] > 0).all() and (action[others] >= 0).all() and (status[others] == 0).all()
+    outs = (torch.zeros(STUCK_N, 3, dtype=torch.int64, device=DEV), torch.zeros(STUCK_N, dtype=torch.int32, device=DEV),
+            torch.zeros(STUCK_N, dtype=torch.int16, device=DEV), torch.zeros(STUCK_N, dtype=torch.int32, device=DEV))
+    b.rule_ply(*outs)
+    for x, y in zip((mask, count, action, status), outs):
+        assert torch.equal(x, y)
+    for env in (a, b):
+        ply1, seed1 = _ply_and_seed(env)
+        assert (ply1[stuck] == STUCK_PLIES).all() and (ply1[others] == STUCK_PLIES + 1).all()
+        assert (seed1 == seed0).all()
+        st1, mt1, idx1 = (t.cpu().numpy() for t in env.export_state(with_mt=True))
+        assert (st1[:, stuck] == st0[:, stuck]).all() and (st1[:, others] != st0[:, others]).any(axis=0).all()
+        assert (mt1.view(np.uint32)[stuck] == mt0[stuck]).all() and (idx1[stuck] == idx0[stuck]).all()
+    for x, y in zip(a.export_state(with_mt=True), b.export_state(with_mt=True)):
+        assert torch.equal(x, y)
+    # the greedy agent: no move for a stuck board, its stream not drawn from
+    st1, mt1, idx1 = (t.cpu().numpy() for t in a.export_state(with_mt=True))
+    g = a.greedy_actions().cpu().numpy()
+    assert (g[stuck] == -1).all() and (g[others] >= 0).all()
+    st2, mt2, idx2 = (t.cpu().numpy() for t in a.export_state(with_mt=True))
+    assert (st2 == st1).all()
+    assert (mt2[stuck] == mt1[stuck]).all() and (idx2[stuck] == idx1[stuck]).all()
+    a.close()
+    b.close()
+
+
+@pytest.mark.parametrize("auto_reset", [False, True])
+def test_stuck_boards_stop_for_the_call_in_rollout(Env, auto_reset):
+    """hz_rollout(max_plies=200) stops a stuck board for the rest of the call:
+    no step, no game, its state, next stream word, ply count and seed (its
+    episode) as they were, with auto-reset off and on; the oracle's
+    from-state rollout says the same.  A stuck lane does not disturb its
+    wave: every other board ends where the oracle's rule games end (auto-reset
+    off: its game's final state, ply count and next stream word; on: the state
+    and game count after 200 more steps of or_play_rule_auto)."""
+    stuck = list(STUCK)
+    env, st0, mt0, idx0 = _stuck_batch(Env)
+    ply0, seed0 = _ply_and_seed(env)
+    games, steps, _ = env.rollout(200, auto_reset=auto_reset)
+    env.check_errors()
+    games, steps = games.cpu().numpy(), steps.cpu().numpy()
+    st1, mt1, idx1 = (t.cpu().numpy() for t in env.export_state(with_mt=True))
+    mt1 = mt1.view(np.uint32)
+    ply1, seed1 = _ply_and_seed(env)
+    for b in stuck:
+        assert steps[b] == 0 and games[b] == 0, b
+        assert (st1[:, b] == st0[:, b]).all(), b
+        assert ply1[b] == ply0[b] and seed1[b] == seed0[b], b
+        m = oracle.mt_from_words(mt0[b], idx0[b])
+        fin, k, was_stuck = oracle.play_rule_from(unpack_ref(st0[:, b]), m, STUCK_BASE + b, STUCK_PLIES, 200)
+        assert k == 0 and was_stuck and (fin == unpack_ref(st1[:, b])).all(), b
+        assert _next_words(mt1, idx1, [b]) == [oracle.mt_next32(m)], b
+    others = [b for b in range(STUCK_N) if b not in STUCK]
+    if auto_reset:
+        _, finals, ref_games, _ = oracle.play_rule_auto(STUCK_N, STUCK_BASE, STUCK_PLIES + 200, ep0=0, nthreads=4)
+        for b in others:
+            assert (unpack_ref(st1[:, b]) == finals[b]).all() and games[b] == ref_games[b] and steps[b] == 200, b
+    else:
+        _, finals, plies, nxt = oracle.play_rule_games(STUCK_N, STUCK_BASE, nthreads=4)
+        got_next = _next_words(mt1, idx1, others)
+        for b, w in zip(others, got_next):
+            assert (unpack_ref(st1[:, b]) == finals[b]).all() and steps[b] == plies[b] - STUCK_PLIES, b
+            assert games[b] == 1 and w == nxt[b] and seed1[b] == seed0[b], b
+    env.close()
 
 
 def test_legal_actions_bytes_equal_unpacked_mask(Env):

@@ -1,9 +1,10 @@
 """libhz's host layer (csrc/hz_host.hpp: the knob reader, the device-buffer
-owner, the stream epoch) under AddressSanitizer + UndefinedBehaviorSanitizer,
-without a GPU: tests/host_driver.cpp has its own main, checks every knob rule
-against values written out in the driver, runs the buffer owner over a
-counting allocator that fails at every position, and wraps the epoch; any
-report, leak or failed check ends the run non-zero."""
+owner, the voiding of the saved draw windows) under AddressSanitizer +
+UndefinedBehaviorSanitizer, without a GPU: tests/host_driver.cpp has its own
+main, checks every knob rule against values written out in the driver, runs
+the buffer owner over a counting allocator that fails at every position, and
+voids a fake env's window tags (every row, nothing past them, a failed fill
+reported); any report, leak or failed check ends the run non-zero."""
 import os
 import shutil
 import subprocess

@@ -509,3 +509,82 @@ def test_mcts_few_simulations_vs_oracle(sims):
         assert oracle.mt_next32(oracle.mt_from_words(mt1[b], idx1[b])) == oracle.mt_next32(m), b
     mcts.close()
     env.close()
+
+
+def test_mcts_stuck_roots_get_no_visits():
+    """A stuck board (no legal move, game not over: oracle.stuck_state) searched
+    as an active board: no root visits, a tree of the root alone (1 node, 0
+    edges, no overflow flag), choose_actions gives -1 and the board's stream
+    is not drawn from, as the oracle's search of the same state says.  Boards
+    0, 63, 64 and 129 of 130 are stuck; the others, spread over the game, are
+    searched as the oracle searches them (24 simulations, stub evaluator)."""
+    from hzamd.env import BatchedEnv
+    from hzamd.mcts import BatchedMCTS, choose_actions, stub_evaluator
+    n, base, sims, cpuct = 130, 640, 24, 2.0
+    stuck = (0, 63, 64, 129)
+    env = BatchedEnv(n, seed_base=base, device=DEV)
+    env.reset()
+    plies = torch.arange(n, device=DEV) % 41
+    for p in range(41):
+        mask, count = env.legal_mask()
+        act = env.rule_actions(mask, count)
+        env.step(torch.where(plies > p, act, torch.full_like(act, -1)))
+    words = env.export_state().cpu().numpy().copy()
+    for b in stuck:
+        words[:, b] = words_to_array([pack_ref(oracle.stuck_state(base + b)[0])])[0]
+    env.import_state(torch.from_numpy(words))  # the streams stay
+    st0, mt0, idx0 = env.export_state(with_mt=True)
+    st0, mt0, idx0 = st0.cpu().numpy(), mt0.cpu().numpy().view(np.uint32), idx0.cpu().numpy()
+    assert (st0 == words).all()
+    assert not any(oracle.is_game_over(unpack_ref(st0[:, b])) for b in range(n))
+    mcts = BatchedMCTS(env, sims)
+    visits = mcts.search(stub_evaluator, cpuct, active=torch.ones(n, dtype=torch.bool))
+    act = choose_actions(visits.cpu(), torch.zeros(n, dtype=torch.bool), torch.zeros(n, dtype=torch.float64)).numpy()
+    visits = visits.cpu().numpy()
+    counts = mcts.stats().cpu().numpy()
+    _, mt1, idx1 = env.export_state(with_mt=True)
+    mt1, idx1 = mt1.cpu().numpy().view(np.uint32), idx1.cpu().numpy()
+    for b in range(n):
+        m = oracle.mt_from_words(mt0[b], idx0[b])
+        a, ov, nn, ne = oracle.mcts_search(unpack_ref(st0[:, b]), m, sims, cpuct, testing=True)
+        assert (visits[b] == ov).all(), b
+        assert (counts[b, 0], counts[b, 1], counts[b, 3]) == (nn, ne, 0), b
+        assert act[b] == a, b
+        assert oracle.mt_next32(oracle.mt_from_words(mt1[b], idx1[b])) == oracle.mt_next32(m), b
+        if b in stuck:
+            assert a == -1 and ov.sum() == 0 and (nn, ne) == (1, 0), b
+            assert (mt1[b] == mt0[b]).all() and idx1[b] == idx0[b], b
+        else:
+            assert ov.sum() > 0 and a >= 0, b
+    mcts.close()
+    env.close()
+
+
+def test_child_keys_equal_full_rebuild_over_whole_games():
+    """canon_key_child (the child's transposition key built from its parent's,
+    what the expansion stores) against canon_key (the key built from the
+    child's state) through hz_key_check: every legal action of 256 boards at
+    every ply of their rule-played games, in both key forms (exact and
+    Python-hash).  The pairs checked are the legal moves the loop saw; none
+    mismatches and no step fails."""
+    import hzamd._native as nat
+    from hzamd.env import BatchedEnv
+    n = 256
+    env = BatchedEnv(n, seed_base=12345, device=DEV)
+    env.reset()
+    out = torch.zeros(3, dtype=torch.int64, device=DEV)
+    count = torch.zeros(n, dtype=torch.int32, device=DEV)
+    legal = torch.zeros((), dtype=torch.int64, device=DEV)
+    plies = 0
+    while not bool(env.done().all()):
+        assert plies < 200
+        st = env.export_state()
+        nat.check(nat.lib().hz_key_check(nat.ptr(st), n, nat.ptr(out), nat.stream_ptr(st.device)), "hz_key_check")
+        env.rule_ply(count=count)  # (the legal counts of the states just checked; 0 for a finished board)
+        legal += count.sum()
+        plies += 1
+    pairs, mismatch, step_fail = out.tolist()
+    assert plies > 40 and pairs == int(legal) and pairs > 20 * n
+    assert mismatch == 0 and step_fail == 0
+    env.close()
+

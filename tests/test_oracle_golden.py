@@ -185,3 +185,44 @@ def test_replay_actions_matches_reference_traces():
     noisy[0, :] = 142
     total2, finals2, rej2 = oracle.replay_actions(seeds.astype(np.uint64), noisy)
     assert total2 == total and (rej2 == 1).all() and (finals2 == finals).all()
+
+
+def test_play_rule_from_continues_rule_games():
+    """or_play_rule_from from a reset state, and from a state part of the way
+    through the game, ends where or_play_rule_games ends: final state, ply
+    count and next stream word (no stuck board occurs in play from a reset)."""
+    n, base = 24, 321
+    _, finals, plies, nxt = oracle.play_rule_games(n, base, nthreads=2)
+    for b in range(n):
+        m = oracle.mt_seed(base + b)
+        st = oracle.reset(m)
+        mid, k, stuck = oracle.play_rule_from(st, m, base + b, 0, 3 + 2 * b)
+        assert k == 3 + 2 * b and not stuck
+        fin, k2, stuck = oracle.play_rule_from(mid, m, base + b, k, 1 << 20)
+        assert not stuck and k + k2 == plies[b], b
+        assert (fin == finals[b]).all() and oracle.is_game_over(fin), b
+        assert oracle.mt_next32(m) == nxt[b], b
+        again, k3, stuck = oracle.play_rule_from(fin, m, base + b, plies[b], 50)  # a finished game: nothing to do
+        assert k3 == 0 and not stuck and (again == fin).all()
+
+
+def test_stuck_board_is_left_alone():
+    """A stuck board (no legal move, game not over; oracle.stuck_state) packs
+    and unpacks like any state; or_play_rule_from stops on it at once, as
+    or_play_rule_auto's loop does: no step, the stuck flag, state and stream
+    untouched; or_mcts_search gives no move: -1, no visits, the root alone."""
+    from conftest import PKG  # noqa: F401  (puts hzamd on the path)
+    from hzamd.state import pack_ref, unpack_ref
+    for seed in (7, 4242, 1 << 33):
+        st, m = oracle.stuck_state(seed)
+        words, idx = m.words()
+        assert oracle.legal(st).sum() == 0 and not oracle.is_game_over(st)
+        assert (unpack_ref(pack_ref(st)) == st).all()
+        for plies in (1, 200):
+            fin, steps, stuck = oracle.play_rule_from(st, m, seed, 1, plies)
+            assert steps == 0 and stuck and (fin == st).all()
+        a, visits, nn, ne = oracle.mcts_search(st, m, 24, 2.0, testing=True)
+        assert a == -1 and visits.sum() == 0 and (nn, ne) == (1, 0)
+        w2, i2 = m.words()
+        assert (w2 == words).all() and i2 == idx
+

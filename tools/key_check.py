@@ -1,11 +1,10 @@
-"""canon_key_child == canon_key over whole games (tools/key_check.hip).
+"""canon_key_child == canon_key over whole games (libhz.so's hz_key_check).
 
 Plays 4096 boards from reset to the end with the build's action rule and,
 at every ply, checks the child key of every legal action of every board in
 both key forms.  Prints one JSON line: pairs checked, mismatches.
-    make -C tools libkeycheck.so && python tools/key_check.py
+    python tools/key_check.py
 """
-import ctypes
 import json
 import os
 import sys
@@ -14,11 +13,12 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "harmonies-alphazero_amd"))
+from hzamd import _native as nat  # noqa: E402
 from hzamd.env import BatchedEnv  # noqa: E402
 
 
 def main():
-    lib = ctypes.CDLL(os.path.join(ROOT, "tools", "libkeycheck.so"))
+    lib = nat.lib()
     n = int(os.environ.get("HZ_KC_BOARDS", "4096"))
     env = BatchedEnv(n, seed_base=12345)
     env.reset()
@@ -26,9 +26,7 @@ def main():
     plies = 0
     while not bool(env.done().all()):
         st = env.export_state().contiguous()
-        torch.cuda.synchronize()
-        if lib.hz_key_check(ctypes.c_void_p(st.data_ptr()), n, ctypes.c_void_p(out.data_ptr())):
-            raise SystemExit("hz_key_check failed")
+        nat.check(lib.hz_key_check(nat.ptr(st), n, nat.ptr(out), nat.stream_ptr(st.device)), "hz_key_check")
         env.rule_ply()
         plies += 1
     torch.cuda.synchronize()
