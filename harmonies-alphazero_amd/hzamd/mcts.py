@@ -404,17 +404,22 @@ class BatchedPredictor:
         return torch.softmax(logits.float(), dim=1), value.float().reshape(-1)
 
 
-def stub_evaluator(board, glob):
-    """Deterministic integer-valued evaluator used by the parity tests; the
-    same formula as tests/golden/make_golden.py:stub_predict_np, so the GPU
-    search and the reference search see identical priors and values."""
+def _stub_key(board, glob):
+    """The integer key K both stub evaluators hash (int64 [k])."""
     n0 = torch.round(board[:, 0:18].double().sum((1, 2, 3))).long()
     n1 = torch.round(board[:, 18:36].double().sum((1, 2, 3))).long()
     cp = torch.round(board[:, 36].amax((1, 2))).long()
     ph3 = torch.round(board[:, 37].amax((1, 2)) * 3.0).long()
     pc = torch.round(glob[:, 0:36].double() * 3.0).long()
     w = (pc * torch.arange(1, 37, device=board.device, dtype=torch.int64)).sum(1)
-    K = (n0 * 73 + n1 * 151 + ph3 * 7 + cp * 3 + w * 13) % (1 << 31)
+    return (n0 * 73 + n1 * 151 + ph3 * 7 + cp * 3 + w * 13) % (1 << 31)
+
+
+def stub_evaluator(board, glob):
+    """Deterministic integer-valued evaluator used by the parity tests; the
+    same formula as tests/golden/make_golden.py:stub_predict_np, so the GPU
+    search and the reference search see identical priors and values."""
+    K = _stub_key(board, glob)
     a = torch.arange(ACTION_SIZE, device=board.device, dtype=torch.int64)
     h = (a.unsqueeze(0) * 2654435761 + K.unsqueeze(1) * 40503) % (1 << 32)
     pol = ((h >> 22) + 1).to(torch.float32) / 1024.0
@@ -423,3 +428,33 @@ def stub_evaluator(board, glob):
 
 
 stub_evaluator.row_independent = True  # a function of each row alone
+
+
+def dense_stub_evaluator(board, glob):
+    """The second parity evaluator (tests/golden/make_golden.py:
+    dense_stub_predict_np): where the stub's priors are k/1024 and its values
+    k/128, so that the search arithmetic is exact in any precision, these
+    priors have full 24-bit significands over twenty binades, in ladders of
+    three actions one fp32 ulp apart, one triple in 32 exactly zero, and the
+    values are signed 24-bit integers times 2^-23, three in four of them
+    within eight ulps of +-1.  Integers converted and
+    scaled by powers of two only: the same bits in NumPy, C and torch."""
+    K = _stub_key(board, glob)
+    a = torch.arange(ACTION_SIZE, device=board.device, dtype=torch.int64)
+    r = a % 3
+    hg = ((a - r).unsqueeze(0) * 2654435761 + K.unsqueeze(1) * 40503) % (1 << 32)
+    low = hg & 31
+    mant = (1 << 23) + ((hg >> 9) & ~3) + r.unsqueeze(0)
+    # 2^-(24+s) from its fp32 bit pattern (exponent field 127 - 24 - s): device
+    # integer ops only, so the evaluator can be captured in a HIP graph
+    scale = ((103 - low % 20) << 23).to(torch.int32).view(torch.float32)
+    pol = mant.to(torch.float32) * scale
+    pol = torch.where(low == 31, torch.zeros_like(pol), pol)
+    hv = (K * 2246822519) % (1 << 32)
+    j = (hv >> 4) & 7
+    sat = torch.where((hv & 8) != 0, j - (1 << 23), (1 << 23) - 1 - j)
+    vi = torch.where((hv & 7) < 6, sat, (hv >> 8) - (1 << 23))
+    return pol, vi.to(torch.float32) * (2.0 ** -23)
+
+
+dense_stub_evaluator.row_independent = True

@@ -29,7 +29,8 @@ class MT(ctypes.Structure):
 class MctsCfg(ctypes.Structure):
     _fields_ = [("sims", ctypes.c_int32), ("cpuct", ctypes.c_float), ("eps", ctypes.c_double),
                 ("testing", ctypes.c_int32), ("tau0", ctypes.c_int32), ("ply", ctypes.c_int32),
-                ("u", ctypes.c_double), ("exact_keys", ctypes.c_int32), ("negate_value", ctypes.c_int32)]
+                ("u", ctypes.c_double), ("exact_keys", ctypes.c_int32), ("negate_value", ctypes.c_int32),
+                ("evaluator", ctypes.c_int32), ("variant", ctypes.c_int32)]
 
 
 def build():
@@ -78,7 +79,10 @@ def lib():
         L.or_mcts_search.argtypes = [ctypes.c_void_p, P(MT), P(MctsCfg), ctypes.c_void_p,
                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.or_mcts_search.restype = ctypes.c_int
+        L.or_mcts_search_ex.argtypes = L.or_mcts_search.argtypes
+        L.or_mcts_search_ex.restype = ctypes.c_int
         L.or_stub_eval.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.or_dense_stub_eval.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         _lib = L
     return _lib
 
@@ -235,15 +239,18 @@ def replay_actions(seeds, actions, nthreads=0):
 
 
 def mcts_search(st, m, sims, cpuct, eps=0.25, testing=True, tau0=15, ply=0, u=0.0, noise=None,
-                exact_keys=False, negate_value=False):
+                exact_keys=False, negate_value=False, evaluator=0, variant=0):
+    """evaluator: 0 the stub, 1 the dense stub.  variant (tests only): a bit
+    mask of deliberately wrong precisions (hz_oracle.h OR_VARIANT_*), used to
+    show that a fixture tells them from the reference's arithmetic."""
     st = np.ascontiguousarray(st, np.int16)
     cfg = MctsCfg(sims, cpuct, eps, int(bool(testing)), tau0, ply, u, int(bool(exact_keys)),
-                  int(bool(negate_value)))
+                  int(bool(negate_value)), int(evaluator), int(variant))
     nz = np.zeros(143, np.float64) if noise is None else np.ascontiguousarray(noise, np.float64)
     visits = np.zeros(143, np.int32)
     nn = ctypes.c_int32(0)
     ne = ctypes.c_int32(0)
-    a = lib().or_mcts_search(_p(st), ctypes.byref(m), ctypes.byref(cfg), _p(nz), _p(visits),
+    a = lib().or_mcts_search_ex(_p(st), ctypes.byref(m), ctypes.byref(cfg), _p(nz), _p(visits),
                              ctypes.byref(nn), ctypes.byref(ne))
     return a, visits, nn.value, ne.value
 
@@ -253,4 +260,12 @@ def stub_eval(st):
     pol = np.zeros(143, np.float32)
     val = ctypes.c_double(0)
     lib().or_stub_eval(_p(st), _p(pol), ctypes.byref(val))
+    return pol, val.value
+
+
+def dense_stub_eval(st):
+    st = np.ascontiguousarray(st, np.int16)
+    pol = np.zeros(143, np.float32)
+    val = ctypes.c_double(0)
+    lib().or_dense_stub_eval(_p(st), _p(pol), ctypes.byref(val))
     return pol, val.value

@@ -76,6 +76,15 @@ int main(void) {
       h = mix(h, (uint64_t)(a + 7 * nn + 11 * ne));
       for (int i = 0; i < 143; i++) h = mix(h, (uint64_t)visits[i]);
     }
+    if (ply % 18 == 9) { /* the dense stub, and a search under it, the test-only variant masks 0..7 in turn */
+      or_dense_stub_eval(st, pol, &v);
+      for (int i = 0; i < 143; i++) h = mix(h, (uint64_t)(int64_t)(pol[i] * 16777216.0f));
+      or_mcts_cfg cfg = {24, 1.1f, 0.3, 0, 10, ply, 0.5, 0, 0, 1, (ply / 18) % 8};
+      memcpy(&g, &m, sizeof g);
+      const int a = or_mcts_search_ex(st, &g, &cfg, noise, visits, &nn, &ne);
+      h = mix(h, (uint64_t)(a + 7 * nn + 11 * ne) + (uint64_t)(int64_t)(v * 8388608.0));
+      for (int i = 0; i < 143; i++) h = mix(h, (uint64_t)visits[i]);
+    }
     int a = -1, k = (int)(or_rule(777, (uint64_t)ply) >> 32) % (L > 0 ? L : 1);
     for (int i = 0; i < 143 && a < 0; i++)
       if (mask[i] && k-- == 0) a = i;

@@ -12,6 +12,7 @@
  * Pinned by the .npz fixtures under tests/golden/ captured from the reference itself
  * (tests/golden/make_golden.py); see tests/test_oracle_golden.py.
  */
+#include <stddef.h>
 #include "hz_oracle.h"
 
 #include <math.h>
@@ -807,7 +808,7 @@ static int tree_add(otree *t, const ostate *s) {
 
 static int st_game_over(const ostate *s) { return s->game_over && s->winner != -2; }
 
-void or_stub_eval(const int16_t *st, float *policy, double *value) {
+static int64_t stub_key(const int16_t *st) {
   ostate s;
   from_ref(st, &s);
   int64_t n0 = 0, n1 = 0;
@@ -827,7 +828,11 @@ void or_stub_eval(const int16_t *st, float *policy, double *value) {
     for (int j = 0; j < s.nhand; j++) if (s.hand[j] == t) cnt++;
     w += (int64_t)cnt * (30 + t + 1);
   }
-  int64_t K = (n0 * 73 + n1 * 151 + ph3 * 7 + cp * 3 + w * 13) % (1LL << 31);
+  return (n0 * 73 + n1 * 151 + ph3 * 7 + cp * 3 + w * 13) % (1LL << 31);
+}
+
+void or_stub_eval(const int16_t *st, float *policy, double *value) {
+  int64_t K = stub_key(st);
   for (int a = 0; a < 143; a++) {
     uint64_t h = ((uint64_t)a * 2654435761ULL + (uint64_t)K * 40503ULL) % (1ULL << 32);
     policy[a] = (float)((h >> 22) + 1) / 1024.0f;
@@ -835,14 +840,33 @@ void or_stub_eval(const int16_t *st, float *policy, double *value) {
   *value = (double)((K % 255) - 127) / 128.0;
 }
 
-static void stub_eval_state(const ostate *s, float *policy, double *value) {
-  int16_t v[78];
-  to_ref(s, v);
-  or_stub_eval(v, policy, value);
+void or_dense_stub_eval(const int16_t *st, float *policy, double *value) {
+  int64_t K = stub_key(st);
+  for (int a = 0; a < 143; a++) {
+    int r = a % 3;
+    uint32_t hg = (uint32_t)((uint64_t)(a - r) * 2654435761ULL + (uint64_t)K * 40503ULL);
+    int low = (int)(hg & 31u);
+    uint32_t mant = (1u << 23) + ((hg >> 9) & ~3u) + (uint32_t)r;
+    policy[a] = low == 31 ? 0.0f : ldexpf((float)mant, -(24 + low % 20)); /* both exact */
+  }
+  uint32_t hv = (uint32_t)((uint64_t)K * 2246822519ULL);
+  int32_t vi = (int32_t)(hv >> 8) - (1 << 23);
+  if ((hv & 7u) < 6u) { /* three keys in four: within eight ulps of +-1, as a tanh head in a decided position */
+    int32_t j = (int32_t)((hv >> 4) & 7u);
+    vi = (hv & 8u) ? -(1 << 23) + j : (1 << 23) - 1 - j;
+  }
+  *value = (double)ldexpf((float)vi, -23);
 }
 
-int or_mcts_search(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg, const double *noise,
-                   int32_t *visits, int32_t *n_nodes, int32_t *n_edges) {
+static void stub_eval_state(const ostate *s, int evaluator, float *policy, double *value) {
+  int16_t v[78];
+  to_ref(s, v);
+  if (evaluator == 1) or_dense_stub_eval(v, policy, value);
+  else or_stub_eval(v, policy, value);
+}
+
+static int mcts_search(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg, const double *noise,
+                       int32_t *visits, int32_t *n_nodes, int32_t *n_edges) {
   geom_init();
   otree t;
   t.cap_n = 1024; t.nodes = malloc(sizeof(onode) * t.cap_n); t.nn = 0;
@@ -871,6 +895,7 @@ int or_mcts_search(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg, co
         if (!mask[ed->action]) continue;
         float cp = cfg->cpuct * ed->P;                       /* float32 * float32 */
         double u = (double)cp * sqrt_ns / (double)(1 + ed->N);
+        if (cfg->variant & OR_VARIANT_CPUCT_F64) u = (double)cfg->cpuct * (double)ed->P * sqrt_ns / (double)(1 + ed->N);
         double qu = ed->Q + u;
         if (qu > best) { best = qu; sel = t.nodes[node].e0 + e; }
       }
@@ -882,7 +907,7 @@ int or_mcts_search(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg, co
     const ostate *ls = &t.nodes[node].s;
     int leaf_player = ls->player;
     if (!st_game_over(ls)) {
-      stub_eval_state(ls, pol, &value);
+      stub_eval_state(ls, cfg->evaluator, pol, &value);
       if (cfg->negate_value) value = -value;
       if (node == 0 && !cfg->testing) {                    /* MCTS.py:308-327 */
         int L = legal_of(ls, mask);
@@ -890,9 +915,10 @@ int or_mcts_search(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg, co
         int i = 0;
         for (int a = 0; a < 143 && L; a++) {
           if (!mask[a]) continue;
-          float a32 = one_m_eps * pol[a];
+          float pol_in = pol[a], a32 = one_m_eps * pol_in;
           double b64 = cfg->eps * noise[i++];
           pol[a] = (float)((double)a32 + b64);
+          if (cfg->variant & OR_VARIANT_MIX_F64) pol[a] = (float)((double)one_m_eps * (double)pol_in + b64);
         }
       }
       /* expand_leaf (MCTS.py:151-218) */
@@ -928,6 +954,7 @@ int or_mcts_search(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg, co
       double dir = ed->player == leaf_player ? 1.0 : -1.0;
       ed->N += 1;
       ed->W += value * dir;
+      if (cfg->variant & OR_VARIANT_W_F32) ed->W = (double)(float)ed->W;
       ed->Q = ed->W / (double)ed->N;
     }
   }
@@ -966,6 +993,22 @@ int or_mcts_search(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg, co
   if (n_edges) *n_edges = t.ne;
   free(t.nodes); free(t.edges); free(t.hslot);
   return best;
+}
+
+/* The entry point older callers were built against: it reads the fields up to
+ * negate_value only (a caller's struct may end there), the stub and the
+ * reference's arithmetic.  or_mcts_search_ex reads the whole struct. */
+int or_mcts_search(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg, const double *noise,
+                   int32_t *visits, int32_t *n_nodes, int32_t *n_edges) {
+  or_mcts_cfg c;
+  memset(&c, 0, sizeof c);
+  memcpy(&c, cfg, offsetof(or_mcts_cfg, evaluator));
+  return mcts_search(root_ref, m, &c, noise, visits, n_nodes, n_edges);
+}
+
+int or_mcts_search_ex(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg, const double *noise,
+                      int32_t *visits, int32_t *n_nodes, int32_t *n_edges) {
+  return mcts_search(root_ref, m, cfg, noise, visits, n_nodes, n_edges);
 }
 
 /* ---------------------------------------------------------- greedy agent

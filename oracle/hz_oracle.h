@@ -82,13 +82,32 @@ typedef struct {
   double  u;            /* uniform for tau=1 sampling */
   int32_t exact_keys;   /* 0: key nodes like hash(state) (reference); 1: exact canonical */
   int32_t negate_value; /* 1: the stub's value negated (a second, different evaluator) */
+  int32_t evaluator;    /* 0: the stub (or_stub_eval); 1: the dense stub (or_dense_stub_eval) */
+  int32_t variant;      /* TEST ONLY, 0 = the reference's arithmetic.  Each bit swaps one step
+                           for a plausible wrong precision, to show that a fixture tells them
+                           apart: 1 cpuct * P formed in double; 2 the root mix's
+                           (1 - eps) * P formed in double; 4 W accumulated in fp32 */
 } or_mcts_cfg;
 
+#define OR_VARIANT_CPUCT_F64 1
+#define OR_VARIANT_MIX_F64   2
+#define OR_VARIANT_W_F32     4
+
+/* or_mcts_search reads cfg up to negate_value only (evaluator = variant = 0):
+ * a caller built against the struct that ended there keeps working.
+ * or_mcts_search_ex reads every field. */
 int or_mcts_search(const int16_t *root, or_mt *m, const or_mcts_cfg *cfg, const double *noise,
                    int32_t *visits143, int32_t *n_nodes, int32_t *n_edges);
+int or_mcts_search_ex(const int16_t *root, or_mt *m, const or_mcts_cfg *cfg, const double *noise,
+                      int32_t *visits143, int32_t *n_nodes, int32_t *n_edges);
 
 /* Stub evaluator (integer formula over the encoder's inputs). */
 void or_stub_eval(const int16_t *st, float *policy143, double *value);
+/* Dense stub (same key K): priors mant * 2^-(24+s) with a full 24-bit mant and
+ * s in 0..19, in ladders of three actions one fp32 ulp apart, one triple in 32
+ * exactly zero, not normalised; value a signed 24-bit integer times 2^-23,
+ * for three keys in four within eight ulps of +-1. */
+void or_dense_stub_eval(const int16_t *st, float *policy143, double *value);
 
 #ifdef __cplusplus
 }

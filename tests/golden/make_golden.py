@@ -30,9 +30,17 @@ Fixtures (all int arrays unless noted; REFSTATE = 78 x int16, see `ref_state`):
                      action index) move order and a deterministic stub
                      evaluator; testing=True and testing=False (noise/choice
                      injected through patched numpy calls).
+  mcts_dense.npz     the same capture under the dense stub (priors with full
+                     24-bit significands one ulp apart, zeros, twenty binades;
+                     24-bit values) with cpuct in {1.1, 0.3, 3.7, 2} and eps
+                     in {0.3, 0.25, 0}: here the precision of every step of
+                     the search arithmetic decides edges.  Positions are read
+                     from the committed env_traces.npz; `numpy_version` names
+                     the NumPy whose scalar promotion the capture ran under.
 
 Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py [part ...]
-        (parts: mt env encoder scoring mcts greedy train; default all)
+        (parts: mt env encoder scoring mcts mcts_dense greedy train; default
+        all but mcts_dense, which only adds its own file)
 """
 import logging
 import os
@@ -271,7 +279,7 @@ def capture_scoring(he, sorted_coords, idx_of):
 
 # ---- MCTS -------------------------------------------------------------------
 
-def stub_predict_np(board, glob):
+def stub_predict_np(board, glob, dense=False):
     """Deterministic stub evaluator; integer arithmetic only so that a torch
     restatement on the GPU produces bit-identical priors/values."""
     b = np.asarray(board, np.float32)
@@ -283,6 +291,8 @@ def stub_predict_np(board, glob):
     pc = np.rint(gl[0:36].astype(np.float64) * 3.0).astype(np.int64)
     w = int((pc * np.arange(1, 37, dtype=np.int64)).sum())
     K = (n0 * 73 + n1 * 151 + ph3 * 7 + cp * 3 + w * 13) % (1 << 31)
+    if dense:
+        return dense_from_key(K)
     a = np.arange(143, dtype=np.int64)
     h = (a * 2654435761 + K * 40503) % (1 << 32)
     pol = ((h >> 22) + 1).astype(np.float32) / np.float32(1024.0)
@@ -290,12 +300,96 @@ def stub_predict_np(board, glob):
     return pol, val
 
 
+def dense_from_key(K):
+    """Dense stub: priors with a full 24-bit significand spread over twenty
+    binades, in ladders of three actions one fp32 ulp apart (3g, 3g+1, 3g+2
+    share the exponent and the mantissa's upper bits), one triple in 32 exactly
+    zero, not normalised; the value a signed 24-bit integer times 2^-23, for
+    three keys in four within eight ulps of +-1 (a tanh head's output in a
+    decided position: W then passes 2, where fp32 no longer holds a sum of
+    them, after three visits).  Every conversion below is exact, so NumPy, C
+    and torch give the same bits."""
+    a = np.arange(143, dtype=np.int64)
+    r = a % 3
+    hg = ((a - r) * 2654435761 + K * 40503) % (1 << 32)
+    low = hg & 31
+    mant = (1 << 23) + ((hg >> 9) & ~np.int64(3)) + r
+    pol = np.ldexp(mant.astype(np.float32), -(24 + low % 20).astype(np.int32)).astype(np.float32)
+    pol[low == 31] = np.float32(0.0)
+    hv = (K * 2246822519) % (1 << 32)
+    vi = (hv >> 8) - (1 << 23)
+    if (hv & 7) < 6:
+        j = (hv >> 4) & 7
+        vi = -(1 << 23) + j if hv & 8 else (1 << 23) - 1 - j
+    return pol, float(np.float32(vi) * np.float32(2.0 ** -23))
+
+
+def dense_stub_predict_np(board, glob):
+    return stub_predict_np(board, glob, dense=True)
+
+
 class StubManager:
     def predict(self, board, glob):
         return stub_predict_np(board.numpy(), glob.numpy())
 
 
+class DenseStubManager:
+    def predict(self, board, glob):
+        return dense_stub_predict_np(board.numpy(), glob.numpy())
+
+
 def capture_mcts(he, pgs, mcts_mod, states, sorted_coords, idx_of):
+    rng = np.random.RandomState(3)
+    # positions: states from the traces, biased to include late-game ones
+    n = len(states)
+    idx = list(rng.choice(n, 56, replace=False))
+    late = [i for i in range(n) if states[i][73] != 4 and (23 - (states[i][0:23] > 0).sum()) <= 4]
+    idx += list(rng.choice(late, 24, replace=False))
+    specs = [dict(testing=(k % 3) != 2, sims=[32, 8, 64, 200][k % 4] if k < 76 else 400,
+                  cpuct=[2, 1.0, 2, 1.5][k % 4], eps=0.25 if k % 6 != 5 else 0,
+                  tau0=15 if k % 5 else 0) for k in range(len(idx))]
+    out = run_mcts_rows(he, pgs, mcts_mod, [states[si] for si in idx], specs, sorted_coords, StubManager())
+    np.savez_compressed(os.path.join(OUT, "mcts.npz"), **out)
+
+
+# Rows 24..47 of mcts_dense.npz: env_traces.npz positions at which, under the
+# row's settings, one of the C oracle's wrong-precision variants
+# (oracle/hz_oracle.h OR_VARIANT_*) gives other root visits than its reference
+# arithmetic.  Found with the oracle alone (a scan of the traces from
+# (167 * row) % n in steps of 37 for the first such position); what the
+# fixture then stores for them is the reference's own search, like every row.
+# tests/test_oracle_golden.py asserts that each variant changes some row.
+DENSE_PICKED = [193, 175, 342, 805, 713, 1024, 1750, 1362, 1344, 1511, 1937, 2696,
+                2049, 2253, 2457, 2846, 2754, 2177, 13, 3329, 3422, 3552, 3978, 774]
+
+
+def capture_mcts_dense(he, pgs, mcts_mod, sorted_coords):
+    """mcts_dense.npz: capture_mcts with the dense stub, cpuct and eps values
+    whose fp32 form is inexact, positions read from the committed
+    env_traces.npz (the other fixtures are not rewritten).  The injected
+    Dirichlet vector is constant over runs of six legal moves, so that the
+    root's mixed priors keep their one-ulp ladders (with a different noise
+    value per move no two root priors come near each other, and the rounding
+    of (1 - eps) * P could not decide an edge)."""
+    states = np.load(os.path.join(OUT, "env_traces.npz"))["states"]
+    rng = np.random.RandomState(5)
+    n = len(states)
+    idx = list(rng.choice(n, 16, replace=False))
+    late = [i for i in range(n) if states[i][73] != 4 and (23 - (states[i][0:23] > 0).sum()) <= 4]
+    idx += list(rng.choice(late, 8, replace=False))
+    idx += DENSE_PICKED
+    assert len(idx) == 48 and all(states[i][73] != 4 for i in DENSE_PICKED)
+    # twelve settings, four rows each (a batched search takes one setting)
+    specs = [dict(testing=k % 12 in (1, 6, 8, 11), sims=[16, 64, 200][k % 3],
+                  cpuct=[1.1, 0.3, 3.7, 2][k % 4], eps=[0.3, 0.25, 0][k % 12 // 4],
+                  tau0=15 if k % 5 else 0) for k in range(len(idx))]
+    out = run_mcts_rows(he, pgs, mcts_mod, [states[si] for si in idx], specs, sorted_coords, DenseStubManager(),
+                        noise_run=6)
+    out["numpy_version"] = np.array(np.__version__)
+    np.savez_compressed(os.path.join(OUT, "mcts_dense.npz"), **out)
+
+
+def run_mcts_rows(he, pgs, mcts_mod, positions, specs, sorted_coords, manager, noise_run=1):
     orig = he.HarmoniesGameState.get_legal_moves
     he.HarmoniesGameState.get_legal_moves = lambda self: sorted(orig(self), key=pgs.get_action_index)
     last = {}
@@ -306,30 +400,21 @@ def capture_mcts(he, pgs, mcts_mod, states, sorted_coords, idx_of):
         last["tree"] = self
     mcts_mod.MCTS.__init__ = init
 
-    rng = np.random.RandomState(3)
-    # positions: states from the traces, biased to include late-game ones
-    n = len(states)
-    idx = list(rng.choice(n, 56, replace=False))
-    late = [i for i in range(n) if states[i][73] != 4 and (23 - (states[i][0:23] > 0).sum()) <= 4]
-    idx += list(rng.choice(late, 24, replace=False))
     rows = []
-    for k, si in enumerate(idx):
-        v = states[si]
-        testing = (k % 3) != 2
-        sims = [32, 8, 64, 200][k % 4] if k < 76 else 400
-        cpuct = [2, 1.0, 2, 1.5][k % 4]
+    for k, (v, spec) in enumerate(zip(positions, specs)):
+        testing, sims, cpuct = spec["testing"], spec["sims"], spec["cpuct"]
         mt_seed = 5000 + k
         noise = np.zeros(143, np.float64)
         u = ((k * 0.6180339887498949) % 1.0)
         cfg = {"num_simulations": sims, "cpuct": cpuct, "dirichlet_alpha": 0.4,
-               "dirichlet_epsilon": 0.25 if k % 6 != 5 else 0, "fpu_value": 0.25,
-               "turns_until_tau0": 15 if k % 5 else 0, "action_size": 143, "testing": testing}
+               "dirichlet_epsilon": spec["eps"], "fpu_value": 0.25,
+               "turns_until_tau0": spec["tau0"], "action_size": 143, "testing": testing}
         ply = k % 30
         choice_used = [False]
 
         def fake_dirichlet(alpha):
             L = len(alpha)
-            raw = np.array([((j * 7 + k * 3) % 11 + 1) for j in range(L)], np.float64)
+            raw = np.array([((j // noise_run * 7 + k * 3) % 11 + 1) for j in range(L)], np.float64)
             vec = raw / raw.sum()
             noise[:L] = vec
             return vec
@@ -348,7 +433,7 @@ def capture_mcts(he, pgs, mcts_mod, states, sorted_coords, idx_of):
         try:
             g = state_from_ref(he, v, sorted_coords)
             random.seed(mt_seed)
-            mv, pi = mcts_mod.get_best_action_and_pi(g, StubManager(), cfg, ply)
+            mv, pi = mcts_mod.get_best_action_and_pi(g, manager, cfg, ply)
             nxt = random.getrandbits(32)
         finally:
             np.random.dirichlet, np.random.choice = saved
@@ -366,8 +451,7 @@ def capture_mcts(he, pgs, mcts_mod, states, sorted_coords, idx_of):
                          n_nodes=len(tree.tree), n_edges=n_edges, sampled=int(choice_used[0])))
     he.HarmoniesGameState.get_legal_moves = orig
     mcts_mod.MCTS.__init__ = orig_init
-    out = {key: np.array([r[key] for r in rows]) for key in rows[0]}
-    np.savez_compressed(os.path.join(OUT, "mcts.npz"), **out)
+    return {key: np.array([r[key] for r in rows]) for key in rows[0]}
 
 
 def capture_greedy(he, pgs, idx_of, seeds=range(5000, 5032)):
@@ -446,6 +530,8 @@ def main():
             capture_encoder(he, pgs, states, sorted_coords, idx_of)
         if "mcts" in parts:
             capture_mcts(he, pgs, mcts_mod, states, sorted_coords, idx_of)
+    if "mcts_dense" in parts:
+        capture_mcts_dense(he, pgs, mcts_mod, sorted_coords)
     if "scoring" in parts:
         capture_scoring(he, sorted_coords, idx_of)
     if "greedy" in parts:

@@ -68,6 +68,127 @@ def test_mcts_matches_reference_fixtures():
     assert checked == len(f["sims"])
 
 
+class _DenseRows:
+    """The dense stub on the device-row protocol (no host read per
+    simulation; PyTorch device ops only, so a simulation can be captured)."""
+    device_rows = True
+    capturable = True
+    row_independent = True
+
+    def __call__(self, board, glob, rows=None, count=None):
+        from hzamd.mcts import dense_stub_evaluator
+        return dense_stub_evaluator(board, glob)
+
+
+# search() forms: (copies of each fixture row in the batch, settings)
+DENSE_FORMS = {
+    "small_batch": (1, {}),                                      # <= 32 boards: select + gather + encode in one launch
+    "full_batch": (1, {"gather": False}),                       # k_select, one evaluator row per board
+    "separate": (9, {"fuse_select": False}),                    # > 32 boards: k_select launches of their own
+    "fused_select": (9, {"fuse_gather": False}),                # select inside the expand / backup launch
+    "fused_select_gather": (9, {}),                             # ... with the next gather + encode too (the default)
+    "graph": (1, {"graph": True}),                              # simulations 2.. one replayed HIP graph
+}
+
+
+@pytest.mark.parametrize("form", list(DENSE_FORMS))
+def test_mcts_dense_matches_reference_fixtures(form):
+    """mcts_dense.npz (the reference's own searches under the dense stub: full
+    24-bit priors one ulp apart, zero priors, twenty binades, 24-bit values,
+    cpuct 1.1 / 0.3 / 3.7 / 2, eps 0.3 / 0.25 / 0) through every form of
+    search() that instantiates select_board or the expansion separately:
+    visits, chosen action, node and edge counts and the next MT word, bit for
+    bit.  Here the fp32 cpuct * P, the fp32 (1 - eps) * P widened before the
+    fp64 add, and the fp64 W decide edges
+    (test_oracle_golden.test_mcts_dense_fixture_tells_precisions_apart)."""
+    from hzamd.mcts import BatchedMCTS, choose_actions, dense_stub_evaluator
+    copies, opts = DENSE_FORMS[form]
+    opts = dict(opts)
+    f = load("mcts_dense.npz")
+    groups = defaultdict(list)
+    for k in range(len(f["sims"])):
+        groups[(int(f["sims"][k]), float(f["cpuct"][k]), int(f["testing"][k]), float(f["eps"][k]))].append(k)
+    assert len(groups) == 12
+    fuse_select, fuse_gather = opts.pop("fuse_select", True), opts.pop("fuse_gather", True)
+    ev = _DenseRows() if opts.get("graph") else dense_stub_evaluator
+    checked = 0
+    for (sims, cpuct, testing, eps), rows in groups.items():
+        ks = rows * copies
+        assert (len(ks) > 32) == (copies > 1)
+        env = make_env(f["state"][ks], f["mt_seed"][ks])
+        mcts = BatchedMCTS(env, sims)
+        mcts.fuse_select, mcts.fuse_gather = fuse_select, fuse_gather
+        noise = torch.from_numpy(np.ascontiguousarray(f["noise"][ks][:, :69]))
+        visits = mcts.search(ev, cpuct, noise=noise, eps=eps, testing=bool(testing), **opts)
+        explore = torch.tensor([(not testing) and f["ply"][k] < f["tau0"][k] for k in ks])
+        u = torch.tensor([f["u"][k] for k in ks], dtype=torch.float64)
+        act = choose_actions(visits.cpu(), explore, u).numpy()
+        counts = mcts.stats().cpu().numpy()
+        v = visits.cpu().numpy()
+        _, mt, mti = env.export_state(with_mt=True)
+        mt = mt.cpu().numpy().view(np.uint32)
+        mti = mti.cpu().numpy()
+        for j, k in enumerate(ks):
+            assert (v[j] == f["visits"][k]).all(), (k, v[j][v[j] > 0], f["visits"][k][f["visits"][k] > 0])
+            assert act[j] == f["action"][k], k
+            assert counts[j, 0] == f["n_nodes"][k] and counts[j, 1] == f["n_edges"][k], k
+            assert counts[j, 3] == 0
+            m = oracle.mt_from_words(mt[j], mti[j])
+            assert oracle.mt_next32(m) == f["next_word"][k], k
+            checked += 1
+        mcts.close()
+        env.close()
+    assert checked == len(f["sims"]) * copies
+
+
+@pytest.mark.parametrize("sims", [1, 2, 3, 32])
+def test_mcts_dense_512_boards_selfplay_config_vs_oracle(sims):
+    """512 boards spread over the game, self-play settings with inexact fp32
+    factors (cpuct 1.1, eps 0.3, testing off, NoiseSource's Dirichlet rows),
+    dense stub: every board's visits, tree sizes and next MT word vs the C
+    oracle's search under the same evaluator.  32 simulations, and the
+    smallest searches (the root's noisy expansion alone, then the first
+    select steps below it)."""
+    from hzamd.env import BatchedEnv
+    from hzamd.mcts import BatchedMCTS, dense_stub_evaluator
+    from hzamd.selfplay import NoiseSource
+    n, base, cpuct, eps = 512, 7300 + sims, 1.1, 0.3
+    env = BatchedEnv(n, seed_base=base, device=DEV)
+    env.reset()
+    plies = torch.arange(n, device=DEV) % 61
+    for p in range(61):
+        mask, count = env.legal_mask()
+        act = env.rule_actions(mask, count)
+        env.step(torch.where(plies > p, act, torch.full_like(act, -1)))
+    st0, mt0, idx0 = env.export_state(with_mt=True)
+    st0, mt0, idx0 = st0.cpu().numpy(), mt0.cpu().numpy().view(np.uint32), idx0.cpu().numpy()
+    active = ~env.done()
+    _, count = env.legal_mask()
+    noise, _ = NoiseSource(base, DEV).draw(3, count, 0.4)
+    mcts = BatchedMCTS(env, sims)
+    visits = mcts.search(dense_stub_evaluator, cpuct, active=active, noise=noise, eps=eps, testing=False)
+    visits = visits.cpu().numpy()
+    counts = mcts.stats().cpu().numpy()
+    _, mt1, idx1 = env.export_state(with_mt=True)
+    mt1, idx1 = mt1.cpu().numpy().view(np.uint32), idx1.cpu().numpy()
+    act_np, nz = active.cpu().numpy(), noise.cpu().numpy()
+    assert act_np.sum() > 400
+    for b in range(n):
+        if not act_np[b]:
+            assert visits[b].sum() == 0
+            continue
+        m = oracle.mt_from_words(mt0[b], idx0[b])
+        # tau0 = 0: the move is the first most-visited edge, so the oracle's stream holds the search's
+        # draws alone (sampling a move from one simulation's all-zero visits would draw a random one)
+        _, ov, nn, ne = oracle.mcts_search(unpack_ref(st0[:, b]), m, sims, cpuct, eps=eps, testing=False, tau0=0,
+                                           noise=np.concatenate([nz[b], np.zeros(143 - 69)]), evaluator=1)
+        assert (visits[b] == ov).all(), b
+        assert (counts[b, 0], counts[b, 1]) == (nn, ne), b
+        assert oracle.mt_next32(oracle.mt_from_words(mt1[b], idx1[b])) == oracle.mt_next32(m), b
+    mcts.close()
+    env.close()
+
+
 def test_mcts_4096_boards_vs_oracle():
     """Full batch: 4096 boards at assorted game positions, 24 simulations,
     testing mode, stub evaluator; every board is searched by the C oracle."""

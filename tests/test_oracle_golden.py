@@ -111,6 +111,111 @@ def test_mcts_matches_reference(k):
     assert oracle.mt_next32(m) == f["next_word"][k]
 
 
+def dense_row(f, k, variant=0):
+    """Row k of mcts_dense.npz searched by the oracle under the dense stub:
+    (action, visits, nodes, edges, next MT word)."""
+    m = oracle.mt_seed(int(f["mt_seed"][k]))
+    a, visits, nn, ne = oracle.mcts_search(
+        f["state"][k], m, int(f["sims"][k]), float(f["cpuct"][k]), eps=float(f["eps"][k]),
+        testing=bool(f["testing"][k]), tau0=int(f["tau0"][k]), ply=int(f["ply"][k]),
+        u=float(f["u"][k]), noise=f["noise"][k], evaluator=1, variant=variant)
+    return a, visits, nn, ne, oracle.mt_next32(m)
+
+
+@pytest.mark.parametrize("k", range(48))
+def test_mcts_dense_matches_reference(k):
+    """The reference's search under the dense stub (mcts_dense.npz: priors with
+    full 24-bit significands one ulp apart, zero priors, twenty binades,
+    24-bit values, cpuct 1.1 / 0.3 / 3.7 / 2, eps 0.3 / 0.25 / 0), where the
+    precision of each arithmetic step decides edges."""
+    f = load("mcts_dense.npz")
+    assert len(f["sims"]) == 48
+    a, visits, nn, ne, nxt = dense_row(f, k)
+    assert (visits == f["visits"][k]).all()
+    assert a == f["action"][k]
+    assert (nn, ne) == (f["n_nodes"][k], f["n_edges"][k])
+    assert nxt == f["next_word"][k]
+
+
+def test_mcts_dense_fixture_tells_precisions_apart():
+    """Each wrong-precision variant of the oracle (hz_oracle.h OR_VARIANT_*),
+    alone, gives other root visits than the reference on some row of
+    mcts_dense.npz, so a kernel or oracle that took that precision would fail
+    the fixture.  Rows changed, of 48 (NumPy 2.2.6 capture):
+      bit 0, cpuct * P formed in double:              15
+      bit 1, the root mix's (1 - eps) * P in double:  13  (of the 24 rows with
+             testing false and eps > 0; on every other row it cannot act)
+      bit 2, W accumulated in fp32:                    4
+    The rows cycle sims over 16 / 64 / 200, cpuct over 1.1 / 0.3 / 3.7 / 2 and
+    eps over 0.3 / 0.25 / 0, with testing and tau0 mixed: twelve settings,
+    four rows each."""
+    f = load("mcts_dense.npz")
+    n = len(f["sims"])
+    assert {int(s) for s in f["sims"]} == {16, 64, 200}
+    assert {float(c) for c in f["cpuct"]} == {1.1, 0.3, 3.7, 2.0}
+    assert {float(e) for e in f["eps"]} == {0.3, 0.25, 0.0}
+    assert {int(t) for t in f["testing"]} == {0, 1} and {int(t) for t in f["tau0"]} == {0, 15}
+    assert int(str(f["numpy_version"]).split(".")[0]) >= 2  # python_float * np.float32 -> float32
+    changed = {1: [], 2: [], 4: []}
+    for k in range(n):
+        for bit in changed:
+            if not (dense_row(f, k, variant=bit)[1] == f["visits"][k]).all():
+                changed[bit].append(k)
+    can_mix = [k for k in range(n) if not f["testing"][k] and f["eps"][k] > 0]
+    assert set(changed[2]) <= set(can_mix)
+    assert len(changed[1]) >= 1 and len(changed[2]) >= 1 and len(changed[4]) >= 1, changed
+    print({bit: len(rows) for bit, rows in changed.items()}, "can_mix", len(can_mix))
+
+
+def test_mcts_variant_zero_is_the_default():
+    """evaluator / variant default to 0: a caller that names neither (the
+    mcts.npz test above, bench.py) gets the stub and the reference's
+    arithmetic, and naming them as 0 changes nothing."""
+    f = load("mcts.npz")
+    for k in (0, 5, 17):
+        args = (f["state"][k], int(f["sims"][k]), float(f["cpuct"][k]))
+        kw = dict(eps=float(f["eps"][k]), testing=bool(f["testing"][k]), noise=f["noise"][k])
+        seed = int(f["mt_seed"][k])
+        r0 = oracle.mcts_search(args[0], oracle.mt_seed(seed), *args[1:], **kw)
+        r1 = oracle.mcts_search(args[0], oracle.mt_seed(seed), *args[1:], evaluator=0, variant=0, **kw)
+        assert (r0[1] == r1[1]).all() and r0[2:] == r1[2:] and (r0[1] == f["visits"][k]).all()
+
+
+def test_mcts_search_reads_no_further_than_the_nine_field_cfg():
+    """or_mcts_search keeps the interface it had before or_mcts_cfg grew its
+    trailing evaluator / variant fields: a caller whose struct ends at
+    negate_value (here followed by set bits where the new fields would lie)
+    gets the stub and the reference's arithmetic; or_mcts_search_ex reads the
+    same bytes as evaluator and variant and so searches otherwise."""
+    import ctypes
+
+    class Cfg9(ctypes.Structure):
+        _fields_ = oracle.MctsCfg._fields_[:9]
+
+    class Padded(ctypes.Structure):
+        _fields_ = [("cfg", Cfg9), ("after", ctypes.c_int32 * 2)]
+
+    assert ctypes.sizeof(Cfg9) == oracle.MctsCfg.evaluator.offset
+    f = load("mcts.npz")
+    for k in (0, 5, 17):
+        st = np.ascontiguousarray(f["state"][k], np.int16)
+        nz = np.ascontiguousarray(f["noise"][k], np.float64)
+        pad = Padded(Cfg9(int(f["sims"][k]), float(f["cpuct"][k]), float(f["eps"][k]), int(f["testing"][k]),
+                          int(f["tau0"][k]), int(f["ply"][k]), float(f["u"][k]), 0, 0), (ctypes.c_int32 * 2)(1, 7))
+        out = []
+        for fn in (oracle.lib().or_mcts_search, oracle.lib().or_mcts_search_ex):
+            m = oracle.mt_seed(int(f["mt_seed"][k]))
+            visits = np.zeros(143, np.int32)
+            nn, ne = ctypes.c_int32(0), ctypes.c_int32(0)
+            a = fn(oracle._p(st), ctypes.byref(m), ctypes.cast(ctypes.byref(pad), ctypes.POINTER(oracle.MctsCfg)),
+                   oracle._p(nz), oracle._p(visits), ctypes.byref(nn), ctypes.byref(ne))
+            out.append((a, visits, nn.value, ne.value))
+        a, visits, nn, ne = out[0]
+        assert (visits == f["visits"][k]).all() and a == f["action"][k]
+        assert (nn, ne) == (f["n_nodes"][k], f["n_edges"][k])
+        assert not (out[1][1] == visits).all()  # the dense stub with every variant on
+
+
 def test_greedy_games_match_reference():
     """evaluation.choose_move_greedy games (greedy.npz): every state, every
     chosen action, the final state and the next CPython word — the greedy

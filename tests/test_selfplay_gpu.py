@@ -14,10 +14,11 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def replay(rec, sp, n, base, sims, cpuct, testing, tau0):
-    """Replays every board's game with the oracle; returns the expected z of
-    every record in SelfPlay.compact's order (trainer.py:517-527: the final
-    outcome from the recorded player's perspective, 0 for a draw)."""
+def replay(rec, sp, n, base, sims, cpuct, testing, tau0, eps=0.25, evaluator=0):
+    """Replays every board's game with the oracle (evaluator 0: the stub, 1:
+    the dense stub); returns the expected z of every record in
+    SelfPlay.compact's order (trainer.py:517-527: the final outcome from the
+    recorded player's perspective, 0 for a draw)."""
     states = rec["states"].cpu().numpy()
     visits = rec["visits"].cpu().numpy()
     valid = rec["valid"].cpu().numpy()
@@ -32,8 +33,8 @@ def replay(rec, sp, n, base, sims, cpuct, testing, tau0):
             assert valid[ply, b]
             assert (unpack_ref(states[ply, :, b]) == s).all(), (b, ply)
             noise, u, act = (t.cpu().numpy() for t in log[ply])
-            a, ov, _, _ = oracle.mcts_search(s, m, sims, cpuct, testing=testing, tau0=tau0, ply=ply,
-                                             u=float(u[b]), noise=noise[b])
+            a, ov, _, _ = oracle.mcts_search(s, m, sims, cpuct, eps=eps, testing=testing, tau0=tau0, ply=ply,
+                                             u=float(u[b]), noise=noise[b], evaluator=evaluator)
             assert (visits[ply, b] == ov).all(), (b, ply)
             assert a == act[b], (b, ply)
             r, s = oracle.step(s, a, m)
@@ -165,6 +166,12 @@ def test_selfplay_steady_matches_oracle_replay(testing):
     sp = SelfPlay(n, stub_evaluator, cfg, seed_base=base, device=DEV)
     sp.keep_noise = True
     rec = sp.play_steady(M)
+    check_steady(rec, sp, n, base, sims, cpuct, testing, tau0, M)
+
+
+def check_steady(rec, sp, n, base, sims, cpuct, testing, tau0, M, eps=0.25, evaluator=0):
+    """play_steady's record replayed by the oracle, then compact_steady's
+    examples (test_selfplay_steady_matches_oracle_replay)."""
     states, visits = rec["states"].cpu().numpy(), rec["visits"].cpu().numpy()
     game, ended = rec["game"].cpu().numpy(), rec["ended"].cpu().numpy()
     outc = rec["outcome"].cpu().numpy()
@@ -179,8 +186,8 @@ def test_selfplay_steady_matches_oracle_replay(testing):
         for mv in range(M):
             assert game[mv, b] == k and (unpack_ref(states[mv, :, b]) == s).all(), (b, mv)
             noise, u, act = log[mv]
-            a, ov, _, _ = oracle.mcts_search(s, m, sims, cpuct, testing=testing, tau0=tau0, ply=ply,
-                                             u=float(u[b]), noise=noise[b])
+            a, ov, _, _ = oracle.mcts_search(s, m, sims, cpuct, eps=eps, testing=testing, tau0=tau0, ply=ply,
+                                             u=float(u[b]), noise=noise[b], evaluator=evaluator)
             assert (visits[mv, b] == ov).all() and a == act[b], (b, mv)
             players.append((mv, int(s[72])))
             r, s = oracle.step(s, a, m)
@@ -206,3 +213,33 @@ def test_selfplay_steady_matches_oracle_replay(testing):
     assert np.array_equal(comp["z"].cpu().numpy(), np.array([z_want[k] for k in order], np.float32))
     assert np.array_equal(comp["board"].cpu().numpy(), np.array([b for _, b in order]))
     assert sorted(comp["lengths"].cpu().tolist()) == sorted(lengths)
+
+
+@pytest.mark.parametrize("steady", [False, True])
+def test_selfplay_dense_stub_matches_oracle_replay(steady):
+    """test_selfplay_matches_oracle_replay's and
+    test_selfplay_steady_matches_oracle_replay's replays under the dense stub
+    (full 24-bit priors one ulp apart, zero priors, 24-bit values) with
+    factors that are inexact in fp32 (cpuct 1.1, dirichlet_epsilon 0.3):
+    16 boards, 6 simulations, root noise on; every state, visit vector and
+    move, compact's z and the pi targets."""
+    from hzamd.mcts import dense_stub_evaluator
+    from hzamd.selfplay import SelfPlay
+    n, base, sims, cpuct, eps, tau0, M = 16, 5600, 6, 1.1, 0.3, 15, 150
+    cfg = {"num_simulations": sims, "cpuct": cpuct, "testing": False, "turns_until_tau0": tau0,
+           "dirichlet_epsilon": eps}
+    sp = SelfPlay(n, dense_stub_evaluator, cfg, seed_base=base, device=DEV)
+    sp.keep_noise = True
+    if steady:
+        rec = sp.play_steady(M)
+        check_steady(rec, sp, n, base, sims, cpuct, False, tau0, M, eps=eps, evaluator=1)
+        return
+    rec = sp.play()
+    z_want = replay(rec, sp, n, base, sims, cpuct, False, tau0, eps=eps, evaluator=1)
+    comp = sp.compact(rec)
+    assert comp["states"].shape[0] == int(rec["valid"].sum())
+    assert np.array_equal(comp["z"].cpu().numpy(), z_want)
+    assert (z_want != 0).any()
+    assert torch.allclose(comp["pi"].sum(1), torch.ones(comp["pi"].shape[0], device=comp["pi"].device))
+    v = comp["visits"].cpu().numpy().astype(np.float64)     # pi = N / sum(N) in float64, stored as float32
+    assert np.array_equal(comp["pi"].cpu().numpy(), (v / v.sum(1, keepdims=True)).astype(np.float32))
