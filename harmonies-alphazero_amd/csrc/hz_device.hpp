@@ -521,7 +521,8 @@ struct LdsMT {
   }
 
   // start the next generation now and twist its first `target` words
-  // (k_seed_ahead: a typical game then never twists)
+  // (seed_in_lds, the stages that prepare an episode: a typical game then
+  // never twists)
   __device__ __forceinline__ void twist_ahead(int target) {
     if (pos >= kMT) { pos = 0; tw = 0; }
     while (tw < target) tw += twist_block(w(), kLdsStride, tw);
@@ -676,82 +677,6 @@ __device__ __forceinline__ void mt_seed_tab(uint32_t *w, const uint32_t *tab, ui
   }
   w[1 * S] = (first1 ^ ((prev ^ (prev >> 30)) * 1566083941U)) - 1U;
   w[0] = 0x80000000U;
-}
-
-// init_by_array (random.seed) split at its pass boundary, the stream word-
-// major in global memory (word i of the board at w[i * ns]), so that the
-// chain's wave issues no LDS operation (hz_play's second pipeline, hz_env.hip
-// "pipeline 2"): pass 1 leaves mt[1] (the 624th iteration's value) and
-// mt[2..623] as pass 2 reads them; pass 2 finishes the array (cursor
-// kMTSeeded).  The two together write exactly mt_seed's words.
-__device__ __forceinline__ void mt_seed_pass1_g(uint32_t* __restrict__ w, size_t ns, uint64_t seed) {
-  const uint32_t key0 = (uint32_t)seed, key1 = (uint32_t)(seed >> 32);
-  const uint32_t kA = key0, kB = key1 ? key1 + 1u : key0;
-  uint32_t prev = 19650218u, m1 = 0;
-  for (int g = 1; g < kMT - 7; g += 8) {  // i = 1..616
-    uint32_t iv[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) iv[u] = kInitGen.v[g + u];
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      const uint32_t v = (iv[u] ^ ((prev ^ (prev >> 30)) * 1664525U)) + ((u & 1) ? kB : kA);
-      if (u || g > 1) w[(size_t)(g + u) * ns] = v;
-      else m1 = v;
-      prev = v;
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < 7; u++) {  // i = 617..623
-    const uint32_t v = (kInitGen.v[617 + u] ^ ((prev ^ (prev >> 30)) * 1664525U)) + ((u & 1) ? kB : kA);
-    w[(size_t)(617 + u) * ns] = v;
-    prev = v;
-  }
-  // mt[0] = mt[623]; the 624th iteration at i = 1 (key j = 623 % keylen -> kB)
-  w[ns] = (m1 ^ ((prev ^ (prev >> 30)) * 1664525U)) + kB;
-}
-template <int PF = 16>
-__device__ __forceinline__ void mt_seed_pass2_g(uint32_t* __restrict__ w, size_t ns) {
-  const uint32_t first1 = w[ns];
-  uint32_t prev = first1;
-  uint32_t ring[PF];  // pass-1 words PF iterations ahead
-#pragma unroll
-  for (int u = 0; u < PF; u++) ring[u] = w[(size_t)(2 + u) * ns];
-  constexpr int kFull = 2 + ((kMT - 2) / PF) * PF;
-  for (int g = 2; g < kFull; g += PF) {
-#pragma unroll
-    for (int u = 0; u < PF; u++) {
-      const uint32_t cur = ring[u];
-      const int nx = g + PF + u;
-      ring[u] = nx < kMT ? w[(size_t)nx * ns] : 0u;
-      const uint32_t v = (cur ^ ((prev ^ (prev >> 30)) * 1566083941U)) - (uint32_t)(g + u);
-      w[(size_t)(g + u) * ns] = v;
-      prev = v;
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < (kMT - 2) % PF; u++) {
-    const uint32_t v = (ring[u] ^ ((prev ^ (prev >> 30)) * 1566083941U)) - (uint32_t)(kFull + u);
-    w[(size_t)(kFull + u) * ns] = v;
-    prev = v;
-  }
-  w[ns] = (first1 ^ ((prev ^ (prev >> 30)) * 1566083941U)) - 1U;
-  w[0] = 0x80000000U;
-}
-// rows [0, rows) of a seeded stream (rows <= 227: every source still old)
-// twisted in place, the next generation's start: the stream afterwards has
-// cursor 0 | rows << 16 (kMTAhead for rows = kAheadTwist)
-__device__ __forceinline__ void mt_pretwist_g(uint32_t* __restrict__ w, size_t ns, int rows) {
-  constexpr int B = 8;
-  for (int i0 = 0; i0 < rows; i0 += B) {
-    uint32_t cur[B + 1], far[B];
-#pragma unroll
-    for (int j = 0; j <= B; j++) cur[j] = w[(size_t)(i0 + j) * ns];
-#pragma unroll
-    for (int j = 0; j < B; j++) far[j] = w[(size_t)(i0 + j + 397) * ns];
-#pragma unroll
-    for (int j = 0; j < B; j++)
-      if (i0 + j < rows) w[(size_t)(i0 + j) * ns] = twist_word(cur[j], cur[j + 1], far[j]);
-  }
 }
 
 // A board's stream in global memory with a runtime word stride (a pipeline-2
@@ -935,8 +860,8 @@ __device__ __forceinline__ void sample3_raw(LdsMT& m, uint32_t n, int k, uint32_
   if (got < k) sample3_serial(m, n, k, j, got);  // window exhausted (rare)
 }
 
-// A window of a pre-twisted stream in LDS: rows [0, lim) only (hz_env.hip's
-// pipeline-2 draw stages, a window per wave side by side).  Reads never
+// A window of a pre-twisted stream in LDS: rows [0, lim) only (hz_play2.hpp's
+// draw stages, a window per wave side by side).  Reads never
 // twist, and the caller discards any draw whose cursor ends past lim (its
 // picks depend only on the words it consumed, all below the cursor).  The
 // scan reads rows up to pos + 23, in bounds while pos <= lim (rows the

@@ -1,0 +1,1007 @@
+// hz_play2.hpp — k_play2, hz_play's second pipeline, and the kernel that
+// copies a board's stream out of its slots.  Part of hz_env.hip's translation
+// unit (included by it alone, after hz_chance.hpp and hz_rollout.hpp; P2Draw,
+// P2Mid and the kP2* stage counts sit with struct hz_env, which is sized by
+// them).
+#pragma once
+
+namespace {
+
+// ============================================================= pipeline 2
+// hz_play's second pipeline (hz_env_set_pipeline(e, 2)).  Each of
+// k_rollout's roles runs one serial per-board chain of ~60 k cycles (a whole
+// game, a whole seeding, 16 pile draws), and a launch lasts as long as its
+// longest chain.  Here every board's episode is cut into fourteen stages of
+// about 20 k cycles, one per consecutive hz_play call, and one launch runs
+// all fourteen at once, each on a different episode of the board (ep = the
+// episode counter the previous call left, p2_ep; stage s works on episode
+// ep + 13 - s).  The wave of each stage outside the seed and play blocks is
+// kP2Wave's (HZ_P2_WAVES); by default:
+//   s = 0  P1    seeding pass 1, all 624 steps, in     draw-Y blocks, wave 2
+//                registers: only its last word leaves
+//   s = 1  P2a   pass 2, steps 2-208                  seed blocks, wave 0
+//   s = 2  P2b   pass 2, steps 209-432                seed blocks, wave 1
+//   s = 3  P2c   pass 2, steps 433-624; rows 0-223    seed blocks, wave 2
+//                of the next generation twisted       (twist: wave 3)
+//   s = 4  D1    pile draws [dcut0 = 0, dcut1)        draw-X blocks, wave 0
+//   s = 5  D2    draws [dcut1, dcut2)                 draw-X blocks, wave 1
+//   s = 6  D3    draws [dcut2, dcut3)                 draw-Y blocks, wave 0
+//   s = 7  D4    draws [dcut3, dcut4)                 draw-Y blocks, wave 1
+//   s = 8  D5    draws [dcut4, 24)                    draw-X blocks, wave 2
+//          (the episode's rule hashes meanwhile:      draw-X blocks, wave 3)
+//   s = 9  playA plies [0, cut0)                      draw-Y blocks, wave 3
+//   s = 10 playB plies [cut0, cut1)                   play blocks, wave 3
+//   s = 11 playC plies [cut1, cut2)                   play blocks, wave 2
+//   s = 12 playD plies [cut2, cut3)                   play blocks, wave 1
+//   s = 13 playE the rest, final scoring, the board's play blocks, wave 0
+//                state, cursor and counters
+// Pass 1 never reaches memory: a pass-1 word is a function of the board's key
+// and the constant kInitGen table, so P1 hands on only what pass 2's last
+// step needs (row 1's word after the 624th step), and each pass-2 stage
+// recomputes pass 1 over its own rows next to its pass-2 chain (a second,
+// independent recurrence of four VALU operations per step), started from
+// pass 1's word at the row before its range: one step from the constants for
+// P2a, handed on with pass 2's value for P2b and P2c.
+// An episode's stream lives in one slot of a ring of kP2Stream from P2a to
+// playE (and afterwards as the board's current stream until materialize or
+// the next call); stage s >= 1 of call c uses slot (c - s) mod kP2Stream.  A
+// stage uses an input only when its tag names the stage's episode, so a wrong
+// prediction costs time, never results: the stages skip the board and playE
+// plays its whole game from scratch (seeding and drawing in LDS, like
+// k_rollout's unprepared boards).  The results are k_rollout's: the board ends
+// the call with episode ep's final state, cursor and counters, and
+// games_done / steps_done count that game (its first plies ran in the four
+// calls before, in playA to playD).  In steady state a call does every stage
+// once per board: one game's worth of work per board per call.
+#ifndef HZ_P2_ST_WT
+// 1: the hand-off stores (hashes, cursors, scripts, mid-game states) write-
+// through too (global_store ... sc1): 17.0 G against 18.3 G with them plain
+// (profiles/r05/p2_writethrough), so plain by default
+#define HZ_P2_ST_WT 0
+#endif
+#ifndef HZ_P2_AUX
+// cache policy of the seeding stages' and the twist's stream-slot stores
+// (~24 MB per 4096-board launch): 16 = sc1, write-through, the line dropped
+// from the XCD's L2 (the next call's stages read them, from the MALL), so
+// the kernel's end finds no dirty slot lines to write back: 14.1 vs 15.8 us
+// per launch against plain stores (0), 15.5 with nt (2)
+// (profiles/r05/p2_writethrough; A/B builds -DHZ_P2_AUX=0 / 2)
+#define HZ_P2_AUX 16
+#endif
+constexpr int kP2Win = 96;        // rows a draw stage stages, from its wave's lowest cursor
+constexpr int kP2WinRows = kP2Win + 24;  // LDS rows per window (a scan reads up to 23 rows past its cursor)
+#ifndef HZ_P2_DCUT
+// the draw stages' first draws (run time: HZ_P2_DCUTS).  Later draws take
+// longer, so the early stages take more of them: with four stages of six, D3
+// ran 13.8 us against D1's 10.5, and the cuts became 0, 7, 13, 18
+// (profiles/r05/p2_dcut); five stages: profiles/r07, and profiles/r09 since
+// the first stage loads its window in its first round trip and takes a sixth
+// draw from the last.
+#if HZ_P2_NDRAW == 5
+#define HZ_P2_DCUT 0, 6, 11, 15, 19
+#elif HZ_P2_NDRAW == 4
+#define HZ_P2_DCUT 0, 7, 13, 18
+#endif
+#endif
+constexpr int kP2DCut[kP2Draw] = {HZ_P2_DCUT};
+// A draw stage's window holds kP2Win rows from its wave's lowest cursor.
+// Seven draws (the most a stage ever had) use at most ~60 words (eight
+// consecutive draws: 67 over 20,000 seeds), which leaves room for the
+// spread of the wave's cursors; a stage of twenty overruns the window for
+// about one board in twenty, every time at the cost of the draws discarded.
+constexpr int kP2StageDraws = 7;
+#ifndef HZ_P2_PCUT
+// the play stages' ply boundaries (run time: HZ_P2_CUTS5; four stages:
+// HZ_P2_CUTS).  Multiples of 8: a stage that starts inside a turn pair plays
+// single plies up to the next pair, and every such setting measured slower
+// (profiles/r07/cuts_scan.json).
+#if HZ_P2_NPLAY == 5
+#define HZ_P2_PCUT 16, 32, 48, 64
+#elif HZ_P2_NPLAY == 4
+#define HZ_P2_PCUT 24, 40, 56
+#endif
+#endif
+constexpr int kP2PCut[kP2Play - 1] = {HZ_P2_PCUT};
+// what each wave of a draw-X (first four) and a draw-Y block runs: a draw
+// stage (0 .. kP2Draw - 1), P1, the rule hashes, play stage 0, or nothing.
+// (A play wave brings the ply loop's ~50 KB of code into its CU pair's
+// instruction cache next to the draw code.)
+enum { kWvP1 = 8, kWvHash = 9, kWvPlay = 10, kWvIdle = 15 };
+#ifndef HZ_P2_WAVES
+#if HZ_P2_NDRAW == 5 && HZ_P2_NPLAY == 5
+#define HZ_P2_WAVES 0, 1, 4, 9, 2, 3, 8, 10
+#elif HZ_P2_NDRAW == 5
+#define HZ_P2_WAVES 0, 1, 4, 9, 2, 3, 8, 15
+#elif HZ_P2_NPLAY == 5
+#define HZ_P2_WAVES 0, 1, 8, 9, 2, 3, 10, 15
+#else
+#define HZ_P2_WAVES 0, 1, 8, 9, 2, 3, 15, 15
+#endif
+#endif
+constexpr int kP2Wave[8] = {HZ_P2_WAVES};
+constexpr int p2_wave_count(int code) {
+  int c = 0;
+  for (int k = 0; k < 8; k++) c += kP2Wave[k] == code;
+  return c;
+}
+constexpr bool p2_waves_ok() {
+  for (int d = 0; d < 5; d++)
+    if (p2_wave_count(d) != (d < kP2Draw ? 1 : 0)) return false;
+  return p2_wave_count(kWvP1) == 1 && p2_wave_count(kWvHash) == 1 && p2_wave_count(kWvPlay) == (kP2Play == 5 ? 1 : 0);
+}
+static_assert(p2_waves_ok(), "HZ_P2_WAVES: every stage outside the seed and play blocks on exactly one wave");
+constexpr int kP2MinPlies = 96;   // hz_play max_plies from which pipeline 2 applies (rule games end by ply 80)
+#ifdef HZ_DIAG
+constexpr int kP2Stamps = 48;  // stamp slots per board in k_play2 (tools/p2_roles.py)
+#define P2_PHASE(slot, t0)                                                                                       \
+  do {                                                                                                           \
+    __builtin_amdgcn_sched_barrier(0);                                                                           \
+    if (g_stamps && b < a.n) g_stamps[(size_t)b * kP2Stamps + (slot)] = __builtin_amdgcn_s_memtime() - (t0); \
+    __builtin_amdgcn_sched_barrier(0);                                                                           \
+  } while (0)
+#else
+#define P2_PHASE(slot, t0) \
+  do {                     \
+  } while (0)
+#endif
+static_assert(4 * kP2WinRows * kWinStride * 4 <= (int)kResetLds, "a window per wave of a draw block");
+
+struct P2Args {
+  uint64_t *st;
+  uint32_t *mt;
+  int32_t *pos, *ply, *episode;
+  uint64_t *seed;
+  int n, max_plies, draws;
+  int cut[kP2Play - 1];
+  int dcut[kP2Draw + 1];      // draw stage k: draws [dcut[k], dcut[k + 1])
+  uint64_t seed_base;
+  long nrow;
+  int32_t *games_done, *steps_done, *mt_src;
+  int32_t *win_tag;           // [nrow] PlyWin's tags: the last play stage sets its board's to none
+  const int32_t *ep_in;
+  int32_t *ep_out;
+  uint32_t *s_mt[kP2Stages];  // the stream slot of each stage this call ([0], P1: none)
+  int32_t *s_tag[kP2Stages];  // [nrow] episode * 8 + 3 P2a / 4 P2b / 5 seeded, rows 0-223 twisted
+  int32_t *s_cur[kP2Stages];  // [kAheadDraws + 1][nrow] cursor before draw 0 and after each draw
+  int s_idx_last;             // the last play stage's slot index (materialize: mt_src = 2 + index)
+  uint32_t *p1h_w;            // [nrow] P1 -> P2a: pass 1's row-1 word after its 624th step
+  const uint32_t *p1h_r;
+  int32_t *p1t_w;             // [nrow] its tag: episode * 8 + 2
+  const int32_t *p1t_r;
+  uint32_t *p2h_w;            // [4][nrow] P2a -> P2b: pass 2's last value, pass 1's row-1 word, row 2's final word,
+  const uint32_t *p2h_r;      //           pass 1's word of P2a's last row
+  uint32_t *p3h_w;            // [4][nrow] P2b -> P2c: the same
+  const uint32_t *p3h_r;
+  P2Draw x_w[kP2Draw - 1], x_r[kP2Draw - 1];  // D1 -> D2 -> ... (tag: episode * 8 + stages done)
+  P2Draw pl_w, pl_r[kP2Play];     // the last draw stage's script: written this call; read by play stage st (st + 1 calls later)
+  P2Mid m_w[kP2Play - 1], m_r[kP2Play - 1];  // play stage st -> st + 1 (written / read this call)
+  uint32_t *h_w;                  // [kRulePlies][nrow] rule hashes
+  const uint32_t *h_r[kP2Play];
+  int32_t *ht_w;                  // [nrow] their episode
+  const int32_t *ht_r[kP2Play];
+  int32_t *err;                   // the env's wait-error word
+  int spin;                       // spin bound of the twist wave's waits
+};
+
+// PlayDraw for the prepared stages: the pile script in registers, then (a
+// script shorter than the game needs) the episode's stream slot in HBM
+struct PlayDraw2 : PileScript {
+  bool fell;
+  MTR gm;                  // valid once fell
+  const int32_t *cur_nd;   // the slot's cursor after the last scripted draw (read when the script runs out)
+  __device__ __forceinline__ bool pair_pops() const { return d + 2 <= nd; }
+  __device__ __forceinline__ uint32_t draw_one(uint64_t misc) {
+    if (d < nd) return pop();
+    if (!fell) {
+      gm = MTR(gm.w, gm.stride, *cur_nd);
+      fell = true;
+    }
+    uint32_t p9;
+    return draw_pile(misc, gm, p9) ? p9 : 0x1FFu;
+  }
+  __device__ __forceinline__ uint32_t operator()(uint64_t misc) { return take(misc, true); }
+  __device__ __forceinline__ uint32_t take(uint64_t misc, bool want) {
+    if (__all(!want || d < nd)) return pop_if(want);
+    return want ? draw_one(misc) : 0x1FFu;
+  }
+};
+
+// the rule policy's plies [g, g_end) of one board (k_rollout's ply loop, no
+// reset, no recording): turn pairs while the wave allows, single plies
+// otherwise; hashes from a pipeline slot when `hs` (row stride nr) holds the
+// episode's, else computed.  Returns the plies played.
+template <class Draw>
+__device__ __forceinline__ int p2_plies(State &s, Draw &draw, int g, int g_end, uint64_t rkey, const uint32_t *hs,
+                                        size_t nr) {
+  const int g0 = g;
+  auto hash = [&](int ply) -> uint32_t { return hs && ply < kRulePlies ? hs[(size_t)ply * nr] : rule_h32(rkey, ply); };
+  // the next turn pair's hashes, read one pair ahead (a slot's are in HBM).
+  // Wave-uniform choices: a per-lane select would evaluate both sides, i.e.
+  // compute all eight hashes and issue their loads every pair.
+  const bool all_hs = __all(hs != nullptr);
+  uint32_t hn[8];
+  int hn_g = -1;  // (wave-uniform)
+  while (g < g_end) {
+    if (phase_of(s.misc) == PH_OVER) break;
+    if (__all(g + 8 <= g_end && turn_pair_safe(s))) {
+      uint32_t h[8];
+      if (__all(hn_g == g)) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) h[j] = hn[j];
+      } else if (all_hs && __all(g + 8 <= kRulePlies)) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) h[j] = hs[(size_t)(g + j) * nr];
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; j++) h[j] = hash(g + j);
+      }
+      if (all_hs && __all(g + 16 <= g_end && g + 16 <= kRulePlies)) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) hn[j] = hs[(size_t)(g + 8 + j) * nr];
+        hn_g = __builtin_amdgcn_readfirstlane(g + 8);
+      }
+      g += play_pair(s, draw, h);
+      continue;
+    }
+    const int a = rule_action(s, hash(g));
+    if (a < 0) break;  // stuck board (unreachable from HarmoniesGameState())
+    step_trusted<true>(s, a, draw);
+    g++;
+  }
+  return g - g0;
+}
+
+__device__ __forceinline__ int p2_wait(int *flag, int need, int limit, int32_t *err) {
+  int v = __hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+  // every publisher reaches kMT + 1 (or kMT rows); the bound only guards
+  // against a hang should that ever change, and giving up is reported (the
+  // caller goes on with rows that may not be final: the host raises)
+  for (int spin = 0; v < need && spin < limit; spin++) {
+    __builtin_amdgcn_s_sleep(1);
+    v = __hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  if (v < need) {
+    wait_failed(err, kWaitErrP2Twist);
+    v = kMT + 1;  // no further waits this launch
+  }
+  return v;
+}
+__device__ __forceinline__ void p2_publish(int *flag, int v) {
+  asm volatile("" ::: "memory");
+  __hip_atomic_store(flag, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// the slot's columns of boards [b0, b0 + 64) as a buffer (rows of nr words)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t p2_slot_rsrc(uint32_t *slot, int b0, size_t nr) {
+  const uint64_t base = (uint64_t)(slot + b0);
+  uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base), hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
+  const int bytes = __builtin_amdgcn_readfirstlane((int)((size_t)kMT * nr * 4 - (size_t)b0 * 4));
+  return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, bytes, 0x00020000);
+}
+#ifndef HZ_P2_LDNT
+#define HZ_P2_LDNT 0  // 1: the stages' 16-B slot reads (staging, windows, the twist's rows) non-temporal (A/B builds)
+#endif
+__device__ __forceinline__ uint4 p2_ld4(const uint32_t *p) {
+  if constexpr (HZ_P2_LDNT) {
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    const v4u v = __builtin_nontemporal_load((const v4u *)p);
+    return make_uint4(v[0], v[1], v[2], v[3]);
+  }
+  return *reinterpret_cast<const uint4 *>(p);
+}
+// a store read by another stage in a later call only: write-through (sc1)
+// like the slot stores (HZ_P2_AUX), so the kernel's end has no dirty lines
+// of it to write back
+template <class T>
+__device__ __forceinline__ void p2_st(T *p, T v) {
+  if constexpr (HZ_P2_AUX == 16 && HZ_P2_ST_WT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else *p = v;
+}
+// (the stream slots' stores: written by one stage, read by another in the
+// next call, never by this one: HZ_P2_AUX write-through (sc1) leaves no
+// dirty lines in the XCD's L2 for the end of the kernel to write back)
+// One step of init_by_array's pass 1 at row i: q is row i - 1's pass-1 word,
+// t kInitGen's word of row i; odd rows take key word kA, even ones kB.
+__device__ __forceinline__ uint32_t p1_step(uint32_t t, uint32_t q, bool odd, uint32_t kA, uint32_t kB) {
+  return (t ^ ((q ^ (q >> 30)) * 1664525U)) + (odd ? kA : kB);
+}
+// pass 1's row-1 word (its first step, from init_genrand's mt[0])
+__device__ __forceinline__ uint32_t p1_row1(uint32_t kA, uint32_t kB) {
+  return p1_step(kInitGen.v[1], 19650218u, true, kA, kB);
+}
+__device__ __forceinline__ void p2_keys(uint64_t seed, uint32_t &kA, uint32_t &kB) {
+  const uint32_t key0 = (uint32_t)seed, key1 = (uint32_t)(seed >> 32);
+  kA = key0;
+  kB = key1 ? key1 + 1u : key0;
+}
+
+// P1: all of init_by_array's pass 1 in registers (624 steps of four
+// dependent VALU operations).  No stream slot and no LDS: what leaves is row
+// 1's word after the 624th step (the only pass-1 word pass 2 cannot recompute
+// from a neighbour: it closes the ring) and the episode tag.
+// The wave is alone on its SIMD, so every instruction it issues, scalar ones
+// included, costs an issue slot: the loop is kept to the chain plus one
+// scalar load and one wait per eight steps.  The table words come a group of
+// eight ahead, in two register sets that alternate (a trip is sixteen steps),
+// so no set is copied; the padded table needs no clamp, so a group is one
+// s_load_dwordx8 from the loop's one table address.
+// The loads and their waits are written out: the compiler moves a plain
+// table read to wherever it likes (both groups' loads to the top of the trip,
+// or each next to its first use, where every group then waits a scalar-cache
+// round trip: 12 us for the stage instead of 8) and copies the words between
+// the sets.  Scalar loads return out of order, so a wait is for all that are
+// out: a group's wait comes before the next group's load is issued, behind
+// the eight steps that ran meanwhile.
+typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+// rows [1 + off / 4 + Imm / 4, + 8) of the table (tab: row 1's address)
+template <int Imm>
+__device__ __forceinline__ u32x8 p1_load8(const uint32_t *tab, uint32_t off) {
+  u32x8 t;
+  asm volatile("s_load_dwordx8 %0, %1, %2 offset:%3" : "=&s"(t) : "s"(tab), "s"(off), "n"(Imm));
+  return t;
+}
+__device__ __forceinline__ void p1_arrived(u32x8 &t) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(t)); }
+__device__ __forceinline__ uint32_t p1_steps8(const u32x8 &t, uint32_t prev, uint32_t kA, uint32_t kB) {
+#pragma unroll
+  for (int u = 0; u < 8; u++) prev = p1_step(t[u], prev, !(u & 1), kA, kB);  // (groups start at odd rows)
+  return prev;
+}
+__device__ __forceinline__ void p2_p1(const P2Args &a, int b) {
+  const int e = a.ep_in[b] + kP2Last;
+  uint32_t kA, kB;
+  p2_keys(episode_seed(a.seed_base, b, e), kA, kB);
+  uint32_t prev = 19650218u;
+  const uint32_t *tab = kInitGen.v + 1;
+  static_assert(38 * 16 + 1 == 609 && 617 + 8 <= kMT + kInitGenPad, "the last group's read (rows 617-624) within the table's padding");
+  u32x8 ta = p1_load8<0>(tab, 0), tb;
+  p1_arrived(ta);
+#pragma unroll 1
+  for (uint32_t off = 0; off < 38 * 64; off += 64) {  // steps 1..608, sixteen per trip
+    tb = p1_load8<32>(tab, off);
+    __builtin_amdgcn_sched_barrier(0);
+    prev = p1_steps8(ta, prev, kA, kB);
+    __builtin_amdgcn_sched_barrier(0);
+    p1_arrived(tb);
+    ta = p1_load8<64>(tab, off);
+    __builtin_amdgcn_sched_barrier(0);
+    prev = p1_steps8(tb, prev, kA, kB);
+    __builtin_amdgcn_sched_barrier(0);
+    p1_arrived(ta);
+  }
+  tb = p1_load8<0>(tab, (617 - 1) * 4);  // (its eighth word is padding)
+  prev = p1_steps8(ta, prev, kA, kB);  // steps 609..616
+  p1_arrived(tb);
+#pragma unroll
+  for (int u = 0; u < 7; u++) prev = p1_step(tb[u], prev, !(u & 1), kA, kB);  // steps 617..623
+  // mt[0] = mt[623]; the 624th step at i = 1 (key j = 623 % keylen -> kB)
+  a.p1h_w[b] = p1_step(p1_row1(kA, kB), prev, false, kA, kB);
+  a.p1t_w[b] = e * 8 + 2;
+}
+
+// Pass 2 in three stages, P2a (steps 2-208), P2b (209-432) and P2c
+// (433-623 and the last step at i = 1), in one seed block (three different
+// episodes).  Every step reads the row's pass-1 word.  The stages once read
+// them from the stream slot (staged into LDS first: an HBM round trip per
+// step is far too slow); now each recomputes pass 1 over its own rows, a
+// group of eight ahead of its pass-2 chain, so the two recurrences are
+// independent instruction streams and interleave.  Each final word goes to
+// the slot with a buffer store (the row offset a scalar: no address
+// arithmetic in the chain).  The chain is cut into thirds rather than made
+// cheaper per step.
+#ifndef HZ_P2_BEND
+// P2b's end (A/B builds: 225 + 8 k).  The twist follows P2c's progress and
+// ends ~1.5 us after it (its last stores' write-through), so P2c gets the
+// fewest rows: the rows r + 397 below this row the twist holds in registers
+// from the start (kTwHbm, P2b's of the call before, from HBM), the rest it
+// reads from P2c's LDS rows as they appear.
+#define HZ_P2_BEND 433
+#endif
+constexpr int kP2aEnd = 209, kP2bEnd = HZ_P2_BEND;
+static_assert(kP2bEnd > 399 && kP2bEnd + 64 < kMT && (kP2bEnd - kAheadTwist - 1) % 8 == 0, "P2b's final steps in groups of eight; rows 397, 398 P2b's");
+// pass 1 a group ahead of pass 2, at row g
+struct P2Ahead {
+  uint32_t cur[8];  // pass 1's words of rows [g, g + 8)
+  uint32_t iv[8];   // kInitGen's words of rows [g + 8, g + 16)
+  uint32_t last;    // pass 1's word of the last row pass 2 has consumed (the next stage starts from it)
+};
+// The table's address as a pass-2 stage holds it: in one scalar register
+// pair from the stage's start, its groups' loads at immediate offsets (the
+// compiler, knowing the address, makes it again from the program counter for
+// every group: three scalar instructions each).
+typedef __attribute__((address_space(4))) const uint32_t ConstWord;
+__device__ __forceinline__ ConstWord *p2_table() {
+  ConstWord *t = (ConstWord *)kInitGen.v;
+  asm volatile("" : "+s"(t));
+  return t;
+}
+// q: pass 1's word of row G - 1
+template <int G>
+__device__ __forceinline__ void p2_ahead_init(ConstWord *tab, P2Ahead &h, uint32_t q, uint32_t kA, uint32_t kB) {
+#pragma unroll
+  for (int u = 0; u < 8; u++) {
+    q = p1_step(tab[G + u], q, (G + u) & 1, kA, kB);
+    h.cur[u] = q;
+  }
+#pragma unroll
+  for (int u = 0; u < 8; u++) h.iv[u] = tab[G + 8 + u];
+  h.last = q;
+}
+// twist_word(cur, next, far) = far ^ twist_part(cur, next): the part of row
+// r's next-generation word that rows r and r + 1 decide.  Four operations:
+// the select of cur's top bit into next (v_bfi_b32), the shift, next's low
+// bit spread (v_bfe_i32), and "and, xor" in one v_bitop3_b32.  (The select
+// is written out: from every source form of it the compiler makes v_and_b32
+// and v_and_or_b32.)
+__device__ __forceinline__ uint32_t twist_part(uint32_t cur, uint32_t next) {
+  uint32_t y;  // (cur & 0x80000000) | (next & 0x7fffffff)
+  asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(y) : "s"(0x7fffffffU), "v"(next), "v"(cur));
+  return (y >> 1) ^ ((next & 1U) ? 0x9908b0dfU : 0U);
+}
+// What a pass-2 step stores: its final word to its row (kP2Final), the same
+// and to the row in LDS (kP2Keep, P2c), or the previous row's twist part
+// (kP2Part: rows 2-223, which only the twist reads)
+enum { kP2Final = 0, kP2Keep = 1, kP2Part = 2 };
+// A stage's store addresses, made once: the slot's buffer, the byte offsets
+// of the lane's column in eight consecutive rows (a store's voffset; the
+// group's first row is its scalar offset: one scalar instruction per group of
+// eight stores, none per store), and the lane's LDS byte address.
+typedef __attribute__((address_space(3))) uint32_t LdsWord;
+struct P2Out {
+  __amdgpu_buffer_rsrc_t rs;
+  int row_bytes;
+  int vo[8];
+  uint32_t lds;
+  __device__ __forceinline__ P2Out(__amdgpu_buffer_rsrc_t r, int rb, int lane) : rs(r), row_bytes(rb) {
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+      vo[u] = lane * 4 + u * rb;
+      asm volatile("" : "+v"(vo[u]));  // (kept: not made again at every store)
+    }
+    lds = (uint32_t)(uintptr_t)(LdsWord *)(hz_lds + lane);
+  }
+  // word v to column `lane` of row g + u (g wave-uniform, soff = g * row_bytes)
+  __device__ __forceinline__ void put(uint32_t v, int soff, int u) const {
+    __builtin_amdgcn_raw_buffer_store_b32(v, rs, vo[u], soff, HZ_P2_AUX);
+  }
+};
+// steps [G0, G1) of pass 2 (G1 - G0 a multiple of 8; h at row G0 on entry, at
+// G1 on return), while pass 1 runs over the next group's rows (past the
+// stage's last row its words are unused); stores to the slot as Mode says,
+// with kP2Keep publishing progress every 8 steps.  kP2Keep's LDS rows: one
+// address per group, the group's rows at immediate offsets.
+template <int G0, int G1, int Mode>
+__device__ __forceinline__ void p2_span(ConstWord *tab, const P2Out &o, uint32_t &prev, P2Ahead &h, uint32_t kA, uint32_t kB, int *prog) {
+  constexpr bool KeepLds = Mode == kP2Keep;
+  static_assert((G1 - G0) % 8 == 0, "groups of eight");
+  static_assert(G1 + 15 < kMT + kInitGenPad, "the table's read-ahead within its padding");
+  constexpr int S = kLdsStride;
+  uint32_t lg = o.lds + G0 * S * 4;
+#pragma unroll 2
+  for (int g = G0; g < G1; g += 8) {
+    uint32_t ivn[8], nx[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) ivn[u] = tab[g + 16 + u];
+    const uint32_t kneg = __builtin_amdgcn_readfirstlane(0u - (uint32_t)g);
+    const int soff = __builtin_amdgcn_readfirstlane((Mode == kP2Part ? g - 1 : g) * o.row_bytes);
+    if (KeepLds) asm volatile("" : "+v"(lg));  // (one register for the group, not an address per row)
+    uint32_t q = h.cur[7];
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+      // (cur ^ p) - (g + u) as one v_xad_u32 with the offset in an SGPR
+      const uint32_t p = (prev ^ (prev >> 30)) * 1566083941U;
+      uint32_t v;
+      asm("v_xad_u32 %0, %1, %2, %3" : "=v"(v) : "v"(p), "v"(h.cur[u]), "s"(kneg - (uint32_t)u));
+      o.put(Mode == kP2Part ? twist_part(prev, v) : v, soff, u);
+      if (KeepLds) *(LdsWord *)(uintptr_t)(lg + u * S * 4) = v;
+      prev = v;
+      // pass 1, row g + 8 + u (the parity of G0 + u: g - G0 is a multiple of 8)
+      q = p1_step(h.iv[u], q, (G0 + u) & 1, kA, kB);
+      nx[u] = q;
+    }
+    if (KeepLds) {
+      p2_publish(prog, g + 8);  // rows [G0, g + 8) final in LDS
+      lg += 8 * S * 4;
+    }
+    h.last = h.cur[7];
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+      h.cur[u] = nx[u];
+      h.iv[u] = ivn[u];
+    }
+  }
+}
+// the last steps [G, G1) one by one (fewer than eight: h holds their pass-1 words)
+template <int G, int G1, int Mode>
+__device__ __forceinline__ void p2_tail(const P2Out &o, int lane, uint32_t &prev, P2Ahead &h) {
+  static_assert(G1 - G >= 1 && G1 - G <= 8, "within the group ahead");
+  const int soff = __builtin_amdgcn_readfirstlane((Mode == kP2Part ? G - 1 : G) * o.row_bytes);
+#pragma unroll
+  for (int i = G; i < G1; i++) {
+    const uint32_t v = (h.cur[i - G] ^ ((prev ^ (prev >> 30)) * 1566083941U)) - (uint32_t)i;
+    o.put(Mode == kP2Part ? twist_part(prev, v) : v, soff, i - G);
+    if (Mode == kP2Keep) hz_lds[i * kLdsStride + lane] = v;
+    prev = v;
+  }
+  h.last = h.cur[G1 - G - 1];
+}
+
+// P2a (seed blocks, wave 0): the seed blocks' P2a episode, whose pass 1
+// completed in the previous call; P2b (wave 1) the next older; P2c (wave 2,
+// with wave 3's twist) the one before.  Each hands (prev, pass 1's row-1
+// word, row 2's final word, pass 1's word of its last row) to the next.
+// Rows 2-223 of the slot are read
+// only by the twist, which needs from each row r only its twist part
+// (rows r and r + 1's words): P2a and P2b store that instead of the final
+// word (one step late, when row r + 1 is known), so the twist is one xor
+// per word with the far row.  (e, ok: the board's episode and whether the
+// stage's input is this episode's, read by every wave of the block before
+// its barrier, so before P2c rewrites its tag.)
+template <int K>  // 0 P2a, 1 P2b, 2 P2c
+__device__ __forceinline__ void p2_third(const P2Args &a, int b0, int lane, int e, bool ok, int *s_prog) {
+  const int b = b0 + lane;
+  const bool act = b < a.n;
+  const size_t nr = (size_t)a.nrow;
+  // (P2a's slot is a fresh one: whatever tag an older episode left on it goes)
+  if (K == 0 && act && !ok) a.s_tag[1][b] = -1;
+  if (!__any(ok)) {
+    if (K == 2) p2_publish(s_prog, kMT + 1);  // (the twist wave's waits end: nothing to twist)
+    return;
+  }
+  uint32_t *slot = a.s_mt[1 + K];
+  uint32_t kA, kB;
+  p2_keys(episode_seed(a.seed_base, b, e), kA, kB);
+  uint32_t prev, first1, row2, q;
+  if (K == 0) {
+    first1 = act ? a.p1h_r[b] : 0u;
+    prev = first1;
+    q = p1_row1(kA, kB);
+  } else {
+    const uint32_t *h = K == 1 ? a.p2h_r : a.p3h_r;
+    prev = act ? h[b] : 0u;
+    first1 = act ? h[nr + b] : 0u;
+    row2 = act ? h[2 * nr + b] : 0u;
+    q = act ? h[3 * nr + b] : 0u;
+  }
+  const __amdgpu_buffer_rsrc_t rs = p2_slot_rsrc(slot, b0, nr);
+  const int row_bytes = __builtin_amdgcn_readfirstlane((int)(nr * 4));
+  const P2Out o(rs, row_bytes, lane);
+  ConstWord *tab = p2_table();
+  P2Ahead h;
+  if constexpr (K == 0) {  // step 2: row 2's final word, handed on (row 1's part needs row 1, P2c's last step)
+    q = p1_step(kInitGen.v[2], q, false, kA, kB);
+    row2 = (q ^ ((prev ^ (prev >> 30)) * 1566083941U)) - 2U;
+    prev = row2;
+    p2_ahead_init<3>(tab, h, q, kA, kB);
+    constexpr int G = 3 + 8 * ((kP2aEnd - 3) / 8);
+    p2_span<3, G, kP2Part>(tab, o, prev, h, kA, kB, s_prog);  // parts of rows 2 ..
+    p2_tail<G, kP2aEnd, kP2Part>(o, lane, prev, h);             // .. 207
+  } else if constexpr (K == 1) {
+    static_assert(kAheadTwist + 1 - kP2aEnd == 16, "P2b's part steps: two groups");
+    p2_ahead_init<kP2aEnd>(tab, h, q, kA, kB);
+    p2_span<kP2aEnd, kAheadTwist + 1, kP2Part>(tab, o, prev, h, kA, kB, s_prog);  // parts of rows 208-223
+    __builtin_amdgcn_raw_buffer_store_b32(prev, rs, lane * 4, kAheadTwist * row_bytes, HZ_P2_AUX);  // row 224's final word
+    p2_span<kAheadTwist + 1, kP2bEnd, kP2Final>(tab, o, prev, h, kA, kB, s_prog);
+  } else {
+    // rows 0 and 1 of the next generation are P2c's own last words: their
+    // far rows (397, 398: P2b's) loaded now, used after the chain
+    const uint32_t f0 = act ? slot[(size_t)397 * nr + b] : 0u, f1 = act ? slot[(size_t)398 * nr + b] : 0u;
+    p2_ahead_init<kP2bEnd>(tab, h, q, kA, kB);
+    constexpr int G = kP2bEnd + 8 * ((kMT - kP2bEnd) / 8);
+    p2_span<kP2bEnd, G, kP2Keep>(tab, o, prev, h, kA, kB, s_prog);
+    p2_tail<G, kMT, kP2Keep>(o, lane, prev, h);
+    p2_publish(s_prog, kMT);
+    const uint32_t row1 = (first1 ^ ((prev ^ (prev >> 30)) * 1566083941U)) - 1U;  // the last step, at i = 1
+    // mt[0] = 0x80000000 after init_by_array; row 1's next row is row 2
+    __builtin_amdgcn_raw_buffer_store_b32(f0 ^ twist_part(0x80000000u, row1), rs, lane * 4, 0, HZ_P2_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(f1 ^ twist_part(row1, row2), rs, lane * 4, row_bytes, HZ_P2_AUX);
+  }
+  if (K < 2) {
+    if (ok) {
+      uint32_t *ho = K == 0 ? a.p2h_w : a.p3h_w;
+      ho[b] = prev;
+      ho[nr + b] = first1;
+      ho[2 * nr + b] = row2;
+      ho[3 * nr + b] = h.last;
+      a.s_tag[1 + K][b] = e * 8 + 3 + K;
+    }
+  } else if (ok) {
+    a.s_tag[3][b] = e * 8 + 5;
+  }
+}
+
+// The twist (seed blocks, wave 3): rows [0, kAheadTwist) of the next
+// generation into P2c's slot (the stream at cursor kMTAhead): row r's new
+// word is the far row r + 397 (P2b's below row kP2bEnd, from HBM; P2c's from
+// LDS) xor row r's twist part, which P2a and P2b left in the slot (rows
+// 2-223).  Lane: four boards, rows grp + 4 i, grp = lane / 16, so iteration
+// i needs P2c's rows up to 4 i + 400 (from iteration 9 on: the rows below
+// kP2bEnd are in registers) and follows P2c's progress (s_prog),
+// two iterations per publish of P2c's; rows 0 and 1 (from row 1, P2c's last
+// step, and row 2's final word) are P2c's own.  All its loads precede its
+// stores.  (Before the parts, the wave shuffled each row's
+// successor in from the next lane group and ran at ~350 cycles per
+// iteration, ending ~8 k cycles after P2c: profiles/r04/p2/.)
+constexpr int kTwIters = kAheadTwist / 4;
+constexpr int kTwHbm = (kP2bEnd - 397 + 3) / 4;  // iterations whose rows r + 397 are P2b's (HBM)
+__device__ __forceinline__ uint4 xor4(const uint4 &a, const uint4 &b) {
+  return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w);
+}
+__device__ __forceinline__ void p2_twist(const P2Args &a, int b0, int lane, bool any, int *s_prog) {
+  if (!any) return;
+  const size_t nr = (size_t)a.nrow;
+  uint32_t *slot = a.s_mt[3];
+  const int grp = lane >> 4, c4 = (lane & 15) * 4;
+  uint32_t *col = slot + b0 + c4;
+  auto row = [&](int r) { return p2_ld4(col + (size_t)r * nr); };
+  const __amdgpu_buffer_rsrc_t rs = p2_slot_rsrc(slot, b0, nr);
+  const int row_bytes = __builtin_amdgcn_readfirstlane((int)(nr * 4));
+  auto store = [&](int r, const uint4 &v) {
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    // (r = grp + 4 i differs across the lane groups: per-lane voffset, no soffset)
+    __builtin_amdgcn_raw_buffer_store_b128(v4u{v.x, v.y, v.z, v.w}, rs, c4 * 4 + r * row_bytes, 0, HZ_P2_AUX);
+  };
+  [[maybe_unused]] const int b = b0 + lane;  // (P2_PHASE's board)
+  HZ_DIAG_T0(tz);
+  // (the wave has ~16 k cycles of slack: its 4 MB of loads wait until P2c is
+  // 64 rows in, out of the launch's opening burst, where every other
+  // stage's inputs arrive)
+  int have = p2_wait(s_prog, kP2bEnd + 64, a.spin, a.err);
+  P2_PHASE(35, tz);
+  uint4 pt[kTwIters], fh[kTwHbm];
+#pragma unroll
+  for (int i = 0; i < kTwIters; i++) {
+    const int r = grp + 4 * i;
+    pt[i] = r >= 2 ? row(r) : make_uint4(0, 0, 0, 0);
+  }
+#pragma unroll
+  for (int i = 0; i < kTwHbm; i++) {
+    const int r = grp + 4 * i + 397;
+    fh[i] = r < kP2bEnd ? row(r) : make_uint4(0, 0, 0, 0);
+  }
+  auto far = [&](int i) -> uint4 {
+    const int r = grp + 4 * i;
+    if (i < kTwHbm && r + 397 < kP2bEnd) return fh[i < kTwHbm ? i : 0];
+    const uint32_t *d = hz_lds + (r + 397) * kLdsStride + c4;
+    return make_uint4(d[0], d[1], d[2], d[3]);
+  };
+#pragma unroll
+  for (int i = 0; i < kTwIters; i += 2) {
+    const int need = 4 * (i + 1) + 3 + 397 + 1;  // the pair's far rows final
+    if (need > kP2bEnd && have < need) have = p2_wait(s_prog, need, a.spin, a.err);
+    const uint4 f0 = far(i), f1 = far(i + 1);
+    if (i > 0 || grp >= 2) store(grp + 4 * i, xor4(f0, pt[i]));
+    store(grp + 4 * (i + 1), xor4(f1, pt[i + 1]));
+    if (i == 0) P2_PHASE(36, tz);
+  }
+  P2_PHASE(37, tz);
+  // (rows 224..623 keep pass 2's words: the current generation's tail)
+}
+
+// seed blocks: waves 0-2 P2a, P2b, P2c; wave 3 the twist of P2c's episode
+__device__ __forceinline__ void p2_seed(const P2Args &a, int blk) {
+  __shared__ int s_prog;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int b0 = blk * kBlock, b = b0 + lane;
+  const bool act = b < a.n;
+  if (tid == 0) s_prog = 0;
+  // each stage's episode and decision (and P2c's for the twist wave), read
+  // before the barrier, so before any wave rewrites a tag
+  const int k = w < 3 ? w : 2;
+  const int e = act ? a.ep_in[b] + kP2Last - 1 - k : 0;
+  const bool ok = act && (k == 0 ? a.p1t_r[b] : a.s_tag[1 + k][b]) == e * 8 + 2 + k;
+  __syncthreads();
+  if (w == 0) p2_third<0>(a, b0, lane, e, ok, &s_prog);
+  else if (w == 1) p2_third<1>(a, b0, lane, e, ok, &s_prog);
+  else if (w == 2) p2_third<2>(a, b0, lane, e, ok, &s_prog);
+  else p2_twist(a, b0, lane, __any(ok), &s_prog);
+}
+
+// a draw stage: draws [d0, d1) of episode e on its stream slot, from an LDS
+// window (at `base`) of kP2Win rows starting at the wave's lowest start
+// cursor (the wave's 64 boards, staged here); `in` (stage > 0) holds the
+// draws so far, `out` gets them plus these; the cursors go to the slot's
+// cursor table
+__device__ __forceinline__ int wave_min_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ void p2_draw_stage(const P2Args &a, int b0, int lane, int stage, int base) {
+  const int b = b0 + lane;
+  HZ_DIAG_T0(t0);
+  const bool act = b < a.n;
+  const size_t nr = (size_t)a.nrow;
+  const int d0 = a.dcut[stage], d1 = stage == kP2Draw - 1 ? a.draws : min(a.draws, a.dcut[stage + 1]);
+  const int e = act ? a.ep_in[b] + kP2Last - kP2SDraw - stage : 0;
+  const uint32_t *slot = a.s_mt[kP2SDraw + stage];
+  int32_t *cur = a.s_cur[kP2SDraw + stage] + b;
+  const P2Draw &in = a.x_r[stage > 0 ? stage - 1 : 0];
+  const P2Draw &out = stage == kP2Draw - 1 ? a.pl_w : a.x_w[stage < kP2Draw - 1 ? stage : 0];
+  bool ok = act && a.s_tag[kP2SDraw + stage][b] == e * 8 + 5;
+  int k0 = 0, c0 = kMTAhead;
+  uint64_t bag = initial_bag(), q[kAheadWords] = {0, 0, 0, 0};
+  // the window: rows [r0, r0 + kP2Win), 16-B loads (four boards of a row per
+  // lane), all in flight, and one 16-B LDS store each
+  constexpr int U = kP2Win / 4;
+  const int c4 = (lane & 15) * 4;
+  uint4 v[U];
+  auto win_load = [&](int r0) {
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int r = r0 + 4 * u + (lane >> 4);
+      v[u] = p2_ld4(slot + (size_t)r * nr + b0 + c4);
+    }
+  };
+  auto win_store = [&]() {
+#pragma unroll
+    for (int u = 0; u < U; u++)
+      *reinterpret_cast<uint4 *>(hz_lds + base + (4 * u + (lane >> 4)) * kWinStride + c4) = v[u];
+  };
+  // the first stage's window starts at row 0 whatever its tags say (every
+  // start cursor is kMTAhead): its loads go out with the tag's, one round
+  // trip instead of two (rows of another episode are never read: !ok)
+  if (stage == 0) win_load(0);
+  if (stage > 0 && act) {  // (one round trip: used only if the tag matches)
+    const int itag = in.tag[b];
+    k0 = in.k[b];
+    c0 = in.c[b];
+    bag = in.bag[b];
+#pragma unroll
+    for (int i = 0; i < kAheadWords; i++) q[i] = in.q[(size_t)i * nr + b];
+    ok = ok && itag == e * 8 + stage;
+  }
+  const bool draws = ok && k0 >= d0 && d0 < d1;
+  const int r0 = wave_min_i(draws ? (c0 & 0xFFFF) : kAheadTwist) & ~3;
+  if (r0 < kAheadTwist) {
+    if (stage > 0) win_load(r0);
+    win_store();
+  }
+  P2_PHASE(28 + stage, t0);  // window staged
+  if (!act) return;
+  if (!ok) {
+    out.tag[b] = -1;
+    return;
+  }
+  if (stage == 0) cur[0] = kMTAhead;
+  int k = k0, cc = c0;
+  if (draws) {  // every earlier draw is done: continue in the window
+    const int lim = min(r0 + kP2Win, kAheadTwist);
+    StreamDraw<WinMT> d{WinMT(base - r0 * kWinStride + lane, c0, lim)};
+#pragma unroll 1
+    for (int i = d0; i < d1; i++) {
+      if (d.m.pos >= lim) break;
+      const uint32_t p9 = d(bag);
+      // a draw that consumed words past the window is discarded: the next
+      // stage (or a play stage, from the stream slot) redoes it from the
+      // last cursor kept
+      if (d.m.pos > lim) break;
+      apply_pile_fast(bag, p9);
+      const int bit = 9 * i, wd = bit >> 6, off = bit & 63;
+      const uint64_t lo9 = (uint64_t)p9 << off, hi9 = off > 55 ? (uint64_t)p9 >> (64 - off) : 0ull;
+      q[0] |= wd == 0 ? lo9 : 0ull;
+      q[1] |= wd == 1 ? lo9 : wd == 0 ? hi9 : 0ull;
+      q[2] |= wd == 2 ? lo9 : wd == 1 ? hi9 : 0ull;
+      q[3] |= wd == 3 ? lo9 : wd == 2 ? hi9 : 0ull;
+      cc = d.m.cursor();
+      p2_st(&cur[(size_t)(i + 1) * nr], cc);
+      k = i + 1;
+    }
+  }
+  p2_st(&out.k[b], k);
+  p2_st(&out.c[b], cc);
+  p2_st(&out.bag[b], bag);
+#pragma unroll
+  for (int i = 0; i < kAheadWords; i++) p2_st(&out.q[(size_t)i * nr + b], q[i]);
+  p2_st(&out.tag[b], e * 8 + stage + 1);
+}
+
+// the rule hashes of the last draw stage's episode (read by the play stages
+// in the next kP2Play calls)
+__device__ __forceinline__ void p2_hashes(const P2Args &a, int b) {
+  const size_t nr = (size_t)a.nrow;
+  const int e = a.ep_in[b] + kP2Last - (kP2SPlay - 1);
+  const uint64_t rk = rule_key(episode_seed(a.seed_base, b, e));
+#pragma unroll 1
+  for (int j = 0; j < kRulePlies; j++) p2_st(&a.h_w[(size_t)j * nr + b], rule_h32(rk, j));
+  a.ht_w[b] = e;
+}
+
+// a wave of a draw-X or draw-Y block that runs no play stage (kP2Wave):
+// a draw stage, which stages its own window (the wave's) and reads only it,
+// P1, or the rule hashes
+__device__ __forceinline__ void p2_draw(const P2Args &a, int blk, int code) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int b0 = blk * kBlock;
+  if (code < kP2Draw) {
+    p2_draw_stage(a, b0, lane, code, w * kP2WinRows * kWinStride);
+  } else if (code == kWvP1 && b0 + lane < a.n) {
+    p2_p1(a, b0 + lane);
+  } else if (code == kWvHash && b0 + lane < a.n) {
+    p2_hashes(a, b0 + lane);
+  }
+}
+
+// a play stage's state after its plies, for the next play stage
+__device__ __forceinline__ void p2_mid_put(const P2Mid &m, size_t nr, int b, const State &s, const PlayDraw2 &d, int g,
+                                           int e) {
+#pragma unroll
+  for (int k = 0; k < 4; k++) p2_st(&m.st[(size_t)k * nr + b], s.pl[k]);
+  p2_st(&m.st[4 * nr + b], s.piles);
+  p2_st(&m.st[5 * nr + b], s.misc);
+  p2_st(&m.q[b], d.q0);
+  p2_st(&m.q[nr + b], d.q1);
+  p2_st(&m.q[2 * nr + b], d.q2);
+  p2_st(&m.q[3 * nr + b], d.q3);
+  p2_st(&m.i[b], d.d);
+  p2_st(&m.i[nr + b], g);
+  p2_st(&m.i[2 * nr + b], d.fell ? d.gm.cursor() : -1);
+  p2_st(&m.tag[b], e);
+}
+// the previous play stage's state; the draw source continues its script
+// (nd entries, cursors in `cur`) or the slot stream it fell onto
+__device__ __forceinline__ PlayDraw2 p2_mid_get(const P2Mid &m, size_t nr, int b, State &s, int &g, int nd,
+                                               uint32_t *slot, const int32_t *cur) {
+#pragma unroll
+  for (int k = 0; k < 4; k++) s.pl[k] = m.st[(size_t)k * nr + b];
+  s.piles = m.st[4 * nr + b];
+  s.misc = m.st[5 * nr + b];
+  const int d = m.i[b], fc = m.i[2 * nr + b];
+  g = m.i[nr + b];
+  return PlayDraw2{{m.q[b], m.q[nr + b], m.q[2 * nr + b], m.q[3 * nr + b], d, nd}, fc >= 0,
+                   MTR(slot, (int)nr, fc >= 0 ? fc : 0), cur + (size_t)nd * nr};
+}
+
+// Play stage st on episode ep + kP2Play - 1 - st (the last stage: the rest of
+// episode ep, or all of it).  In a play block (in_block) wave w runs stage
+// kP2Play - 1 - w, the last on wave 0 with its LDS fallback; with five stages,
+// stage 0 runs on a wave of a draw block (kWvPlay: it needs no LDS and joins
+// no barrier).  The stages run one code path (st wave-uniform), so a block's
+// waves share one copy of the ply loop in the instruction cache (one inlined
+// copy per stage, ~50 KB each, thrashed the cache the two CUs of a pair
+// share), and k_play2 calls this from one place.
+__device__ __forceinline__ void p2_play(const P2Args &a, int blk, int st, bool in_block) {
+  __shared__ uint64_t s_lds_mask;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int b0 = blk * kBlock, b = b0 + lane;
+  const bool act = b < a.n;
+  const uint64_t actmask = __ballot(act);
+  const int nb = a.n - b0 < kBlock ? a.n - b0 : kBlock;
+  const size_t nr = (size_t)a.nrow;
+  HZ_DIAG_T0(t0);
+  const bool last = st == kP2Play - 1;
+  bool lds_used = false;
+  if (act) {
+    const int e = last ? a.episode[b] : a.ep_in[b] + kP2Play - 1 - st;
+    const P2Draw &pl = a.pl_r[st];
+    const uint32_t *hsrc = a.h_r[st];
+    const int32_t *htag = a.ht_r[st];
+    uint32_t *slot = a.s_mt[kP2SPlay + st] + b;
+    const int32_t *cur = a.s_cur[kP2SPlay + st] + b;
+    const int g_end = last ? a.max_plies : min(a.cut[st < kP2Play - 1 ? st : 0], a.max_plies);
+    const uint64_t sd = episode_seed(a.seed_base, b, e), rk = rule_key(sd);
+    // every input's loads issued together (used only if the tags match)
+    const int ptag = pl.tag[b], nd = pl.k[b];
+    const int mtag = st > 0 ? a.m_r[st - 1].tag[b] : e;
+    const uint32_t *hs = htag[b] == e ? hsrc + b : nullptr;
+    State s;
+    int g = 0;
+    PlayDraw2 draw = st == 0 ? PlayDraw2{{pl.q[b], pl.q[nr + b], pl.q[2 * nr + b], pl.q[3 * nr + b], 0, nd}, false,
+                                         MTR(slot, (int)nr, 0), cur + (size_t)nd * nr}
+                             : p2_mid_get(a.m_r[st - 1], nr, b, s, g, nd, slot, cur);
+    const bool prep = ptag == e * 8 + kP2Draw && mtag == e;
+    if (prep) {
+      if (st == 0) {
+        if (__all(nd >= 5)) draw.scripted_reset(s);
+        else reset_state(s, draw);
+      }
+      P2_PHASE(16 + 2 * st, t0);
+      g += p2_plies(s, draw, g, g_end, rk, hs, nr);
+      P2_PHASE(17 + 2 * st, t0);
+    }
+    if (!last) {
+      const P2Mid &mo = a.m_w[st < kP2Play - 1 ? st : 0];
+      if (prep) p2_mid_put(mo, nr, b, s, draw, g, e);
+      else mo.tag[b] = -1;
+    } else {
+      int cursor, src;
+      if (prep) {
+        cursor = draw.fell ? draw.gm.cursor() : cur[(size_t)draw.d * nr];
+        src = 2 + a.s_idx_last;
+      } else {  // unprepared: the whole game, the stream seeded and drawn in LDS
+        mt_seed(hz_lds + lane, kLdsStride, sd);
+        PlayDraw fb{{0, 0, 0, 0, 0, 0}, LdsMT(lane, kMTSeeded), false, false, MT(nullptr, 0), nullptr};
+        reset_state(s, fb);
+        g = p2_plies(s, fb, 0, a.max_plies, rk, nullptr, nr);
+        cursor = fb.m.cursor();
+        src = -1;
+        lds_used = true;
+      }
+      a.episode[b] = e + 1;
+      if (score_pending(s.misc)) finish_game(s);
+      P2_PHASE(27, t0);
+      store_state(a.st, a.n, b, s);
+      a.pos[b] = cursor;
+      a.mt_src[b] = src;
+      a.win_tag[b] = -1;
+      a.ply[b] = g;
+      a.seed[b] = sd;
+      a.ep_out[b] = e + 1;
+      // the game this call completes, as hz_play's other pipeline counts it
+      if (a.games_done) a.games_done[b] = phase_of(s.misc) == PH_OVER ? 1 : 0;
+      if (a.steps_done) a.steps_done[b] = g;
+    }
+    if (in_block) P2_PHASE(w, t0);  // the wave's duration: the last stage .. the second
+  }
+  if (!in_block) return;
+  if (w == 0) {
+    const uint64_t lm = __ballot(lds_used);
+    if (lane == 0) s_lds_mask = lm;
+  }
+  __syncthreads();
+  const uint64_t lds_mask = s_lds_mask & actmask;
+  if (lds_mask) stage_mt(a.mt + (size_t)b0 * kMT, nb, tid, lds_mask, false);
+}
+
+// one 162 KB-LDS block per CU, so one wave per SIMD: every wave may use the
+// whole register file
+__global__ void __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) k_play2(P2Args a, int nblk) {
+  const int blk = (int)blockIdx.x;
+  const int role = blk / nblk;  // 0 play, 1 draw X, 2 draw Y, 3 seed blocks
+  const int rb = blk - role * nblk;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int code = role == 1 || role == 2 ? kP2Wave[4 * (role - 1) + wv] : kWvIdle;
+  // the wave's play stage, if it runs one
+  const int st = role == 0 ? kP2Play - 1 - wv : code == kWvPlay ? 0 : -1;
+#ifdef HZ_DIAG
+  if (g_role_only >= 0 && g_role_only != role) return;
+  const uint64_t t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
+#endif
+  if (st >= 0) p2_play(a, rb, st, role == 0);
+  else if (role == 3) p2_seed(a, rb);
+  else if (role != 0) p2_draw(a, rb, code);
+#ifdef HZ_DIAG
+  {  // wave durations per board, slot 4 role + wave: 0-3 play (the last stage
+     // .. the second: stamped in p2_play, before its barrier), 4-7 draw X,
+     // 8-11 draw Y (kP2Wave says what each runs), 12-15 seed (P2a, P2b, P2c,
+     // twist)
+    const int w = threadIdx.x >> 6, bb = rb * kBlock + (threadIdx.x & 63);
+    const bool idle = (role == 1 || role == 2) && code == kWvIdle;
+    if (g_stamps && role > 0 && !idle && bb < a.n) g_stamps[(size_t)bb * kP2Stamps + 4 * role + w] = __builtin_amdgcn_s_memtime() - t0;
+    // the wave's realtime (100 MHz) start and end and its clock cycles, per
+    // (role, wave): slot 40 of the block's boards 16 role + 4 w + k
+    // (tools/p2_span.py: the launch's span against its waves')
+    if (g_stamps && bb < a.n && (threadIdx.x & 63) < 4) {
+      const int k = threadIdx.x & 63;
+      const uint64_t v = k == 0 ? r0 : k == 1 ? __builtin_amdgcn_s_memrealtime() : k == 2 ? t0 : __builtin_amdgcn_s_memtime();
+      g_stamps[(size_t)(rb * kBlock + 16 * role + 4 * w + k) * kP2Stamps + 40] = v;
+      // where the wave ran: HW_ID (cu, sh, se in bits 8-14) and XCC_ID
+      if (k == 0)
+        g_stamps[(size_t)(rb * kBlock + 16 * role + 4 * w) * kP2Stamps + 41] =
+            (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((uint64_t)__builtin_amdgcn_s_getreg((15 << 11) | 20) << 32);
+    }
+  }
+#endif
+}
+
+// boards whose stream lives in a pipeline-2 slot (mt_src = 2 + slot): the
+// slot's column (word-major) into the board's own stream, one wave per board
+struct P2Slots {
+  uint32_t *s[kP2Stream];
+};
+__global__ void __launch_bounds__(64) k_mt_materialize2(uint32_t *__restrict__ mt, P2Slots slots,
+                                                       int32_t *__restrict__ mt_src, long nrow) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int src = mt_src[b];
+  if (src < 2 || src >= 2 + kP2Stream) return;
+  const uint32_t *from = slots.s[src - 2] + b;
+  uint32_t *to = mt + (size_t)b * kMT;
+  uint32_t v[(kMT + 63) / 64];
+#pragma unroll
+  for (int k = 0; k < (kMT + 63) / 64; k++) v[k] = lane + 64 * k < kMT ? from[(size_t)(lane + 64 * k) * nrow] : 0u;
+#pragma unroll
+  for (int k = 0; k < (kMT + 63) / 64; k++)
+    if (lane + 64 * k < kMT) to[lane + 64 * k] = v[k];
+  if (lane == 0) mt_src[b] = -1;
+}
+
+
+}  // namespace

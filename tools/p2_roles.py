@@ -18,7 +18,7 @@ out = {}
 for pipe in (1, 2):
     env = BatchedEnv(n, device="cuda")
     env.set_pipeline(pipe)
-    # (the draw blocks' waves as hz_env.hip's default HZ_P2_WAVES places them)
+    # (the draw blocks' waves as hz_play2.hpp's default HZ_P2_WAVES places them)
     names = ({0: "playE", 1: "playD", 2: "playC", 3: "playB", 4: "D1", 5: "D2", 6: "D5", 7: "hashes", 8: "D3",
               9: "D4", 10: "P1", 11: "playA", 12: "P2a", 13: "P2b", 14: "P2c", 15: "twist",
               16: "playA_loaded", 17: "playA_plies", 18: "playB_loaded", 19: "playB_plies",

@@ -38,7 +38,7 @@ if ROLE >= 0:
     torch.cuda.synchronize()
     L.hz_diag_set_role_only(-1)
 s = stamps[:, 40].cpu().numpy().astype(np.int64).reshape(-1, 64)  # [block][16 role + 4 w + k]
-# (the draw blocks' waves as hz_env.hip's default HZ_P2_WAVES places them)
+# (the draw blocks' waves as hz_play2.hpp's default HZ_P2_WAVES places them)
 names = {0: ["playE", "playD", "playC", "playB"], 1: ["D1", "D2", "D5", "hashes"], 2: ["D3", "D4", "P1", "playA"],
          3: ["P2a", "P2b", "P2c", "twist"]}
 rs, re_, ts, te = (s[:, k::4] for k in range(4))  # [block][role * 4 + w]
