@@ -48,7 +48,8 @@ def split3_bf16(w):
 
 def pack_conv3x3_x6(w):
     """[co][ci][3][3] fp32 -> bf16 planes [kh*3+kw][ci/32][plane][co][ci%32],
-    the layout hz_conv3x3_x6_bias_act reads (one 16-byte B fragment per lane)."""
+    the layout hz_conv3x3_x6_bias_act reads (one 16-byte B fragment per lane),
+    and hz_conv3x3_x6g_bias_act for any ci, co that are multiples of 32."""
     co, ci = w.shape[0], w.shape[1]
     p = split3_bf16(w)                                   # [3][co][ci][3][3]
     p = p.permute(3, 4, 2, 0, 1).reshape(9, ci // 32, 32, 3, co)  # [tap][q][k][plane][co]
@@ -357,6 +358,77 @@ def _stem_x6_act(board, wpack6, b, live=None):
     return out
 
 
+WIDE_FILTERS = tuple(range(32, 257, 32))  # cin, cout of hz_conv3x3_x6g_bias_act
+
+
+def pack_stem_x6g(w):
+    """Stem weights [F][38][3][3] in hz_stem3x3_x6g_bias_act's layout: the
+    input channels zero-padded to 64, packed as pack_conv3x3_x6."""
+    w64 = torch.zeros(w.shape[0], 64, 3, 3, dtype=w.dtype, device=w.device)
+    w64[:, :w.shape[1]] = w
+    return pack_conv3x3_x6(w64)
+
+
+def _conv3x3_x6g_act(x, wpack6, b, res=None, live=None, products=6, spg=0):
+    """_conv3x3_xn_act for cin, cout in WIDE_FILTERS (hz_conv3x3_x6g_bias_act;
+    wpack6 [9][cin/32][3][cout][32]); spg 1 or 8 forces the one- or the
+    eight-state workgroup form (the same bits), 0 chooses by the batch."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)
+            and x.shape[2:] == (5, 7)):
+        raise NativeError("hz_conv3x3_x6g_bias_act needs a CUDA fp32 channels_last [B,cin,5,7] activation")
+    cin, cout = x.shape[1], b.numel()
+    if wpack6.numel() != 27 * cin * cout or not wpack6.is_contiguous():
+        raise NativeError("hz_conv3x3_x6g_bias_act: weights not packed [9][cin/32][3][cout][32]")
+    out = torch.empty(x.shape[0], cout, 5, 7, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    if res is not None and (res.shape != out.shape or res.stride() != out.stride()):
+        raise NativeError("hz_conv3x3_x6g_bias_act: residual layout differs from the output")
+    rc = lib().hz_conv3x3_x6g_bias_act(x.data_ptr(), wpack6.data_ptr(), b.data_ptr(),
+                                       res.data_ptr() if res is not None else None, out.data_ptr(), cin, cout,
+                                       x.shape[0], _live_ptr(live), products, spg,
+                                       torch.cuda.current_stream(x.device).cuda_stream)
+    if rc != 0:
+        raise NativeError(f"hz_conv3x3_x6g_bias_act failed ({rc})")
+    return out
+
+
+def _stem_x6g_act(board, wpack6, b, live=None, spg=0):
+    """_stem_x6_act for the filter counts of WIDE_FILTERS (hz_stem3x3_x6g_bias_act)."""
+    if not (board.is_cuda and board.dtype == torch.float32 and board.shape[1:] == (38, 5, 7)):
+        raise NativeError("hz_stem3x3_x6g_bias_act needs a CUDA fp32 [B,38,5,7] board")
+    board = board.contiguous()
+    cout = b.numel()
+    if wpack6.numel() != 27 * 64 * cout or not wpack6.is_contiguous():
+        raise NativeError("hz_stem3x3_x6g_bias_act: weights not packed [9][2][3][cout][32]")
+    out = torch.empty(board.shape[0], cout, 5, 7, dtype=torch.float32, device=board.device,
+                      memory_format=torch.channels_last)
+    rc = lib().hz_stem3x3_x6g_bias_act(board.data_ptr(), wpack6.data_ptr(), b.data_ptr(), out.data_ptr(), cout,
+                                       board.shape[0], _live_ptr(live), spg,
+                                       torch.cuda.current_stream(board.device).cuda_stream)
+    if rc != 0:
+        raise NativeError(f"hz_stem3x3_x6g_bias_act failed ({rc})")
+    return out
+
+
+def _heads_fc_g(x, glob, hw, hb, fc, dims, live=None, logits=True, probs=False):
+    """_heads_fc for other shapes (hz_heads_fc_g): dims = (pf, vf, hidden),
+    hw [pf + vf][ch]."""
+    B, ch = x.shape[0], x.shape[1]
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)
+            and x.shape[2:] == (5, 7) and hw.shape[1] == ch):
+        raise NativeError("hz_heads_fc_g needs a CUDA fp32 channels_last [B,ch,5,7] activation")
+    glob = glob.to(torch.float32).contiguous()
+    lo = torch.empty(B, 143, dtype=torch.float32, device=x.device) if logits else None
+    pr = torch.empty(B, 143, dtype=torch.float32, device=x.device) if probs else None
+    v = torch.empty(B, dtype=torch.float32, device=x.device)
+    ptr = (lambda t: t.data_ptr() if t is not None else None)
+    rc = lib().hz_heads_fc_g(x.data_ptr(), glob.data_ptr(), hw.data_ptr(), hb.data_ptr(),
+                             *(t.data_ptr() for t in fc), ptr(lo), ptr(pr), v.data_ptr(), ch, *dims, B,
+                             _live_ptr(live), torch.cuda.current_stream(x.device).cuda_stream)
+    if rc != 0:
+        raise NativeError(f"hz_heads_fc_g failed ({rc})")
+    return lo, pr, v
+
+
 def _stem_act(board, wpack, b, live=None):
     """relu(conv3x3(board) + b) from the encoder's NCHW board, NHWC out, one HIP launch."""
     if not (board.is_cuda and board.dtype == torch.float32 and board.shape[1:] == (38, 5, 7)):
@@ -454,6 +526,12 @@ class FoldedNet(nn.Module):
     # hz_conv3x3_xn_bias_act per block above; never the split tower or the
     # fused block/tower forms).  tower=None reads HZ_TOWER (default "x6") at
     # construction.
+    # A network with another filter count F in WIDE_FILTERS (F != 128) takes,
+    # in the bf16 modes, the width-generic kernels of csrc/hz_net_wide.hip:
+    # hz_stem3x3_x6g_bias_act, two hz_conv3x3_x6g_bias_act per block (x6, x3
+    # and x1 alike) and hz_heads_fc_g (1-4 head filters, hidden <= 1024), with
+    # `live` passed through.  128-filter networks keep the kernels above (and
+    # PyTorch's linear layers at a hidden width other than 256).
     TOWER_MFMA = ("x6", "x3", "x1", "f32")
     TOWER_PRODUCTS = {"x6": 6, "x3": 3, "x1": 1}
     # batches of at most this many boards run the x6 tower as one resident
@@ -473,6 +551,9 @@ class FoldedNet(nn.Module):
     # 2.261 ms and 2.272 vs 2.286 ms on two boxes; self-play 141.8 vs 141.0
     # games/s (profiles/r05/tower)
     tower_loop = int(os.environ.get("HZ_TOWER_LOOP", "1"))
+    # the width-generic convs' workgroup form: 0 = by the batch, 1 or 8 forced
+    # (tests, tools/width_bench.py; the same bits)
+    wide_spg = 0
 
     def __init__(self, net, epilogue=None, native_conv=True, tower=None, fused_head=True):
         super().__init__()
@@ -496,10 +577,15 @@ class FoldedNet(nn.Module):
     def row_independent(self):
         """True where every stage is one of the HIP kernels, which sum a row
         in one order whatever batch it is in (so its result is the same bits
-        in any batch).  The unfused head's F.linear (a value-head width other
-        than 256) and the MIOpen convs (other filter counts) choose their
-        algorithm by the batch size: measured on a 128x20 net with hidden 512,
-        a row's value differed in the last bits between a batch of 1 and of 803."""
+        in any batch): the 128-filter networks with the fused head, and in the
+        bf16 modes the other filter counts of WIDE_FILTERS with head shapes
+        hz_heads_fc_g takes.  The unfused head's F.linear (128 filters with a
+        value-head width other than 256) and the MIOpen convs (tower "f32" or
+        a filter count outside WIDE_FILTERS) choose their algorithm by the
+        batch size: measured on a 128x20 net with hidden 512, a row's value
+        differed in the last bits between a batch of 1 and of 803."""
+        if self.wide is not None:
+            return True
         return self.stem_packed is not None and (self.packed is not None or not self.blocks) and self.fc is not None
 
     def set_tower(self, kind):
@@ -527,7 +613,8 @@ class FoldedNet(nn.Module):
         self.stem = _fold(n.conv, n.bn)
         self.blocks = [(_fold(b.conv1, b.bn1), _fold(b.conv2, b.bn2)) for b in n.residual_blocks]
         # the tower's 128-channel convs run as one fused HIP kernel each
-        # (conv + bias + skip + ReLU); other widths use MIOpen + hz_bias_act
+        # (conv + bias + skip + ReLU); other widths: self.wide below, else
+        # MIOpen + hz_bias_act
         self.stem_packed = None
         if self.native_conv and self.stem[0].shape == (128, 38, 3, 3):
             self.stem_packed = pack_stem_x6(self.stem[0]) if x6 else pack_stem(self.stem[0])
@@ -573,6 +660,24 @@ class FoldedNet(nn.Module):
             self.fc = (self.pfc[0].t().contiguous(), self.pfc[1].contiguous(), self.vfc1[0].t().contiguous(),
                        self.vfc1[1].contiguous(), self.vfc2[0].reshape(-1).contiguous(),
                        self.vfc2[1].contiguous())
+        # another filter count, bf16 modes: every stage on the width-generic
+        # kernels (stem pack, per-block packs, head weights + (pf, vf, hidden))
+        self.wide = None
+        F_, pf, vf, hid = self.stem[0].shape[0], self.pconv[0].shape[0], self.vconv[0].shape[0], self.vfc1[0].shape[0]
+        if (self.native_conv and x6 and F_ != 128 and F_ in WIDE_FILTERS and self.stem[0].shape == (F_, 38, 3, 3)
+                and all(w.shape == (F_, F_, 3, 3) for blk in self.blocks for (w, _) in blk)
+                and self.pconv[0].shape == (pf, F_, 1, 1) and self.vconv[0].shape == (vf, F_, 1, 1)
+                and 1 <= pf <= 4 and 1 <= vf <= 4 and 1 <= hid <= 1024
+                and self.pfc[0].shape == (143, pf * 35 + 42) and self.vfc1[0].shape == (hid, vf * 35 + 42)
+                and self.vfc2[0].shape == (1, hid)):
+            self.wide = dict(
+                stem=pack_stem_x6g(self.stem[0]),
+                blocks=[(pack_conv3x3_x6(w1), pack_conv3x3_x6(w2)) for (w1, _), (w2, _) in self.blocks],
+                hw=torch.cat((self.pconv[0].reshape(pf, F_), self.vconv[0].reshape(vf, F_))).contiguous(),
+                hb=torch.cat((self.pconv[1], self.vconv[1])).contiguous(),
+                fc=(self.pfc[0].t().contiguous(), self.pfc[1].contiguous(), self.vfc1[0].t().contiguous(),
+                    self.vfc1[1].contiguous(), self.vfc2[0].reshape(-1).contiguous(), self.vfc2[1].contiguous()),
+                dims=(pf, vf, hid))
 
     @torch.no_grad()
     def forward(self, board, glob, live=None):
@@ -590,6 +695,15 @@ class FoldedNet(nn.Module):
         ep = self.epilogue
         w, b = self.stem
         products = self.products
+        if self.wide is not None:
+            wd, spg = self.wide, self.wide_spg
+            x = _stem_x6g_act(board, wd["stem"], b, live, spg)
+            for ((_, b1), (_, b2)), (p1, p2) in zip(self.blocks, wd["blocks"]):
+                y = _conv3x3_x6g_act(x, p1, b1, None, live, products, spg)
+                x = _conv3x3_x6g_act(y, p2, b2, x, live, products, spg)
+            lo, pr, v = _heads_fc_g(x, glob, wd["hw"], wd["hb"], wd["fc"], wd["dims"], live=live, logits=not probs,
+                                    probs=probs)
+            return (pr, v) if probs else (lo, v.unsqueeze(1))
         if self.stem_packed is None or self.packed is None:
             live = None
         if self.stem_packed is not None:  # reads the NCHW board directly

@@ -466,6 +466,48 @@ int hz_heads_fc(const float *x, const float *glob, const float *hw, const float 
                 const float *bp, const float *w1T, const float *b1, const float *w2, const float *b2, float *logits,
                 float *probs, float *value, int32_t batch, const int32_t *live, void *stream);
 
+/* ---- other filter counts and head shapes (csrc/hz_net_wide.hip) ---------- */
+/* hz_conv3x3_xn_bias_act for the tower convs of a network with another
+ * cnn_filters (model.py:362-371 with ch = cin = cout; model.py:376-393 for
+ * the skip): cin, cout multiples of 32 in [32, 256], x NHWC
+ * [batch][5][7][cin], res, out NHWC [batch][5][7][cout] (res may be NULL; out
+ * must not alias x or res), wpack6 = bf16 planes
+ * [kh*3+kw][cin/32][plane h,m,l][cout][cin%32] (hzamd/infer.py:pack_conv3x3_x6),
+ * products as in hz_conv3x3_xn_bias_act.  Per output element the products are
+ * accumulated in hz_conv3x3_x6_bias_act's order (chunks of 32 input channels
+ * ascending, taps 0..8, plane pairs pa outer, pb inner), so at cin = cout =
+ * 128 the result is that kernel's (products 6) or hz_conv3x3_xn_bias_act's
+ * (3, 1) bit for bit.  Two workgroup forms with identical bits: one state per
+ * workgroup, or eight (280 rows share each weight fragment).
+ * spg: 0 = chosen by batch (one state per workgroup up to a row count that
+ * falls with cin * cout: 7,550 at 32 x 32, 2,887 at 64 x 64, 422 at 256 x 256;
+ * HZ_X6G_SMALL_MAX overrides it for every width), 1 or 8 = forced (tests, A/B).  -1, nothing enqueued: cin/cout not a
+ * multiple of 32 in [32, 256], products not in {1,3,6}, spg not in {0,1,8}, batch < 0. */
+int hz_conv3x3_x6g_bias_act(const float *x, const void *wpack6, const float *bias, const float *res, float *out,
+                            int32_t cin, int32_t cout, int32_t batch, const int32_t *live, int32_t products,
+                            int32_t spg, void *stream);
+/* The stem (model.py:328-330, 38 -> cout channels, padding 1) for those
+ * networks, all six piece products: board NCHW [batch][38][5][7] as the
+ * encoder writes it, out NHWC [batch][5][7][cout]; wpack6 = w with the input
+ * channels zero-padded to 64, packed as above (hzamd/infer.py:pack_stem_x6g).
+ * Channel 37 (phase / 3) is split like any other value; not the 128-wide
+ * stem's bits (that one packs its second chunk by taps).  spg and the
+ * refusals as above. */
+int hz_stem3x3_x6g_bias_act(const float *board, const void *wpack6, const float *bias, float *out, int32_t cout,
+                            int32_t batch, const int32_t *live, int32_t spg, void *stream);
+/* hz_heads_fc for other shapes (model.py:336-355, BN folded; predict's
+ * softmax, model.py:100-104): x NHWC [batch][5][7][ch], hw [pf + vf][ch]
+ * (policy filters first), hb [pf + vf], wpT = policy_fc.weight^T
+ * [pf*35 + 42][143], w1T = value_fc1.weight^T [vf*35 + 42][hidden], w2
+ * [hidden], b2 [1]; logits and probs optional (NULL: not written), value
+ * [batch].  fp32 FMAs, each sum in one order whatever the batch or live (not
+ * hz_heads_fc's bits).  -1, nothing enqueued: ch as cin above, pf or vf
+ * outside 1..4, hidden outside 1..1024, batch < 0. */
+int hz_heads_fc_g(const float *x, const float *glob, const float *hw, const float *hb, const float *wpT,
+                  const float *bp, const float *w1T, const float *b1, const float *w2, const float *b2, float *logits,
+                  float *probs, float *value, int32_t ch, int32_t pf, int32_t vf, int32_t hidden, int32_t batch,
+                  const int32_t *live, void *stream);
+
 /* ---- build info ---------------------------------------------------------- */
 const char *hz_version(void);
 
