@@ -68,6 +68,38 @@ class MCTS:
         return self.root.edges
 
 
+def root_edge_records(root, n, w, q, p, child):
+    """The reference's root.edges (MCTS.py:268-269) from one board's
+    root-edge arrays by action id (BatchedMCTS.root_edges(): n, w, q, p,
+    child; an action has an edge where child >= 0): {move: Edge} in ascending
+    action order, stats N int, W and Q float, P np.float32 as Edge.stats holds
+    them (MCTS.py:34-39).  Only the root's edges exist here: out_node is None."""
+    edges = {}
+    for a in np.flatnonzero(np.asarray(child) >= 0):
+        move = action_to_move(a)
+        e = Edge(root, None, np.float32(p[a]), move)
+        e.stats.update(N=int(n[a]), W=float(w[a]), Q=float(q[a]))
+        edges[move] = e
+    return edges
+
+
+_LAST = None  # (search handle, game state, config) of the most recent get_best_action_and_pi
+
+
+def last_search():
+    """An MCTS object for the most recent get_best_action_and_pi call: its
+    root.edges (get_root_edges()) hold that search's N, W, Q and P per move
+    (root_edge_records).  Built here, on demand, from the device tree the
+    search left (one launch and one read); None before any search."""
+    if _LAST is None:
+        return None
+    search, game_state, mcts_config = _LAST
+    r = {k: v[0].cpu().numpy() for k, v in search.root_edges(value=False).items()}
+    root = Node(game_state)
+    root.edges = root_edge_records(root, r["n"], r["w"], r["q"], r["p"], r["child"])
+    return MCTS(root, mcts_config)
+
+
 _SEARCH = {}
 # simulations 2.. of a search replay one captured HIP graph, kept across moves
 # while the network's weights do not change (hzamd.mcts.BatchedMCTS.search);
@@ -148,6 +180,8 @@ def get_best_action_and_pi(game_state, model_manager, mcts_config, game_move_num
                            graph=GRAPH)
     v = visits[0].cpu().numpy().astype(np.int64)
     br.store_rng()
+    global _LAST
+    _LAST = (search, game_state, mcts_config)  # for last_search(): the tree stays on the device
 
     # root edges exist once the root was expanded, in ascending action order
     root_actions = legal if (sims > 0 and not terminal) else []
@@ -175,4 +209,4 @@ def get_best_action_and_pi(game_state, model_manager, mcts_config, game_move_num
     return best, pi
 
 
-__all__ = ["Node", "Edge", "MCTS", "get_best_action_and_pi", "get_action_index"]
+__all__ = ["Node", "Edge", "MCTS", "get_best_action_and_pi", "get_action_index", "last_search"]

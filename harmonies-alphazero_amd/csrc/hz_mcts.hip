@@ -1290,6 +1290,136 @@ __global__ void __launch_bounds__(kWave) k_result(hz_mcts m, int32_t *__restrict
   for (int i = lane; i < ne; i += kWave) out[m.edge_action[eb + e0 + i]] = m.edge_n[eb + e0 + i];
 }
 
+// ------------------------------------------------------------ search report
+// Read-only views of the tree for the caller (no reference kernel: the
+// reference keeps Python objects, MCTS.get_root_edges MCTS.py:268-269).  Both
+// kernels trust nothing they read from the tree: a node's edge range is used
+// only when it lies inside the board's edge count, a child link only when it
+// is below the board's node count; anything else reads as "no edges".
+// A node's edge range [e0, e0 + ne) when it lies within the board's n_edges
+// edges (two per lane at most), else ne = 0.
+__device__ __forceinline__ int checked_edges(const hz_mcts &m, size_t nb, int node, int n_edges, int &e0) {
+  const int ne = m.node_ne[nb + node];
+  e0 = m.node_e0[nb + node];
+  return ne > 0 && ne <= kChildSlots && e0 >= 0 && e0 <= n_edges - ne ? ne : 0;
+}
+__device__ __forceinline__ bool checked_counts(const hz_mcts &m, int n_nodes, int n_edges) {
+  return n_nodes > 0 && n_nodes <= m.max_nodes && n_edges >= 0 && n_edges <= m.max_edges;
+}
+
+// The root's edges by action id (MCTS.py:355-376 reads N from them; Edge.stats
+// MCTS.py:34-39): N, W, Q = W / N as back_fill leaves it (MCTS.py:254; 0 while
+// N == 0), P, the child node; value = sum W / sum N, both sums in edge order.
+// One wave per board: the edges' lanes note their action's slot in LDS, then
+// lanes are actions and every output row is written once, whole.
+__global__ void __launch_bounds__(kWave) k_root_edges(hz_mcts m, int32_t *__restrict__ n_out, double *__restrict__ w_out,
+                                                      double *__restrict__ q_out, float *__restrict__ p_out,
+                                                      int32_t *__restrict__ child_out,
+                                                      double *__restrict__ value_out) {
+  __shared__ int16_t slot[kActions];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int32_t *cnt = m.counts + (size_t)b * 4;
+  const size_t nb = (size_t)b * m.max_nodes, eb = (size_t)b * m.max_edges;
+  const int n_nodes = cnt[0], n_edges = cnt[1];
+  int e0 = 0;
+  const int ne = checked_counts(m, n_nodes, n_edges) ? checked_edges(m, nb, 0, n_edges, e0) : 0;
+  for (int a = lane; a < kActions; a += kWave) slot[a] = -1;
+  __syncthreads();
+  int n0 = 0, n1 = 0;
+  double w0 = 0.0, w1 = 0.0;
+  if (lane < ne) {
+    const size_t e = eb + e0 + lane;
+    n0 = m.edge_n[e];
+    w0 = m.edge_w[e];
+    const int a = m.edge_action[e];
+    if (a >= 0 && a < kActions) slot[a] = (int16_t)lane;
+  }
+  if (lane + kWave < ne) {
+    const size_t e = eb + e0 + lane + kWave;
+    n1 = m.edge_n[e];
+    w1 = m.edge_w[e];
+    const int a = m.edge_action[e];
+    if (a >= 0 && a < kActions) slot[a] = (int16_t)(lane + kWave);
+  }
+  __syncthreads();
+  for (int a = lane; a < kActions; a += kWave) {
+    const int i = slot[a];
+    int n = 0, child = -1;
+    double w = 0.0, q = 0.0;
+    float p = 0.f;
+    if (i >= 0) {
+      const size_t e = eb + e0 + i;
+      n = m.edge_n[e];
+      w = m.edge_w[e];
+      p = m.edge_p[e];
+      child = m.edge_child[e];
+      q = n ? __ddiv_rn(w, (double)n) : 0.0;
+    }
+    const size_t o = (size_t)b * kActions + a;
+    n_out[o] = n;
+    w_out[o] = w;
+    q_out[o] = q;
+    p_out[o] = p;
+    if (child_out) child_out[o] = child;
+  }
+  if (value_out) {
+    const int sn = wave_sum_i(n0 + n1);
+    double sw = 0.0;
+    for (int i = 0; i < ne; i++) sw = __dadd_rn(sw, __shfl(i < kWave ? w0 : w1, i & (kWave - 1)));
+    if (lane == 0) value_out[b] = sn ? __ddiv_rn(sw, (double)sn) : 0.0;
+  }
+}
+
+// The line the search expects: from the root, the first edge with the most
+// visits (the greedy choice of MCTS.py:418-423 applied at every level), until
+// a node without edges, an edge without visits or max_len moves.  One wave
+// per board, two edges per lane, one (N, index) reduction per level.
+__global__ void __launch_bounds__(kWave) k_pv(hz_mcts m, int max_len, int16_t *__restrict__ action,
+                                              int32_t *__restrict__ visits, double *__restrict__ q,
+                                              uint8_t *__restrict__ player, int32_t *__restrict__ len) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int32_t *cnt = m.counts + (size_t)b * 4;
+  const size_t nb = (size_t)b * m.max_nodes, eb = (size_t)b * m.max_edges, ob = (size_t)b * max_len;
+  const int n_nodes = cnt[0], n_edges = cnt[1];
+  int node = 0, d = 0;
+  if (checked_counts(m, n_nodes, n_edges)) {
+    while (d < max_len && node >= 0 && node < n_nodes) {
+      int e0 = 0;
+      const int ne = checked_edges(m, nb, node, n_edges, e0);
+      if (ne == 0) break;
+      double best = -INFINITY;  // a visit count as a double (exact)
+      int bi = 0x7fffffff;
+      if (lane < ne) {
+        best = (double)m.edge_n[eb + e0 + lane];
+        bi = lane;
+      }
+      if (lane + kWave < ne) {
+        const double v = (double)m.edge_n[eb + e0 + lane + kWave];
+        if (v > best) { best = v; bi = lane + kWave; }
+      }
+      wave_argmax(best, bi);
+      const int nsel = (int)best;
+      if (nsel <= 0) break;
+      const size_t e = eb + e0 + bi;
+      if (lane == 0) {
+        action[ob + d] = m.edge_action[e];
+        visits[ob + d] = nsel;
+        q[ob + d] = __ddiv_rn(m.edge_w[e], (double)nsel);
+        player[ob + d] = m.edge_player[e];
+      }
+      node = m.edge_child[e];
+      d++;
+    }
+  }
+  for (int i = d + lane; i < max_len; i += kWave) {
+    action[ob + i] = -1;
+    visits[ob + i] = 0;
+    q[ob + i] = 0.0;
+    player[ob + i] = 0;
+  }
+  if (lane == 0) len[b] = d;
+}
+
 template <class T>
 bool alloc(T **p, size_t count) {
   return hipMalloc((void **)p, count * sizeof(T)) == hipSuccess;
@@ -1571,6 +1701,39 @@ int hz_mcts_stats(hz_mcts *m, int32_t *counts) {
   return hipMemcpyAsync(counts, m->counts, (size_t)m->n * 4 * sizeof(int32_t), hipMemcpyDeviceToDevice, m->stream)
              ? 1
              : 0;
+}
+
+int hz_mcts_root_edges(hz_mcts *m, int32_t *n, double *w, double *q, float *p, int32_t *child, double *value) {
+  if (!m || !n || !w || !q || !p) return -1;
+  hipLaunchKernelGGL(k_root_edges, dim3(m->n), dim3(kWave), 0, m->stream, *m, n, w, q, p, child, value);
+  return launch_err();
+}
+
+int hz_mcts_pv(hz_mcts *m, int32_t max_len, int16_t *action, int32_t *visits, double *q, uint8_t *player,
+               int32_t *len) {
+  if (!m || max_len < 1 || max_len > m->max_depth || !action || !visits || !q || !player || !len) return -1;
+  hipLaunchKernelGGL(k_pv, dim3(m->n), dim3(kWave), 0, m->stream, *m, max_len, action, visits, q, player, len);
+  return launch_err();
+}
+
+int hz_mcts_export_tree(hz_mcts *m, int32_t b, uint64_t *node_state, int32_t *node_e0, int32_t *node_ne,
+                        int16_t *edge_action, int32_t *edge_child, int32_t *edge_n, double *edge_w, float *edge_p,
+                        uint8_t *edge_player) {
+  if (!m || b < 0 || b >= m->n) return -1;
+  const size_t nb = (size_t)b * m->max_nodes, eb = (size_t)b * m->max_edges, N = m->max_nodes, E = m->max_edges;
+  auto copy = [&](void *dst, const void *src, size_t bytes) {
+    return !dst || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, m->stream) == hipSuccess;
+  };
+  const bool ok = copy(node_state, m->node_state + nb * 6, N * 6 * sizeof(uint64_t)) &&
+                  copy(node_e0, m->node_e0 + nb, N * sizeof(int32_t)) &&
+                  copy(node_ne, m->node_ne + nb, N * sizeof(int32_t)) &&
+                  copy(edge_action, m->edge_action + eb, E * sizeof(int16_t)) &&
+                  copy(edge_child, m->edge_child + eb, E * sizeof(int32_t)) &&
+                  copy(edge_n, m->edge_n + eb, E * sizeof(int32_t)) &&
+                  copy(edge_w, m->edge_w + eb, E * sizeof(double)) &&
+                  copy(edge_p, m->edge_p + eb, E * sizeof(float)) &&
+                  copy(edge_player, m->edge_player + eb, E * sizeof(uint8_t));
+  return ok ? 0 : 1;
 }
 
 #ifdef HZ_DIAG

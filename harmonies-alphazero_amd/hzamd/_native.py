@@ -69,6 +69,9 @@ _SIGS = {
     "hz_root_noise": ([_vp, _c.c_int32, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_double, _vp, _vp, _vp],
                       _c.c_int),
     "hz_mcts_stats": ([_vp, _vp], _c.c_int),
+    "hz_mcts_root_edges": ([_vp] * 7, _c.c_int),
+    "hz_mcts_pv": ([_vp, _c.c_int32] + [_vp] * 5, _c.c_int),
+    "hz_mcts_export_tree": ([_vp, _c.c_int32] + [_vp] * 9, _c.c_int),
     "hz_mcts_leaf_ptrs": ([_vp, _vp, _vp], _c.c_int),
     "hz_mcts_path_edges": ([_vp, _vp], _c.c_int),
     "hz_key_check": ([_vp, _c.c_int32, _vp, _vp], _c.c_int),

@@ -42,8 +42,10 @@ class BatchedMCTS:
         self._graph_cache = None  # (key, captured simulation, network) kept by search(graph=True)
         self._capture_stream = None  # this handle's graph-capture stream (own split-tower counter block)
         self.max_nodes = int(max_nodes or 1 + MAX_CHILDREN * self.num_simulations)
+        self.max_depth = int(max_depth)
+        self._report = {}  # output buffers of root_edges / principal_variation / export_tree, made on first use
         L = nat.lib()
-        self._h = L.hz_mcts_create(self.n, self.max_nodes, int(max_depth), int(bool(exact_keys)),
+        self._h = L.hz_mcts_create(self.n, self.max_nodes, self.max_depth, int(bool(exact_keys)),
                                    nat.stream_ptr(self.device))
         if not self._h:
             raise nat.NativeError("hz_mcts_create failed (out of device memory?)")
@@ -177,6 +179,77 @@ class BatchedMCTS:
     def stats(self):
         nat.check(nat.lib().hz_mcts_stats(self._h, nat.ptr(self.counts)), "hz_mcts_stats")
         return self.counts
+
+    # -- the search report (read-only views of the trees) ---------------------
+    def _zeros(self, dtype, *shape):
+        return torch.zeros(shape, dtype=dtype, device=self.device)
+
+    def root_edges(self, value=True):
+        """The root's edge statistics by action id (hz_mcts_root_edges; the
+        reference's MCTS.get_root_edges, MCTS.py:268-269): device tensors n
+        int32 [n, 143], w f64, q f64 (W / N; 0 while N == 0), p f32 (the prior
+        after the root mix), child int32 (-1: no such edge) and, with value,
+        value f64 [n] = sum W / sum N from the root mover's side.  One launch,
+        no host read; the tensors are the handle's own, rewritten by the next
+        call."""
+        r = self._report.get("root")
+        if r is None:
+            z = self._zeros
+            A = ACTION_SIZE
+            r = self._report["root"] = {
+                "n": z(torch.int32, self.n, A), "w": z(torch.float64, self.n, A), "q": z(torch.float64, self.n, A),
+                "p": z(torch.float32, self.n, A), "child": z(torch.int32, self.n, A), "value": z(torch.float64, self.n)}
+        nat.check(nat.lib().hz_mcts_root_edges(self._h, nat.ptr(r["n"]), nat.ptr(r["w"]), nat.ptr(r["q"]),
+                                               nat.ptr(r["p"]), nat.ptr(r["child"]),
+                                               nat.ptr(r["value"]) if value else None), "hz_mcts_root_edges")
+        return dict(r) if value else {k: v for k, v in r.items() if k != "value"}
+
+    def principal_variation(self, max_len=16):
+        """The line each board's search expects (hz_mcts_pv): at every node
+        the first edge with the most visits, until a node without edges, an
+        edge without visits or max_len moves (1 <= max_len <= max_depth).
+        Device tensors action int16 [n, max_len] (-1 past the end), visits
+        int32, q f64 (the edge's W / N), player uint8 (the edge's mover) and
+        len int32 [n]; the handle's own, rewritten by the next call with the
+        same max_len."""
+        max_len = int(max_len)
+        if not 1 <= max_len <= self.max_depth:
+            raise ValueError(f"max_len {max_len} outside 1..{self.max_depth}")
+        r = self._report.get(("pv", max_len))
+        if r is None:
+            z = self._zeros
+            r = self._report[("pv", max_len)] = {
+                "action": z(torch.int16, self.n, max_len), "visits": z(torch.int32, self.n, max_len),
+                "q": z(torch.float64, self.n, max_len), "player": z(torch.uint8, self.n, max_len),
+                "len": z(torch.int32, self.n)}
+        nat.check(nat.lib().hz_mcts_pv(self._h, max_len, nat.ptr(r["action"]), nat.ptr(r["visits"]), nat.ptr(r["q"]),
+                                       nat.ptr(r["player"]), nat.ptr(r["len"])), "hz_mcts_pv")
+        return dict(r)
+
+    def export_tree(self, b):
+        """Board b's tree as CPU numpy arrays (hz_mcts_export_tree), trimmed
+        to its node and edge counts: state uint64 [nodes, 6], e0 / ne int32
+        [nodes] (a node's first edge and edge count; ne -1: terminal, 0: not
+        expanded), and per edge action int16, child int32, n int32, w f64,
+        p f32, player uint8.  The debugging view: it waits for the device."""
+        b = int(b)
+        if not 0 <= b < self.n:
+            raise IndexError(f"board {b} outside 0..{self.n - 1}")
+        r = self._report.get("tree")
+        if r is None:
+            z = self._zeros
+            m = self.max_nodes
+            r = self._report["tree"] = {
+                "state": z(torch.int64, m, 6), "e0": z(torch.int32, m), "ne": z(torch.int32, m),
+                "action": z(torch.int16, m), "child": z(torch.int32, m), "n": z(torch.int32, m),
+                "w": z(torch.float64, m), "p": z(torch.float32, m), "player": z(torch.uint8, m)}
+        nat.check(nat.lib().hz_mcts_export_tree(self._h, b, *(nat.ptr(r[k]) for k in (
+            "state", "e0", "ne", "action", "child", "n", "w", "p", "player"))), "hz_mcts_export_tree")
+        nodes, edges = (int(x) for x in self.stats()[b, :2].tolist())
+        out = {k: r[k][:nodes].cpu().numpy() for k in ("state", "e0", "ne")}
+        out["state"] = out["state"].view("uint64")
+        out.update({k: r[k][:edges].cpu().numpy() for k in ("action", "child", "n", "w", "p", "player")})
+        return out
 
     # -- one full search per board -------------------------------------------
     def _device_step(self, evaluator, cpuct, active, noise, eps, testing, max_rows=None):

@@ -51,7 +51,7 @@ class NoiseSource:
 
 class SelfPlay:
     def __init__(self, n_boards, evaluator, mcts_config=None, seed_base=0, device="cuda", max_plies=200,
-                 env=None, exact_keys=False):
+                 env=None, exact_keys=False, keep_root_value=False):
         self.cfg = dict(MCTS_DEFAULT, **(mcts_config or {}))
         self.device = torch.device(device)
         self.env = env or BatchedEnv(n_boards, seed_base=seed_base, device=self.device)
@@ -61,6 +61,12 @@ class SelfPlay:
         self.max_plies = int(max_plies)
         self.noise = NoiseSource(seed_base, self.device)
         self.keep_noise = False
+        # keep_root_value: each move() also takes the searches' root value
+        # (BatchedMCTS.root_edges()["value"]: sum W / sum N over the root's
+        # edges, from the root mover's side; one more launch, no host read)
+        # into last_root_value, and play() / play_steady() record it
+        self.keep_root_value = bool(keep_root_value)
+        self.last_root_value = None  # f64 [n] of the last move() (the search handle's buffer), when kept
         self.noise_log = []
         self.step_counter = 0
         # move() holds the host back only after its search is queued: the
@@ -99,6 +105,8 @@ class SelfPlay:
         # an upper bound from an earlier move, so no host read waits here
         v = self.mcts.search(self.evaluator, cfg["cpuct"], active=active, noise=noise,
                              eps=cfg["dirichlet_epsilon"], testing=testing, max_rows=max(1, bound))
+        if self.keep_root_value:
+            self.last_root_value = self.mcts.root_edges()["value"]
         self.check_steps()  # the previous move's step, done long before this search runs
         if torch.is_tensor(ply):
             explore = (ply < cfg["turns_until_tau0"]) & (not testing)
@@ -146,6 +154,7 @@ class SelfPlay:
         players = torch.zeros(T, n, dtype=torch.int8, device=d)
         visits = torch.zeros(T, n, 143, dtype=torch.int32, device=d)
         valid = torch.zeros(T, n, dtype=torch.bool, device=d)
+        root_value = torch.zeros(T, n, dtype=torch.float64, device=d) if self.keep_root_value else None
         done = env.done()
         ply = 0
         while ply < T:
@@ -158,12 +167,17 @@ class SelfPlay:
             players[ply] = ((st[5] >> 41) & 1).to(torch.int8)
             valid[ply] = active
             visits[ply] = v
+            if root_value is not None:
+                root_value[ply] = self.last_root_value
             done = env.done()
             ply += 1
         self.check_steps()
         final = env.export_state()
-        return {"states": states[:ply], "players": players[:ply], "visits": visits[:ply],
-                "valid": valid[:ply], "final": final, "plies": ply}
+        rec = {"states": states[:ply], "players": players[:ply], "visits": visits[:ply],
+               "valid": valid[:ply], "final": final, "plies": ply}
+        if root_value is not None:
+            rec["root_value"] = root_value[:ply]  # f64 [T, n], from the recorded player's side
+        return rec
 
     def play_steady(self, moves, reset=True, progress=None):
         """Continuous self-play: the reference's self_play_worker
@@ -192,11 +206,14 @@ class SelfPlay:
         outcome = torch.zeros(M, n, dtype=torch.float32, device=d)
         plies = torch.zeros(M, n, dtype=torch.int16, device=d)
         none = torch.zeros(n, dtype=torch.bool, device=d)
+        root_value = torch.zeros(M, n, dtype=torch.float64, device=d) if self.keep_root_value else None
         for m in range(M):
             self._n_active, self._n_active_epoch = n, env.epoch
             st, v, _ = self.move(ply, none, _bound=n)
             states[m] = st
             visits[m] = v
+            if root_value is not None:
+                root_value[m] = self.last_root_value
             games[m] = game.to(torch.int32)
             fin = env.export_state()
             over = env.done()
@@ -212,14 +229,18 @@ class SelfPlay:
                 progress(m)
         self.check_steps()
         players = ((states[:, 5] >> 41) & 1).to(torch.int8)
-        return {"states": states, "visits": visits, "players": players, "game": games, "ended": ended,
-                "outcome": outcome, "plies": plies, "moves": M}
+        rec = {"states": states, "visits": visits, "players": players, "game": games, "ended": ended,
+               "outcome": outcome, "plies": plies, "moves": M}
+        if root_value is not None:
+            rec["root_value"] = root_value  # f64 [M, n], from the recorded player's side
+        return rec
 
     def compact_steady(self, rec):
         """play_steady's records of the games that ended inside the run, in
         (move, board) order: as compact() (states, visits, pi, z from the
         recorded player's side, player, board), plus each record's game
-        index, and per ended game its length (`lengths`: plies)."""
+        index, and per ended game its length (`lengths`: plies); with
+        keep_root_value also q f32 [M], as compact()."""
         M, n, d = rec["moves"], self.n, self.device
         game = rec["game"].to(torch.int64)                         # [M, n]
         K = int(game.max().item()) + 1 if M else 1
@@ -236,9 +257,12 @@ class SelfPlay:
         states = rec["states"].permute(0, 2, 1)[mask]
         visits = rec["visits"][mask]
         board_id = torch.arange(n, device=d).expand(M, n)[mask].to(torch.int32)
-        return {"states": states.contiguous(), "visits": visits, "pi": pi_from_visits(visits),
+        comp = {"states": states.contiguous(), "visits": visits, "pi": pi_from_visits(visits),
                 "z": z[mask].contiguous(), "player": rec["players"][mask], "board": board_id,
                 "game": game[mask].to(torch.int32), "lengths": rec["plies"][em].to(torch.int64)}
+        if "root_value" in rec:
+            comp["q"] = rec["root_value"][mask].to(torch.float32)
+        return comp
 
     @staticmethod
     def outcomes(final):
@@ -249,7 +273,9 @@ class SelfPlay:
     def compact(self, rec):
         """Flatten the valid records: states int64 [M, 6], visits int32
         [M, 143], pi f32 [M, 143], z f32 [M] (trainer.py:517-538), player
-        int8 [M], board id int32 [M]."""
+        int8 [M], board id int32 [M]; from records kept with keep_root_value
+        also q f32 [M], the search's root value from the recorded player's
+        side like z (the recorded player is the root's mover)."""
         out = self.outcomes(rec["final"])                       # [n]
         T = rec["plies"]
         mask = rec["valid"]                                      # [T, n]
@@ -259,8 +285,11 @@ class SelfPlay:
         visits = rec["visits"][mask]
         pi = pi_from_visits(visits)                              # [M, 143]
         board_id = torch.arange(self.n, device=self.device).expand(T, self.n)[mask].to(torch.int32)
-        return {"states": states.contiguous(), "visits": visits, "pi": pi, "z": z[mask].contiguous(),
+        comp = {"states": states.contiguous(), "visits": visits, "pi": pi, "z": z[mask].contiguous(),
                 "player": rec["players"][mask], "board": board_id}
+        if "root_value" in rec:
+            comp["q"] = rec["root_value"][mask].to(torch.float32)
+        return comp
 
     def iteration(self, buffer=None, group=None, timings=None):
         """One self-play phase: every board plays a game; with torch.distributed

@@ -305,6 +305,44 @@ int hz_root_noise(const int32_t *count, int32_t n, uint64_t seed, uint64_t board
 int hz_mcts_result(hz_mcts *mcts, int32_t *visits);
 /* per-board [nodes, edges, search generation, overflow flag] -> counts[n][4] */
 int hz_mcts_stats(hz_mcts *mcts, int32_t *counts);
+/* ---- search report: three read-only views of the trees ---------------------
+ * None writes the tree, the env or the streams; each is enqueued on the
+ * handle's stream without synchronising, can be captured in a HIP graph, and
+ * is valid at any point between the calls of a search once hz_mcts_begin has
+ * run (before it every board reads as left out).  Node and edge ids read from
+ * the tree are checked against the board's counts before they are used. */
+/* MCTS.get_root_edges (MCTS.py:268-269) by action id, what Edge.stats holds
+ * (MCTS.py:34-39): n[n][143] (equals hz_mcts_result), w[n][143] the stored
+ * fp64 W, q[n][143] = W / N as back_fill's last update left it (MCTS.py:254,
+ * one fp64 division; 0.0 while N == 0), p[n][143] the stored fp32 prior (the
+ * root's after the Dirichlet mix, MCTS.py:323), child[n][143] (may be NULL)
+ * the edge's child node id, value[n] (may be NULL) = sum W / sum N over the
+ * root's edges, both sums taken in ascending edge order in fp64 (0.0 when
+ * sum N is 0), from the root mover's side.  An action without a root edge
+ * (illegal, a skipped self-loop child of MCTS.py:189-194, a board left out of
+ * the search, a stuck, terminal or unexpanded root) gets 0, 0.0, 0.0, 0.0 and
+ * child -1. */
+int hz_mcts_root_edges(hz_mcts *mcts, int32_t *n, double *w, double *q, float *p, int32_t *child, double *value);
+/* The principal variation: from the root, at every node the edge with the
+ * most visits, the first in edge (= ascending action) order among equals, as
+ * the greedy move choice of MCTS.py:418-423 picks at the root; the line ends
+ * at a node without edges, at an edge with N == 0, at a link outside the
+ * board's tree, or after max_len moves (1 <= max_len <= the handle's
+ * max_depth, else -1).  action[n][max_len], visits[n][max_len] (the edge's
+ * N), q[n][max_len] (its W / N), player[n][max_len] (its mover,
+ * Edge.current_player MCTS.py:29-31), len[n]; entries at and past len[b] are
+ * -1, 0, 0.0 and 0. */
+int hz_mcts_pv(hz_mcts *mcts, int32_t max_len, int16_t *action, int32_t *visits, double *q, uint8_t *player,
+               int32_t *len);
+/* Board b's whole node and edge slices (Node MCTS.py:8-20, Edge :23-39),
+ * copied in stream order into device buffers of max_nodes entries each (any
+ * may be NULL): node_state[max_nodes][6], node_e0 / node_ne (a node's first
+ * edge and edge count; ne = -1 marks a terminal node, 0 an unexpanded one);
+ * per edge its action, child node, N, W, P and mover.  Entries past the
+ * board's node / edge counts (hz_mcts_stats) are stale: the caller trims. */
+int hz_mcts_export_tree(hz_mcts *mcts, int32_t b, uint64_t *node_state, int32_t *node_e0, int32_t *node_ne,
+                        int16_t *edge_action, int32_t *edge_child, int32_t *edge_n, double *edge_w, float *edge_p,
+                        uint8_t *edge_player);
 /* out[0] (device int64) += the sum of every edge's visit count over every
  * board's current tree, i.e. the edge levels its simulations walked (each
  * back_fill, MCTS.py:220-266, visits every edge of its path once): the
