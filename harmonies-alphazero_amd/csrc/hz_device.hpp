@@ -680,18 +680,23 @@ __device__ __forceinline__ void mt_seed_tab(uint32_t *w, const uint32_t *tab, ui
 }
 
 // A board's stream in global memory with a runtime word stride (a pipeline-2
-// stream slot, word-major: stride = the slot's row length).  As MTS.
+// stream slot, word-major: stride = the slot's row length).  Read-only: a
+// slot holds the next generation's rows below its cursor's tw and nothing
+// that a twist past them could start from, so the stream never twists.  Rows
+// [0, lim) are read (the caller's lim <= tw); from row lim on next() returns words that
+// keep changing (as WinMT's, so no rejection loop spins for ever) and the
+// caller discards the game: over() says that a draw consumed such a word.
 struct MTR {
   uint32_t* w;
-  int stride, pos, tw;
-  __device__ __forceinline__ MTR(uint32_t* words, int s, int cursor)
-      : w(words), stride(s), pos(cursor & 0xFFFF), tw(cursor >> 16) {}
+  int stride, pos, tw, lim;
+  __device__ __forceinline__ MTR(uint32_t* words, int s, int cursor, int limit)
+      : w(words), stride(s), pos(cursor & 0xFFFF), tw(cursor >> 16), lim(limit) {}
   __device__ __forceinline__ int cursor() const { return pos | (tw << 16); }
+  __device__ __forceinline__ bool over() const { return pos > lim; }
   __device__ __forceinline__ void prefetch() {}
   __device__ __forceinline__ uint32_t next() {
-    if (pos >= kMT) { pos = 0; tw = 0; }
-    if (pos >= tw) tw += twist_block(w, stride, tw);
-    return temper(w[(size_t)(pos++) * stride]);
+    const int i = pos++;
+    return i < lim ? temper(w[(size_t)i * stride]) : 0x9E3779B9u * (uint32_t)(i + 1);
   }
 };
 

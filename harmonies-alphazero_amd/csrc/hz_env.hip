@@ -120,6 +120,7 @@ struct hz_env {
   int calls2, primed2;
   int p2_cut[kP2Play - 1];   // the play stages' ply boundaries (HZ_P2_CUTS5)
   int p2_dcut[kP2Draw + 1];  // the draw stages' first draws (HZ_P2_DCUTS); [0] = 0, [kP2Draw] = kAheadDraws
+  int p2_fell_lim;           // slot rows a play stage may draw from past its script (HZ_P2_FELL_LIMIT)
   uint32_t *p2_s[kP2Stream];     // [624][nrow] stream slots
   int32_t *p2_s_tag[kP2Stream];  // [nrow] episode * 8 + 3 P2a / 4 P2b / 5 seeded, rows 0-223 twisted (-1: none)
   int32_t *p2_s_cur[kP2Stream];  // [kAheadDraws + 1][nrow] the slot's cursor before draw 0 and after each draw
@@ -656,12 +657,9 @@ static int materialize(hz_env *e) {
     hipLaunchKernelGGL(k_mt_materialize_ar, dim3(e->n), dim3(64), 0, e->stream, e->mt, e->ar_mt, e->mt_src, e->n);
   hipLaunchKernelGGL(k_mt_materialize, dim3(e->n), dim3(64), 0, e->stream, e->mt, e->ahead_mt[0], e->ahead_mt[1],
                      e->mt_src, e->n);
-  if (e->p2_s[0]) {
-    P2Slots sl;
-    for (int k = 0; k < kP2Stream; k++) sl.s[k] = e->p2_s[k];
-    hipLaunchKernelGGL(k_mt_materialize2, dim3(e->n), dim3(64), 0, e->stream, e->mt, sl, e->mt_src,
-                       (long)e->nrow);
-  }
+  if (e->p2_s[0])
+    hipLaunchKernelGGL(k_mt_materialize2, dim3(grid_for(e->n)), dim3(kStageThreads), kResetLds, e->stream, e->mt,
+                       e->seed, e->pos, e->mt_src, e->n);
   e->lazy = 0;
   return launch_err();
 }
@@ -763,6 +761,7 @@ static int launch_play2(hz_env *e, int32_t max_plies, int32_t *games_done, int32
   a.draws = e->seed_ahead;
   a.err = e->wait_err;
   a.spin = e->spin_limit;
+  a.fell_lim = e->p2_fell_lim;
   for (int k = 0; k < kP2Play - 1; k++) a.cut[k] = e->p2_cut[k];
   for (int k = 0; k <= kP2Draw; k++) a.dcut[k] = e->p2_dcut[k];
   a.seed_base = e->seed_base;
@@ -823,7 +822,8 @@ hz_env *hz_env_create(int32_t n_boards, uint64_t seed_base, void *stream) {
   // k_reset / k_rollout stage 64 boards' MT words in 158 KiB of LDS
   if (lds_opt_in<k_reset>(kResetLds) || lds_opt_in<k_rollout<false, false>>(kResetLds) ||
       lds_opt_in<k_rollout<false, true>>(kResetLds) || lds_opt_in<k_rollout<true, false>>(kResetLds) ||
-      lds_opt_in<k_rollout<true, true>>(kResetLds) || lds_opt_in<k_play2>(kResetLds))
+      lds_opt_in<k_rollout<true, true>>(kResetLds) || lds_opt_in<k_play2>(kResetLds) ||
+      lds_opt_in<k_mt_materialize2>(kResetLds))
     return nullptr;
   hz_env *e = new (std::nothrow) hz_env();
   if (!e) return nullptr;
@@ -881,6 +881,11 @@ hz_env *hz_env_create(int32_t n_boards, uint64_t seed_base, void *stream) {
         cuts_gaps_within(dc, kP2Draw + 1, kP2StageDraws))
       for (int k = 0; k <= kP2Draw; k++) e->p2_dcut[k] = dc[k];
   }
+  // HZ_P2_FELL_LIMIT: the slot rows a play stage may draw from once its
+  // script has run out (a slot holds kP2Twist; a game that needs more is
+  // played again from scratch by the last play stage).  Lower values only
+  // force that path (tests).
+  e->p2_fell_lim = env_clamped("HZ_P2_FELL_LIMIT", kP2Twist, 0, kP2Twist);
   e->wait_err = e->wait_err_own;
   e->spin_limit = kSpinLimitDefault;
   if (!o.ok || hipDeviceSynchronize() != hipSuccess) {

@@ -1,5 +1,5 @@
 // hz_play2.hpp — k_play2, hz_play's second pipeline, and the kernel that
-// copies a board's stream out of its slots.  Part of hz_env.hip's translation
+// rebuilds a board's own stream after it.  Part of hz_env.hip's translation
 // unit (included by it alone, after hz_chance.hpp and hz_rollout.hpp; P2Draw,
 // P2Mid and the kP2* stage counts sit with struct hz_env, which is sized by
 // them).
@@ -19,11 +19,15 @@ namespace {
 // kP2Wave's (HZ_P2_WAVES); by default:
 //   s = 0  P1    seeding pass 1, all 624 steps, in     draw-Y blocks, wave 2
 //                registers: only its last word leaves
-//   s = 1  P2a   pass 2, steps 2-208                  seed blocks, wave 0
-//   s = 2  P2b   pass 2, steps 209-432                seed blocks, wave 1
-//   s = 3  P2c   pass 2, steps 433-624; rows 0-223    seed blocks, wave 2
-//                of the next generation twisted       (twist: wave 3)
-//   s = 4  D1    pile draws [dcut0 = 0, dcut1)        draw-X blocks, wave 0
+//   s = 1  P2a   pass 2, steps 2-208: stores the      seed blocks, wave 0
+//                twist parts of rows 2-161
+//   s = 2  P2b   pass 2, steps 209-432: stores rows   seed blocks, wave 1
+//                393-432
+//   s = 3  P2c   pass 2, steps 433-624, rows 433-560  seed blocks, wave 2
+//                kept in LDS; rows 0-159 of the next  (twist: wave 3)
+//                generation twisted
+//   s = 4  D1    pile draws [dcut0 = 0, dcut1), from  draw-X blocks, wave 0
+//                slot rows [L, L + 96), L = 3 dcut & ~3
 //   s = 5  D2    draws [dcut1, dcut2)                 draw-X blocks, wave 1
 //   s = 6  D3    draws [dcut2, dcut3)                 draw-Y blocks, wave 0
 //   s = 7  D4    draws [dcut3, dcut4)                 draw-Y blocks, wave 1
@@ -43,8 +47,14 @@ namespace {
 // pass 1's word at the row before its range: one step from the constants for
 // P2a, handed on with pass 2's value for P2b and P2c.
 // An episode's stream lives in one slot of a ring of kP2Stream from P2a to
-// playE (and afterwards as the board's current stream until materialize or
-// the next call); stage s >= 1 of call c uses slot (c - s) mod kP2Stream.  A
+// playE; stage s >= 1 of call c uses slot (c - s) mod kP2Stream.  A slot
+// holds what the stages read and no more: the next generation's rows below
+// kP2Twist (the draw stages' windows, a play stage past its script) and, on
+// the way there, the twist's inputs (the parts of those rows, the old
+// generation's rows 397 .. kP2bEnd - 1).  Nothing else of pass 2 reaches
+// memory.  A game that would read past row kP2Twist is played again from
+// scratch by playE, and the board's own stream, when another entry point
+// needs it, is rebuilt from the episode's seed (k_mt_materialize2).  A
 // stage uses an input only when its tag names the stage's episode, so a wrong
 // prediction costs time, never results: the stages skip the board and playE
 // plays its whole game from scratch (seeding and drawing in LDS, like
@@ -68,7 +78,12 @@ namespace {
 // (profiles/r05/p2_writethrough; A/B builds -DHZ_P2_AUX=0 / 2)
 #define HZ_P2_AUX 16
 #endif
-constexpr int kP2Win = 96;        // rows a draw stage stages, from its wave's lowest cursor
+#ifndef HZ_P2_STATIC_WIN
+#define HZ_P2_STATIC_WIN 1
+#endif
+constexpr bool kP2StaticWin = HZ_P2_STATIC_WIN;
+
+constexpr int kP2Win = 96;        // rows a draw stage stages, from row (3 dcut[stage]) & ~3 (p2_draw_stage)
 constexpr int kP2WinRows = kP2Win + 24;  // LDS rows per window (a scan reads up to 23 rows past its cursor)
 #ifndef HZ_P2_DCUT
 // the draw stages' first draws (run time: HZ_P2_DCUTS).  Later draws take
@@ -84,11 +99,13 @@ constexpr int kP2WinRows = kP2Win + 24;  // LDS rows per window (a scan reads up
 #endif
 #endif
 constexpr int kP2DCut[kP2Draw] = {HZ_P2_DCUT};
-// A draw stage's window holds kP2Win rows from its wave's lowest cursor.
+// A draw stage's window holds kP2Win rows from row (3 dcut[stage]) & ~3.
 // Seven draws (the most a stage ever had) use at most ~60 words (eight
 // consecutive draws: 67 over 20,000 seeds), which leaves room for the
-// spread of the wave's cursors; a stage of twenty overruns the window for
-// about one board in twenty, every time at the cost of the draws discarded.
+// cursors' spread at the stage's start: over 1,000,000 simulated streams
+// with the default cuts no stage's last draw ended past its window
+// (tests/test_p2_windows_cpu.py).  A draw that does is discarded and redone
+// by a later stage: time, never results.
 constexpr int kP2StageDraws = 7;
 #ifndef HZ_P2_PCUT
 // the play stages' ply boundaries (run time: HZ_P2_CUTS5; four stages:
@@ -181,19 +198,24 @@ struct P2Args {
   const int32_t *ht_r[kP2Play];
   int32_t *err;                   // the env's wait-error word
   int spin;                       // spin bound of the twist wave's waits
+  int fell_lim;                   // slot rows a play stage may draw from (HZ_P2_FELL_LIMIT; at most kP2Twist)
 };
 
 // PlayDraw for the prepared stages: the pile script in registers, then (a
-// script shorter than the game needs) the episode's stream slot in HBM
+// script shorter than the game needs) the episode's stream slot in HBM: its
+// next-generation rows below fell_lim (at most kP2Twist, all a slot
+// holds).  A game that would draw past them is lost(): the stage voids its
+// hand-off and the last play stage plays the board's game from scratch.
 struct PlayDraw2 : PileScript {
   bool fell;
   MTR gm;                  // valid once fell
   const int32_t *cur_nd;   // the slot's cursor after the last scripted draw (read when the script runs out)
   __device__ __forceinline__ bool pair_pops() const { return d + 2 <= nd; }
+  __device__ __forceinline__ bool lost() const { return fell && gm.over(); }
   __device__ __forceinline__ uint32_t draw_one(uint64_t misc) {
     if (d < nd) return pop();
     if (!fell) {
-      gm = MTR(gm.w, gm.stride, *cur_nd);
+      gm = MTR(gm.w, gm.stride, *cur_nd, gm.lim);
       fell = true;
     }
     uint32_t p9;
@@ -383,9 +405,10 @@ __device__ __forceinline__ void p2_p1(const P2Args &a, int b) {
 // them from the stream slot (staged into LDS first: an HBM round trip per
 // step is far too slow); now each recomputes pass 1 over its own rows, a
 // group of eight ahead of its pass-2 chain, so the two recurrences are
-// independent instruction streams and interleave.  Each final word goes to
-// the slot with a buffer store (the row offset a scalar: no address
-// arithmetic in the chain).  The chain is cut into thirds rather than made
+// independent instruction streams and interleave.  A word that a later
+// stage reads goes to the slot with a buffer store (the row offset a scalar:
+// no address arithmetic in the chain); the others are not stored at all
+// (HZ_P2_LEAN, kP2None).  The chain is cut into thirds rather than made
 // cheaper per step.
 #ifndef HZ_P2_BEND
 // P2b's end (A/B builds: 225 + 8 k).  The twist follows P2c's progress and
@@ -395,8 +418,41 @@ __device__ __forceinline__ void p2_p1(const P2Args &a, int b) {
 // reads from P2c's LDS rows as they appear.
 #define HZ_P2_BEND 433
 #endif
-constexpr int kP2aEnd = 209, kP2bEnd = HZ_P2_BEND;
+#ifndef HZ_P2_AEND
+#define HZ_P2_AEND 209  // P2a's end (A/B builds: 209 - 8 k)
+#endif
+#ifndef HZ_P2_LEAN
+// 1: pass 2 stores only the rows a later stage reads.  The old generation's
+// rows 225-396 (P2b) and P2c's rows in HBM had two readers, materialize and a
+// play stage twisting past row kAheadTwist; the first now rebuilds a stream
+// from its seed and the second is gone (MTR), so 0 is only the A/B build that
+// still issues the stores.
+#define HZ_P2_LEAN 1
+#endif
+#ifndef HZ_P2_TWIST
+// The next-generation rows a slot gets, [0, kP2Twist): the twist makes no
+// more, P2a and P2b store no twist part past them, and P2c keeps in LDS only
+// the far rows below kP2Twist + 397.  The draw stages' windows end at row 152
+// with the default cuts, and of 26,214,400 rule games (boards 0-4095, episodes
+// 0-6399: tools/p2_fell_count.py) the longest read 134 words; a game that
+// would read past row kP2Twist is played again from scratch (PlayDraw2), so
+// the value decides time, never results.  A multiple of 8, at most
+// kAheadTwist (which it was).
+#define HZ_P2_TWIST 160
+#endif
+constexpr int kP2Twist = HZ_P2_TWIST;
+constexpr int kP2Ahead = 0 | (kP2Twist << 16);  // a slot's cursor before its first draw
+static_assert(kP2Twist % 8 == 0 && kP2Twist >= 64 && kP2Twist <= kAheadTwist, "the slot's twisted rows");
+constexpr int kP2PartEnd = HZ_P2_LEAN ? kP2Twist + 1 : kAheadTwist + 1;  // steps [3, kP2PartEnd) store the previous row's twist part
+constexpr int p2_up8(int from, int x) { return x <= from ? from : from + 8 * ((x - from + 7) / 8); }
+constexpr int p2_min(int a, int b) { return a < b ? a : b; }
+constexpr int kP2aEnd = HZ_P2_AEND, kP2bEnd = HZ_P2_BEND;
 static_assert(kP2bEnd > 399 && kP2bEnd + 64 < kMT && (kP2bEnd - kAheadTwist - 1) % 8 == 0, "P2b's final steps in groups of eight; rows 397, 398 P2b's");
+static_assert(kP2aEnd > 11 && kP2aEnd <= kAheadTwist - 7 && (kAheadTwist + 1 - kP2aEnd) % 8 == 0, "P2b's part steps in groups of eight");
+// P2b's final steps [kAheadTwist + 1, kP2bDrop) store nothing: whole groups
+// below row 397, the first row the twist reads as a far row (the group that
+// holds row 397 stores its rows from 393 on)
+constexpr int kP2bDrop = HZ_P2_LEAN ? kAheadTwist + 1 + 8 * ((397 - kAheadTwist - 1) / 8) : kAheadTwist + 1;
 // pass 1 a group ahead of pass 2, at row g
 struct P2Ahead {
   uint32_t cur[8];  // pass 1's words of rows [g, g + 8)
@@ -437,9 +493,13 @@ __device__ __forceinline__ uint32_t twist_part(uint32_t cur, uint32_t next) {
   return (y >> 1) ^ ((next & 1U) ? 0x9908b0dfU : 0U);
 }
 // What a pass-2 step stores: its final word to its row (kP2Final), the same
-// and to the row in LDS (kP2Keep, P2c), or the previous row's twist part
-// (kP2Part: rows 2-223, which only the twist reads)
-enum { kP2Final = 0, kP2Keep = 1, kP2Part = 2 };
+// and to the row in LDS (kP2Keep), the previous row's twist part (kP2Part:
+// rows 2 .. kP2Twist - 1, which only the twist reads), the row in LDS only (kP2KeepLds,
+// P2c: the twist reads its rows there), or nothing (kP2None: rows no stage
+// reads; the loop then has no store, no row offset and no use of vo[])
+enum { kP2Final = 0, kP2Keep = 1, kP2Part = 2, kP2KeepLds = 3, kP2None = 4 };
+constexpr bool p2_mode_lds(int m) { return m == kP2Keep || m == kP2KeepLds; }
+constexpr bool p2_mode_hbm(int m) { return m == kP2Final || m == kP2Keep || m == kP2Part; }
 // A stage's store addresses, made once: the slot's buffer, the byte offsets
 // of the lane's column in eight consecutive rows (a store's voffset; the
 // group's first row is its scalar offset: one scalar instruction per group of
@@ -470,7 +530,7 @@ struct P2Out {
 // address per group, the group's rows at immediate offsets.
 template <int G0, int G1, int Mode>
 __device__ __forceinline__ void p2_span(ConstWord *tab, const P2Out &o, uint32_t &prev, P2Ahead &h, uint32_t kA, uint32_t kB, int *prog) {
-  constexpr bool KeepLds = Mode == kP2Keep;
+  constexpr bool KeepLds = p2_mode_lds(Mode), Hbm = p2_mode_hbm(Mode);
   static_assert((G1 - G0) % 8 == 0, "groups of eight");
   static_assert(G1 + 15 < kMT + kInitGenPad, "the table's read-ahead within its padding");
   constexpr int S = kLdsStride;
@@ -481,7 +541,8 @@ __device__ __forceinline__ void p2_span(ConstWord *tab, const P2Out &o, uint32_t
 #pragma unroll
     for (int u = 0; u < 8; u++) ivn[u] = tab[g + 16 + u];
     const uint32_t kneg = __builtin_amdgcn_readfirstlane(0u - (uint32_t)g);
-    const int soff = __builtin_amdgcn_readfirstlane((Mode == kP2Part ? g - 1 : g) * o.row_bytes);
+    [[maybe_unused]] int soff = 0;
+    if constexpr (Hbm) soff = __builtin_amdgcn_readfirstlane((Mode == kP2Part ? g - 1 : g) * o.row_bytes);
     if (KeepLds) asm volatile("" : "+v"(lg));  // (one register for the group, not an address per row)
     uint32_t q = h.cur[7];
 #pragma unroll
@@ -490,7 +551,7 @@ __device__ __forceinline__ void p2_span(ConstWord *tab, const P2Out &o, uint32_t
       const uint32_t p = (prev ^ (prev >> 30)) * 1566083941U;
       uint32_t v;
       asm("v_xad_u32 %0, %1, %2, %3" : "=v"(v) : "v"(p), "v"(h.cur[u]), "s"(kneg - (uint32_t)u));
-      o.put(Mode == kP2Part ? twist_part(prev, v) : v, soff, u);
+      if constexpr (Hbm) o.put(Mode == kP2Part ? twist_part(prev, v) : v, soff, u);
       if (KeepLds) *(LdsWord *)(uintptr_t)(lg + u * S * 4) = v;
       prev = v;
       // pass 1, row g + 8 + u (the parity of G0 + u: g - G0 is a multiple of 8)
@@ -513,12 +574,12 @@ __device__ __forceinline__ void p2_span(ConstWord *tab, const P2Out &o, uint32_t
 template <int G, int G1, int Mode>
 __device__ __forceinline__ void p2_tail(const P2Out &o, int lane, uint32_t &prev, P2Ahead &h) {
   static_assert(G1 - G >= 1 && G1 - G <= 8, "within the group ahead");
-  const int soff = __builtin_amdgcn_readfirstlane((Mode == kP2Part ? G - 1 : G) * o.row_bytes);
+  [[maybe_unused]] const int soff = __builtin_amdgcn_readfirstlane((Mode == kP2Part ? G - 1 : G) * o.row_bytes);
 #pragma unroll
   for (int i = G; i < G1; i++) {
     const uint32_t v = (h.cur[i - G] ^ ((prev ^ (prev >> 30)) * 1566083941U)) - (uint32_t)i;
-    o.put(Mode == kP2Part ? twist_part(prev, v) : v, soff, i - G);
-    if (Mode == kP2Keep) hz_lds[i * kLdsStride + lane] = v;
+    if constexpr (p2_mode_hbm(Mode)) o.put(Mode == kP2Part ? twist_part(prev, v) : v, soff, i - G);
+    if (p2_mode_lds(Mode)) hz_lds[i * kLdsStride + lane] = v;
     prev = v;
   }
   h.last = h.cur[G1 - G - 1];
@@ -528,7 +589,7 @@ __device__ __forceinline__ void p2_tail(const P2Out &o, int lane, uint32_t &prev
 // completed in the previous call; P2b (wave 1) the next older; P2c (wave 2,
 // with wave 3's twist) the one before.  Each hands (prev, pass 1's row-1
 // word, row 2's final word, pass 1's word of its last row) to the next.
-// Rows 2-223 of the slot are read
+// Rows 2 .. kP2Twist - 1 of the slot are read
 // only by the twist, which needs from each row r only its twist part
 // (rows r and r + 1's words): P2a and P2b store that instead of the final
 // word (one step late, when row r + 1 is known), so the twist is one xor
@@ -571,23 +632,31 @@ __device__ __forceinline__ void p2_third(const P2Args &a, int b0, int lane, int 
     row2 = (q ^ ((prev ^ (prev >> 30)) * 1566083941U)) - 2U;
     prev = row2;
     p2_ahead_init<3>(tab, h, q, kA, kB);
-    constexpr int G = 3 + 8 * ((kP2aEnd - 3) / 8);
-    p2_span<3, G, kP2Part>(tab, o, prev, h, kA, kB, s_prog);  // parts of rows 2 ..
-    p2_tail<G, kP2aEnd, kP2Part>(o, lane, prev, h);             // .. 207
+    constexpr int G = 3 + 8 * ((kP2aEnd - 3) / 8), Gp = p2_min(G, p2_up8(3, kP2PartEnd));
+    p2_span<3, Gp, kP2Part>(tab, o, prev, h, kA, kB, s_prog);  // parts of rows 2 .. (whole groups: a few past kP2Twist)
+    p2_span<Gp, G, kP2None>(tab, o, prev, h, kA, kB, s_prog);
+    p2_tail<G, kP2aEnd, (G < kP2PartEnd ? kP2Part : kP2None)>(o, lane, prev, h);
   } else if constexpr (K == 1) {
-    static_assert(kAheadTwist + 1 - kP2aEnd == 16, "P2b's part steps: two groups");
     p2_ahead_init<kP2aEnd>(tab, h, q, kA, kB);
-    p2_span<kP2aEnd, kAheadTwist + 1, kP2Part>(tab, o, prev, h, kA, kB, s_prog);  // parts of rows 208-223
-    __builtin_amdgcn_raw_buffer_store_b32(prev, rs, lane * 4, kAheadTwist * row_bytes, HZ_P2_AUX);  // row 224's final word
-    p2_span<kAheadTwist + 1, kP2bEnd, kP2Final>(tab, o, prev, h, kA, kB, s_prog);
+    constexpr int E1 = kAheadTwist + 1, Pb = p2_min(E1, p2_up8(kP2aEnd, kP2PartEnd));
+    p2_span<kP2aEnd, Pb, kP2Part>(tab, o, prev, h, kA, kB, s_prog);  // the parts P2a left to do, if any
+    p2_span<Pb, E1, kP2None>(tab, o, prev, h, kA, kB, s_prog);
+    if constexpr (!HZ_P2_LEAN)  // row 224's final word
+      __builtin_amdgcn_raw_buffer_store_b32(prev, rs, lane * 4, kAheadTwist * row_bytes, HZ_P2_AUX);
+    p2_span<E1, kP2bDrop, kP2None>(tab, o, prev, h, kA, kB, s_prog);
+    p2_span<kP2bDrop, kP2bEnd, kP2Final>(tab, o, prev, h, kA, kB, s_prog);
   } else {
     // rows 0 and 1 of the next generation are P2c's own last words: their
     // far rows (397, 398: P2b's) loaded now, used after the chain
     const uint32_t f0 = act ? slot[(size_t)397 * nr + b] : 0u, f1 = act ? slot[(size_t)398 * nr + b] : 0u;
     p2_ahead_init<kP2bEnd>(tab, h, q, kA, kB);
     constexpr int G = kP2bEnd + 8 * ((kMT - kP2bEnd) / 8);
-    p2_span<kP2bEnd, G, kP2Keep>(tab, o, prev, h, kA, kB, s_prog);
-    p2_tail<G, kMT, kP2Keep>(o, lane, prev, h);
+    constexpr int Keep = HZ_P2_LEAN ? kP2KeepLds : kP2Keep;
+    // (the twist's far rows end below row kP2Twist + 397: the steps past them are the bare chain)
+    constexpr int Kc = HZ_P2_LEAN ? p2_min(G, p2_up8(kP2bEnd, kP2Twist + 397)) : G;
+    p2_span<kP2bEnd, Kc, Keep>(tab, o, prev, h, kA, kB, s_prog);
+    p2_span<Kc, G, kP2None>(tab, o, prev, h, kA, kB, s_prog);
+    p2_tail<G, kMT, (Kc == G ? Keep : kP2None)>(o, lane, prev, h);
     p2_publish(s_prog, kMT);
     const uint32_t row1 = (first1 ^ ((prev ^ (prev >> 30)) * 1566083941U)) - 1U;  // the last step, at i = 1
     // mt[0] = 0x80000000 after init_by_array; row 1's next row is row 2
@@ -608,8 +677,8 @@ __device__ __forceinline__ void p2_third(const P2Args &a, int b0, int lane, int 
   }
 }
 
-// The twist (seed blocks, wave 3): rows [0, kAheadTwist) of the next
-// generation into P2c's slot (the stream at cursor kMTAhead): row r's new
+// The twist (seed blocks, wave 3): rows [0, kP2Twist) of the next
+// generation into P2c's slot (the stream at cursor kP2Ahead): row r's new
 // word is the far row r + 397 (P2b's below row kP2bEnd, from HBM; P2c's from
 // LDS) xor row r's twist part, which P2a and P2b left in the slot (rows
 // 2-223).  Lane: four boards, rows grp + 4 i, grp = lane / 16, so iteration
@@ -620,7 +689,11 @@ __device__ __forceinline__ void p2_third(const P2Args &a, int b0, int lane, int 
 // stores.  (Before the parts, the wave shuffled each row's
 // successor in from the next lane group and ran at ~350 cycles per
 // iteration, ending ~8 k cycles after P2c: profiles/r04/p2/.)
-constexpr int kTwIters = kAheadTwist / 4;
+#ifndef HZ_P2_TWGO
+#define HZ_P2_TWGO 64  // rows of P2c the twist waits for before its loads (A/B builds; < 0: none)
+#endif
+constexpr int kTwGo = HZ_P2_TWGO;
+constexpr int kTwIters = kP2Twist / 4;
 constexpr int kTwHbm = (kP2bEnd - 397 + 3) / 4;  // iterations whose rows r + 397 are P2b's (HBM)
 __device__ __forceinline__ uint4 xor4(const uint4 &a, const uint4 &b) {
   return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w);
@@ -644,7 +717,7 @@ __device__ __forceinline__ void p2_twist(const P2Args &a, int b0, int lane, bool
   // (the wave has ~16 k cycles of slack: its 4 MB of loads wait until P2c is
   // 64 rows in, out of the launch's opening burst, where every other
   // stage's inputs arrive)
-  int have = p2_wait(s_prog, kP2bEnd + 64, a.spin, a.err);
+  int have = kTwGo >= 0 ? p2_wait(s_prog, kP2bEnd + kTwGo, a.spin, a.err) : 0;
   P2_PHASE(35, tz);
   uint4 pt[kTwIters], fh[kTwHbm];
 #pragma unroll
@@ -673,7 +746,7 @@ __device__ __forceinline__ void p2_twist(const P2Args &a, int b0, int lane, bool
     if (i == 0) P2_PHASE(36, tz);
   }
   P2_PHASE(37, tz);
-  // (rows 224..623 keep pass 2's words: the current generation's tail)
+  // (the old generation's rows are not in the slot: k_mt_materialize2 rebuilds a board's stream)
 }
 
 // seed blocks: waves 0-2 P2a, P2b, P2c; wave 3 the twist of P2c's episode
@@ -717,7 +790,7 @@ __device__ __forceinline__ void p2_draw_stage(const P2Args &a, int b0, int lane,
   const P2Draw &in = a.x_r[stage > 0 ? stage - 1 : 0];
   const P2Draw &out = stage == kP2Draw - 1 ? a.pl_w : a.x_w[stage < kP2Draw - 1 ? stage : 0];
   bool ok = act && a.s_tag[kP2SDraw + stage][b] == e * 8 + 5;
-  int k0 = 0, c0 = kMTAhead;
+  int k0 = 0, c0 = kP2Ahead;
   uint64_t bag = initial_bag(), q[kAheadWords] = {0, 0, 0, 0};
   // the window: rows [r0, r0 + kP2Win), 16-B loads (four boards of a row per
   // lane), all in flight, and one 16-B LDS store each
@@ -736,10 +809,15 @@ __device__ __forceinline__ void p2_draw_stage(const P2Args &a, int b0, int lane,
     for (int u = 0; u < U; u++)
       *reinterpret_cast<uint4 *>(hz_lds + base + (4 * u + (lane >> 4)) * kWinStride + c4) = v[u];
   };
-  // the first stage's window starts at row 0 whatever its tags say (every
-  // start cursor is kMTAhead): its loads go out with the tag's, one round
-  // trip instead of two (rows of another episode are never read: !ok)
-  if (stage == 0) win_load(0);
+  // The window's first row is the stage's first draw's (wave-uniform, from
+  // the kernel's arguments): every draw of a script is from a bag of more
+  // than 21 tiles, so it consumes at least three words, and a board that has
+  // made d0 draws stands at row 3 d0 or later.  So the window's loads go out
+  // with the tags' and the hand-off's, one round trip instead of two (rows of
+  // another episode are never read: !ok).  HZ_P2_STATIC_WIN=0 (A/B builds):
+  // from the wave's lowest cursor, known only after the hand-off arrived.
+  const int rs = kP2StaticWin ? __builtin_amdgcn_readfirstlane((3 * d0) & ~3) : 0;
+  if (kP2StaticWin || stage == 0) win_load(rs);
   if (stage > 0 && act) {  // (one round trip: used only if the tag matches)
     const int itag = in.tag[b];
     k0 = in.k[b];
@@ -749,11 +827,17 @@ __device__ __forceinline__ void p2_draw_stage(const P2Args &a, int b0, int lane,
     for (int i = 0; i < kAheadWords; i++) q[i] = in.q[(size_t)i * nr + b];
     ok = ok && itag == e * 8 + stage;
   }
-  const bool draws = ok && k0 >= d0 && d0 < d1;
-  const int r0 = wave_min_i(draws ? (c0 & 0xFFFF) : kAheadTwist) & ~3;
-  if (r0 < kAheadTwist) {
-    if (stage > 0) win_load(r0);
+  bool draws = ok && k0 >= d0 && d0 < d1;
+  int r0 = rs;
+  if constexpr (kP2StaticWin) {
+    draws = draws && (c0 & 0xFFFF) >= r0;  // (always: see above; a board below the window would read outside it)
     win_store();
+  } else {
+    r0 = wave_min_i(draws ? (c0 & 0xFFFF) : kP2Twist) & ~3;
+    if (r0 < kP2Twist) {
+      if (stage > 0) win_load(r0);
+      win_store();
+    }
   }
   P2_PHASE(28 + stage, t0);  // window staged
   if (!act) return;
@@ -761,10 +845,10 @@ __device__ __forceinline__ void p2_draw_stage(const P2Args &a, int b0, int lane,
     out.tag[b] = -1;
     return;
   }
-  if (stage == 0) cur[0] = kMTAhead;
+  if (stage == 0) cur[0] = kP2Ahead;
   int k = k0, cc = c0;
   if (draws) {  // every earlier draw is done: continue in the window
-    const int lim = min(r0 + kP2Win, kAheadTwist);
+    const int lim = min(r0 + kP2Win, kP2Twist);
     StreamDraw<WinMT> d{WinMT(base - r0 * kWinStride + lane, c0, lim)};
 #pragma unroll 1
     for (int i = d0; i < d1; i++) {
@@ -839,7 +923,7 @@ __device__ __forceinline__ void p2_mid_put(const P2Mid &m, size_t nr, int b, con
 // the previous play stage's state; the draw source continues its script
 // (nd entries, cursors in `cur`) or the slot stream it fell onto
 __device__ __forceinline__ PlayDraw2 p2_mid_get(const P2Mid &m, size_t nr, int b, State &s, int &g, int nd,
-                                               uint32_t *slot, const int32_t *cur) {
+                                               uint32_t *slot, const int32_t *cur, int fell_lim) {
 #pragma unroll
   for (int k = 0; k < 4; k++) s.pl[k] = m.st[(size_t)k * nr + b];
   s.piles = m.st[4 * nr + b];
@@ -847,7 +931,7 @@ __device__ __forceinline__ PlayDraw2 p2_mid_get(const P2Mid &m, size_t nr, int b
   const int d = m.i[b], fc = m.i[2 * nr + b];
   g = m.i[nr + b];
   return PlayDraw2{{m.q[b], m.q[nr + b], m.q[2 * nr + b], m.q[3 * nr + b], d, nd}, fc >= 0,
-                   MTR(slot, (int)nr, fc >= 0 ? fc : 0), cur + (size_t)nd * nr};
+                   MTR(slot, (int)nr, fc >= 0 ? fc : 0, fell_lim), cur + (size_t)nd * nr};
 }
 
 // Play stage st on episode ep + kP2Play - 1 - st (the last stage: the rest of
@@ -885,9 +969,9 @@ __device__ __forceinline__ void p2_play(const P2Args &a, int blk, int st, bool i
     State s;
     int g = 0;
     PlayDraw2 draw = st == 0 ? PlayDraw2{{pl.q[b], pl.q[nr + b], pl.q[2 * nr + b], pl.q[3 * nr + b], 0, nd}, false,
-                                         MTR(slot, (int)nr, 0), cur + (size_t)nd * nr}
-                             : p2_mid_get(a.m_r[st - 1], nr, b, s, g, nd, slot, cur);
-    const bool prep = ptag == e * 8 + kP2Draw && mtag == e;
+                                         MTR(slot, (int)nr, 0, a.fell_lim), cur + (size_t)nd * nr}
+                             : p2_mid_get(a.m_r[st - 1], nr, b, s, g, nd, slot, cur, a.fell_lim);
+    bool prep = ptag == e * 8 + kP2Draw && mtag == e;
     if (prep) {
       if (st == 0) {
         if (__all(nd >= 5)) draw.scripted_reset(s);
@@ -896,6 +980,9 @@ __device__ __forceinline__ void p2_play(const P2Args &a, int blk, int st, bool i
       P2_PHASE(16 + 2 * st, t0);
       g += p2_plies(s, draw, g, g_end, rk, hs, nr);
       P2_PHASE(17 + 2 * st, t0);
+      // a game that drew past the slot's rows: its draws since are not the
+      // stream's, so the board counts as unprepared from here on
+      if (draw.lost()) prep = false;
     }
     if (!last) {
       const P2Mid &mo = a.m_w[st < kP2Play - 1 ? st : 0];
@@ -982,25 +1069,38 @@ __global__ void __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per
 #endif
 }
 
-// boards whose stream lives in a pipeline-2 slot (mt_src = 2 + slot): the
-// slot's column (word-major) into the board's own stream, one wave per board
-struct P2Slots {
-  uint32_t *s[kP2Stream];
-};
-__global__ void __launch_bounds__(64) k_mt_materialize2(uint32_t *__restrict__ mt, P2Slots slots,
-                                                       int32_t *__restrict__ mt_src, long nrow) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const int src = mt_src[b];
-  if (src < 2 || src >= 2 + kP2Stream) return;
-  const uint32_t *from = slots.s[src - 2] + b;
-  uint32_t *to = mt + (size_t)b * kMT;
-  uint32_t v[(kMT + 63) / 64];
-#pragma unroll
-  for (int k = 0; k < (kMT + 63) / 64; k++) v[k] = lane + 64 * k < kMT ? from[(size_t)(lane + 64 * k) * nrow] : 0u;
-#pragma unroll
-  for (int k = 0; k < (kMT + 63) / 64; k++)
-    if (lane + 64 * k < kMT) to[lane + 64 * k] = v[k];
-  if (lane == 0) mt_src[b] = -1;
+// Boards whose stream lives in a pipeline-2 slot (mt_src = 2 + slot).  A slot
+// holds only the rows the pipeline reads (the next generation's rows below
+// kAheadTwist and a few of the old one), so the board's own stream is rebuilt
+// from what the last play stage left: init_by_array of the episode's seed,
+// then the twist of the rows below the cursor's tw, bit for bit the state a
+// whole slot would hold.  64 boards per block, a lane per board, in LDS, like
+// the reset's seeding and at its cost (one seeding per block, tens of
+// microseconds for 4096 boards, where the copy it replaces moved 10 MB: no
+// timed path runs it; DESIGN section 3, "Round 14").
+__global__ void __launch_bounds__(kStageThreads) k_mt_materialize2(uint32_t *__restrict__ mt,
+                                                                  const uint64_t *__restrict__ seed,
+                                                                  const int32_t *__restrict__ pos,
+                                                                  int32_t *__restrict__ mt_src, int n) {
+  __shared__ uint64_t s_mask;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int b0 = blockIdx.x * kBlock, b = b0 + lane;
+  const int nb = n - b0 < kBlock ? n - b0 : kBlock;
+  if (tid < 64) {
+    const int src = b < n ? mt_src[b] : -1;
+    const bool mine = src >= 2 && src < 2 + kP2Stream;
+    const uint64_t m = __ballot(mine);
+    if (lane == 0) s_mask = m;
+    if (mine) {
+      mt_seed(hz_lds + lane, kLdsStride, seed[b]);
+      LdsMT s(lane, kMTSeeded);
+      s.twist_ahead(pos[b] >> 16);
+      mt_src[b] = -1;
+    }
+  }
+  __syncthreads();
+  const uint64_t mask = s_mask;
+  if (mask) stage_mt(mt + (size_t)b0 * kMT, nb, tid, mask, false);
 }
 
 

@@ -89,7 +89,7 @@ out["cus_used"] = len(per_cu)
 # tools/p2_roles.py's slot names)
 ph = stamps.cpu().numpy().astype(np.int64)
 pnames = {16: "playA_loaded", 17: "playA_plies", 24: "playE_loaded", 25: "playE_plies", 27: "playE_scored",
-          28: "D1_staged", 30: "D3_staged", 32: "D5_staged",
+          28: "D1_staged", 29: "D2_staged", 30: "D3_staged", 31: "D4_staged", 32: "D5_staged",
           35: "twist_go", 36: "twist_it1", 37: "twist_looped"}
 out["phases_last_column"] = {nm: [float(ph[:, k].max()), float(np.median(ph[:, k]))] for k, nm in pnames.items()}
 out["longest"] = max((v["dur_max"], k) for k, v in waves.items())
