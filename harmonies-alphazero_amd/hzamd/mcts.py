@@ -31,18 +31,31 @@ from . import _native as nat
 from .env import ACTION_SIZE
 
 MAX_CHILDREN = 69
+MAX_NODES_END = 1 << 24  # hz_mcts_create refuses max_nodes from here on (an edge id must fit 24 bits)
+DEFAULT_MAX_DEPTH = 192
 
 
 class BatchedMCTS:
-    def __init__(self, env, num_simulations, max_nodes=None, max_depth=192, exact_keys=False):
+    def __init__(self, env, num_simulations, max_nodes=None, max_depth=DEFAULT_MAX_DEPTH, exact_keys=False):
         self.env = env
         self.n = env.n
         self.device = env.device
         self.num_simulations = int(num_simulations)
         self._graph_cache = None  # (key, captured simulation, network) kept by search(graph=True)
         self._capture_stream = None  # this handle's graph-capture stream (own split-tower counter block)
-        self.max_nodes = int(max_nodes or 1 + MAX_CHILDREN * self.num_simulations)
+        # the default pools cannot overflow: one expansion of at most 69
+        # children per simulation (hz_abi.h, hz_mcts_create)
+        default_nodes = 1 + MAX_CHILDREN * self.num_simulations
+        self.max_nodes = default_nodes if max_nodes is None else int(max_nodes)
         self.max_depth = int(max_depth)
+        if not 2 <= self.max_nodes < MAX_NODES_END:
+            raise ValueError(f"max_nodes {self.max_nodes} outside 2..{MAX_NODES_END - 1}")
+        if self.max_depth < 1:
+            raise ValueError(f"max_depth {self.max_depth} below 1")
+        # smaller pools or a shorter path than the defaults: a search may hit
+        # a limit (stats()[:, 3] != 0: still a search, of a truncated tree, no
+        # longer the reference's); _finish() then counts the flagged boards
+        self.bounded = self.max_nodes < default_nodes or self.max_depth < DEFAULT_MAX_DEPTH
         self._report = {}  # output buffers of root_edges / principal_variation / export_tree, made on first use
         L = nat.lib()
         self._h = L.hz_mcts_create(self.n, self.max_nodes, self.max_depth, int(bool(exact_keys)),
@@ -81,6 +94,9 @@ class BatchedMCTS:
         # are added on the device to path_total (one small launch per search)
         self.count_path = False
         self.path_total = torch.zeros(1, dtype=torch.int64, device=d)
+        # boards whose search hit a limit, all searches (added by _finish() on
+        # a bounded handle only: one small device sum per search, no host read)
+        self.limit_hits_total = torch.zeros(1, dtype=torch.int64, device=d)
         self._nil_pol = torch.zeros(1, ACTION_SIZE, dtype=torch.float32, device=d)
         self._nil_val = torch.zeros(1, dtype=torch.float32, device=d)
 
@@ -179,6 +195,15 @@ class BatchedMCTS:
     def stats(self):
         nat.check(nat.lib().hz_mcts_stats(self._h, nat.ptr(self.counts)), "hz_mcts_stats")
         return self.counts
+
+    def limit_flags(self):
+        """Device int32 [n]: nonzero where the board's last search hit a limit
+        (1: an expansion did not fit max_nodes, or a walk reached max_depth;
+        2: a leaf with more than 69 legal moves) -- stats()[:, 3], no host
+        read.  A board with 0 searched exactly as an unbounded search would.
+        hz_mcts_begin clears the flag of the boards it starts; a board left
+        out of the last search (stats()[:, 0] == 0) keeps its earlier flag."""
+        return self.stats()[:, 3]
 
     # -- the search report (read-only views of the trees) ---------------------
     def _zeros(self, dtype, *shape):
@@ -397,6 +422,9 @@ class BatchedMCTS:
         self.eval_rows_total += self.eval_rows
         if self.count_edges:
             self.edges_total += self.stats()[:, 1].sum(dtype=torch.int64)
+        if self.bounded:
+            c = self.stats()  # (a board left out of this search has no nodes and keeps its last flag)
+            self.limit_hits_total += ((c[:, 3] != 0) & (c[:, 0] > 0)).sum(dtype=torch.int64)
         if self.count_path:
             nat.check(nat.lib().hz_mcts_path_edges(self._h, nat.ptr(self.path_total)), "hz_mcts_path_edges")
         visits = self.result()

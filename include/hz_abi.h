@@ -215,10 +215,40 @@ int hz_import_state(hz_env *env, const uint64_t *state, const uint32_t *mt, cons
  * get_best_action_and_pi (MCTS.py:272-441) with moves in ascending action
  * order (the reference's order is set iteration order).
  * Transpositions are keyed like the reference's hash(state) (exact_keys = 0)
- * or by the exact canonical tuple (exact_keys = 1).  max_nodes bounds nodes
- * and edges per board per search (1 + sims * 69 never overflows); it must be
- * below 2^24 (edge ids are packed into 24 bits of the walk's hints), else
- * create returns NULL. */
+ * or by the exact canonical tuple (exact_keys = 1).
+ *
+ * Limits (no reference counterpart: the reference's tree grows without bound;
+ * this is the build's defined behaviour, restated by the C oracle's
+ * or_mcts_cfg.max_nodes / max_depth and pinned by
+ * tests/test_mcts_limits_gpu.py).  max_nodes bounds the nodes and, separately,
+ * the edges (max_edges = max_nodes) of a board's search; 1 + sims * 69 never
+ * overflows.  It must be at least 2 and below 2^24 (edge ids are packed into
+ * 24 bits of the walk's hints), max_depth at least 1, else create returns
+ * NULL.  max_depth bounds the edges of a simulation's path (and
+ * hz_mcts_pv's max_len).
+ *  - An expansion that does not fit is refused whole.  "Fits" counts what the
+ *    expansion actually adds, after transposition and sibling de-duplication:
+ *    nodes + new nodes <= max_nodes and edges + new edges <= max_nodes.  A
+ *    refused expansion writes no node, edge or hash slot; the leaf stays
+ *    unexpanded, and counts[b][3] is set to 1.
+ *  - A refused leaf is still evaluated and its value backed up along the path.
+ *  - A refused expansion of a place_tile_3 leaf has already replayed its
+ *    children's turn-end chance draws and written the board's stream and cursor
+ *    back: the draws are kept, and the same leaf draws again the next time it
+ *    is selected.  The stream after a flagged search is therefore not the
+ *    unbounded search's.
+ *  - Each expansion is judged on its own: after a refusal a later, smaller
+ *    expansion may still fit.  If the root's own expansion does not fit, every
+ *    simulation tries it again and the search ends with no edges and no visits.
+ *  - A walk that stands on a node with edges after max_depth edges stops there
+ *    and sets counts[b][3] to 1.  That node is evaluated again and the value
+ *    backed up along the max_depth edges; it is not expanded a second time.
+ *  - A leaf with more than 69 legal moves (no legal position has them) is not
+ *    expanded and sets counts[b][3] to 2.
+ * counts[b][3] is per search: hz_mcts_begin clears it for every active board.
+ * A board whose flag is 0 after a search is bit for bit the unbounded search:
+ * visits, tree, counts and stream.  A flagged search is still a valid PUCT
+ * search, of a truncated tree; it is no longer the reference's. */
 typedef struct hz_mcts hz_mcts;
 hz_mcts *hz_mcts_create(int32_t n_boards, int32_t max_nodes, int32_t max_depth, int32_t exact_keys, void *stream);
 void hz_mcts_destroy(hz_mcts *mcts);
@@ -303,7 +333,11 @@ int hz_root_noise(const int32_t *count, int32_t n, uint64_t seed, uint64_t board
                   double *noise, double *u, void *stream);
 /* root visit counts by action id: visits[n][143] (MCTS.py:355-376) */
 int hz_mcts_result(hz_mcts *mcts, int32_t *visits);
-/* per-board [nodes, edges, search generation, overflow flag] -> counts[n][4] */
+/* per-board [nodes, edges, search generation, limit flag] -> counts[n][4].
+ * The limit flag (hz_mcts_create, "Limits"): 0 = this search is the unbounded
+ * search; 1 = an expansion did not fit max_nodes or a walk reached max_depth;
+ * 2 = a leaf had more than 69 legal moves.  Cleared by hz_mcts_begin for the
+ * boards it starts (a board left out keeps counts 0, 0 and its last flag). */
 int hz_mcts_stats(hz_mcts *mcts, int32_t *counts);
 /* ---- search report: three read-only views of the trees ---------------------
  * None writes the tree, the env or the streams; each is enqueued on the

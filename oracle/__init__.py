@@ -30,7 +30,8 @@ class MctsCfg(ctypes.Structure):
     _fields_ = [("sims", ctypes.c_int32), ("cpuct", ctypes.c_float), ("eps", ctypes.c_double),
                 ("testing", ctypes.c_int32), ("tau0", ctypes.c_int32), ("ply", ctypes.c_int32),
                 ("u", ctypes.c_double), ("exact_keys", ctypes.c_int32), ("negate_value", ctypes.c_int32),
-                ("evaluator", ctypes.c_int32), ("variant", ctypes.c_int32)]
+                ("evaluator", ctypes.c_int32), ("variant", ctypes.c_int32),
+                ("max_nodes", ctypes.c_int32), ("max_depth", ctypes.c_int32)]
 
 
 def build():
@@ -81,6 +82,8 @@ def lib():
         L.or_mcts_search.restype = ctypes.c_int
         L.or_mcts_search_ex.argtypes = L.or_mcts_search.argtypes
         L.or_mcts_search_ex.restype = ctypes.c_int
+        L.or_mcts_search_lim.argtypes = L.or_mcts_search.argtypes + [ctypes.c_void_p, ctypes.c_void_p]
+        L.or_mcts_search_lim.restype = ctypes.c_int
         L.or_stub_eval.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.or_dense_stub_eval.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         _lib = L
@@ -239,19 +242,27 @@ def replay_actions(seeds, actions, nthreads=0):
 
 
 def mcts_search(st, m, sims, cpuct, eps=0.25, testing=True, tau0=15, ply=0, u=0.0, noise=None,
-                exact_keys=False, negate_value=False, evaluator=0, variant=0):
+                exact_keys=False, negate_value=False, evaluator=0, variant=0, max_nodes=0, max_depth=0,
+                with_limits=False):
     """evaluator: 0 the stub, 1 the dense stub.  variant (tests only): a bit
     mask of deliberately wrong precisions (hz_oracle.h OR_VARIANT_*), used to
-    show that a fixture tells them from the reference's arithmetic."""
+    show that a fixture tells them from the reference's arithmetic.
+    max_nodes / max_depth: hz_mcts_create's limits (0: unlimited, the
+    reference).  Returns (action, visits, nodes, edges), and with with_limits
+    also the limit flag (0 / 1) and the search's deepest path."""
     st = np.ascontiguousarray(st, np.int16)
     cfg = MctsCfg(sims, cpuct, eps, int(bool(testing)), tau0, ply, u, int(bool(exact_keys)),
-                  int(bool(negate_value)), int(evaluator), int(variant))
+                  int(bool(negate_value)), int(evaluator), int(variant), int(max_nodes), int(max_depth))
     nz = np.zeros(143, np.float64) if noise is None else np.ascontiguousarray(noise, np.float64)
     visits = np.zeros(143, np.int32)
     nn = ctypes.c_int32(0)
     ne = ctypes.c_int32(0)
-    a = lib().or_mcts_search_ex(_p(st), ctypes.byref(m), ctypes.byref(cfg), _p(nz), _p(visits),
-                             ctypes.byref(nn), ctypes.byref(ne))
+    flag = ctypes.c_int32(0)
+    deep = ctypes.c_int32(0)
+    a = lib().or_mcts_search_lim(_p(st), ctypes.byref(m), ctypes.byref(cfg), _p(nz), _p(visits),
+                                 ctypes.byref(nn), ctypes.byref(ne), ctypes.byref(flag), ctypes.byref(deep))
+    if with_limits:
+        return a, visits, nn.value, ne.value, flag.value, deep.value
     return a, visits, nn.value, ne.value
 
 

@@ -45,7 +45,7 @@ int main(void) {
   free(acts);
 
   /* one game by hand: legal masks, every encoder, canonical keys, scoring,
-   * greedy moves and searches along it */
+   * greedy moves and searches (one of them bounded) along it */
   or_mt m, g;
   int16_t st[OR_REFSTATE];
   uint8_t mask[143], key[128], cells[23];
@@ -83,6 +83,19 @@ int main(void) {
       memcpy(&g, &m, sizeof g);
       const int a = or_mcts_search_ex(st, &g, &cfg, noise, visits, &nn, &ne);
       h = mix(h, (uint64_t)(a + 7 * nn + 11 * ne) + (uint64_t)(int64_t)(v * 8388608.0));
+      for (int i = 0; i < 143; i++) h = mix(h, (uint64_t)visits[i]);
+      /* a bounded search: expansions that do not fit in 60 nodes or edges are
+       * undone (nodes, edges and hash slots taken back, the table rebuilt),
+       * walks stop at depth 2, the path storage is two entries long */
+      or_mcts_cfg lim = {48, 2.0f, 0.25, 1, 10, ply, 0.5, 0, 0, 0, 0, 60, 2};
+      int32_t flag = -1, deep = -1;
+      memcpy(&g, &m, sizeof g);
+      const int b = or_mcts_search_lim(st, &g, &lim, noise, visits, &nn, &ne, &flag, &deep);
+      if (nn > 60 || ne > 60 || deep > 2 || flag != 1) {
+        printf("bounded search out of its limits: %d nodes %d edges depth %d flag %d\n", nn, ne, deep, flag);
+        return 1;
+      }
+      h = mix(h, (uint64_t)(b + 7 * nn + 11 * ne + 13 * deep) ^ or_mt_next32(&g));
       for (int i = 0; i < 143; i++) h = mix(h, (uint64_t)visits[i]);
     }
     int a = -1, k = (int)(or_rule(777, (uint64_t)ply) >> 32) % (L > 0 ? L : 1);

@@ -16,6 +16,7 @@
 #include "hz_oracle.h"
 
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #ifdef _OPENMP
@@ -865,9 +866,20 @@ static void stub_eval_state(const ostate *s, int evaluator, float *policy, doubl
   else or_stub_eval(v, policy, value);
 }
 
+/* cfg->max_nodes / cfg->max_depth (0: unlimited, the reference) bound the
+ * search as hz_mcts_create's limits bound the kernels' (include/hz_abi.h):
+ * an expansion that would leave more than max_nodes nodes or edges is undone
+ * whole, the chance draws of its children kept; a walk that stands on an
+ * expanded node at depth max_depth stops there.  Either sets *limit_flag; the
+ * leaf is evaluated and backed up all the same.  *deepest: the longest path. */
 static int mcts_search(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg, const double *noise,
-                       int32_t *visits, int32_t *n_nodes, int32_t *n_edges) {
+                       int32_t *visits, int32_t *n_nodes, int32_t *n_edges, int32_t *limit_flag,
+                       int32_t *deepest) {
   geom_init();
+  const int max_nodes = cfg->max_nodes > 0 ? cfg->max_nodes : 0;
+  const int max_depth = cfg->max_depth > 0 ? cfg->max_depth : 0;
+  const int path_cap = max_depth ? max_depth : 512;
+  int flag = 0, deep = 0;
   otree t;
   t.cap_n = 1024; t.nodes = malloc(sizeof(onode) * t.cap_n); t.nn = 0;
   t.cap_e = 4096; t.edges = malloc(sizeof(oedge) * t.cap_e); t.ne = 0;
@@ -877,7 +889,7 @@ static int mcts_search(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg
   ostate root;
   from_ref(root_ref, &root);
   tree_add(&t, &root);
-  int path[512];
+  int *path = malloc(sizeof(int) * (size_t)path_cap);
   uint8_t mask[143];
   float pol[143];
   for (int sim = 0; sim < cfg->sims; sim++) {
@@ -900,9 +912,12 @@ static int mcts_search(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg
         if (qu > best) { best = qu; sel = t.nodes[node].e0 + e; }
       }
       if (sel < 0) break;
+      if (max_depth && depth >= max_depth) { flag = 1; break; } /* on an expanded node: no deeper */
+      if (depth >= path_cap) { fprintf(stderr, "hz_oracle: search path longer than %d\n", path_cap); abort(); }
       path[depth++] = sel;
       node = t.edges[sel].child;
     }
+    if (depth > deep) deep = depth;
     double value;
     const ostate *ls = &t.nodes[node].s;
     int leaf_player = ls->player;
@@ -923,8 +938,8 @@ static int mcts_search(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg
       }
       /* expand_leaf (MCTS.py:151-218) */
       int L = legal_of(&t.nodes[node].s, mask);
-      if (L) {
-        int e0 = t.ne, cnt = 0;
+      if (L && t.nodes[node].ne == 0) {                    /* (a walk cut at max_depth: expanded already) */
+        int e0 = t.ne, cnt = 0, nn0 = t.nn;
         for (int a = 0; a < 143; a++) {
           if (!mask[a]) continue;
           ostate child = t.nodes[node].s;
@@ -940,8 +955,19 @@ static int mcts_search(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg
           ed->P = pol[a]; ed->player = t.nodes[node].s.player;
           cnt++;
         }
-        t.nodes[node].e0 = e0;
-        t.nodes[node].ne = cnt;
+        if (max_nodes && (t.nn > max_nodes || t.ne > max_nodes)) {
+          /* does not fit: the nodes and edges it added are taken back (the
+           * table rebuilt: linear probing cannot delete in place), the leaf
+           * stays unexpanded, *m stays where the children's draws left it */
+          t.nn = nn0;
+          t.ne = e0;
+          for (int i = 0; i < t.hcap; i++) t.hslot[i] = -1;
+          for (int v = 0; v < t.nn; v++) tree_insert_slot(&t, v);
+          flag = 1;
+        } else {
+          t.nodes[node].e0 = e0;
+          t.nodes[node].ne = cnt;
+        }
       }
     } else {
       int outcome = ls->winner == 0 ? 1 : ls->winner == 1 ? -1 : 0;
@@ -991,24 +1017,36 @@ static int mcts_search(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg
   }
   if (n_nodes) *n_nodes = t.nn;
   if (n_edges) *n_edges = t.ne;
-  free(t.nodes); free(t.edges); free(t.hslot);
+  if (limit_flag) *limit_flag = flag;
+  if (deepest) *deepest = deep;
+  free(t.nodes); free(t.edges); free(t.hslot); free(path);
   return best;
 }
 
 /* The entry point older callers were built against: it reads the fields up to
  * negate_value only (a caller's struct may end there), the stub and the
- * reference's arithmetic.  or_mcts_search_ex reads the whole struct. */
+ * reference's arithmetic.  or_mcts_search_ex reads up to variant (the struct
+ * it was introduced with), or_mcts_search_lim the whole struct. */
 int or_mcts_search(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg, const double *noise,
                    int32_t *visits, int32_t *n_nodes, int32_t *n_edges) {
   or_mcts_cfg c;
   memset(&c, 0, sizeof c);
   memcpy(&c, cfg, offsetof(or_mcts_cfg, evaluator));
-  return mcts_search(root_ref, m, &c, noise, visits, n_nodes, n_edges);
+  return mcts_search(root_ref, m, &c, noise, visits, n_nodes, n_edges, NULL, NULL);
 }
 
 int or_mcts_search_ex(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg, const double *noise,
                       int32_t *visits, int32_t *n_nodes, int32_t *n_edges) {
-  return mcts_search(root_ref, m, cfg, noise, visits, n_nodes, n_edges);
+  or_mcts_cfg c; /* up to variant, where the struct of this entry point's callers may end: no limits */
+  memset(&c, 0, sizeof c);
+  memcpy(&c, cfg, offsetof(or_mcts_cfg, max_nodes));
+  return mcts_search(root_ref, m, &c, noise, visits, n_nodes, n_edges, NULL, NULL);
+}
+
+int or_mcts_search_lim(const int16_t *root_ref, or_mt *m, const or_mcts_cfg *cfg, const double *noise,
+                       int32_t *visits, int32_t *n_nodes, int32_t *n_edges, int32_t *limit_flag,
+                       int32_t *deepest) {
+  return mcts_search(root_ref, m, cfg, noise, visits, n_nodes, n_edges, limit_flag, deepest);
 }
 
 /* ---------------------------------------------------------- greedy agent

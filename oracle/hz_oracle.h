@@ -87,19 +87,34 @@ typedef struct {
                            for a plausible wrong precision, to show that a fixture tells them
                            apart: 1 cpuct * P formed in double; 2 the root mix's
                            (1 - eps) * P formed in double; 4 W accumulated in fp32 */
+  int32_t max_nodes;    /* 0: unlimited (the reference).  Else hz_mcts_create's max_nodes: an
+                           expansion that would leave more than max_nodes nodes or more than
+                           max_nodes edges is undone whole (its nodes, edges and hash slots taken
+                           back, the leaf left unexpanded), the chance draws of its children kept;
+                           the leaf's value is backed up as usual */
+  int32_t max_depth;    /* 0: unlimited.  Else hz_mcts_create's max_depth: a walk standing on a
+                           node with edges after max_depth edges stops there; the node is
+                           evaluated and backed up, not expanded again */
 } or_mcts_cfg;
 
 #define OR_VARIANT_CPUCT_F64 1
 #define OR_VARIANT_MIX_F64   2
 #define OR_VARIANT_W_F32     4
 
-/* or_mcts_search reads cfg up to negate_value only (evaluator = variant = 0):
- * a caller built against the struct that ended there keeps working.
- * or_mcts_search_ex reads every field. */
+/* or_mcts_search reads cfg up to negate_value only (evaluator = variant = 0,
+ * no limits): a caller built against the struct that ended there keeps
+ * working.  or_mcts_search_ex reads up to variant, likewise (no limits).
+ * or_mcts_search_lim reads every field and reports *limit_flag (1: some
+ * simulation of this search had its expansion refused or its walk cut,
+ * counts[b][3] != 0 of hz_mcts_stats; else 0) and *deepest (the longest path
+ * of the search, in edges); either pointer may be NULL. */
 int or_mcts_search(const int16_t *root, or_mt *m, const or_mcts_cfg *cfg, const double *noise,
                    int32_t *visits143, int32_t *n_nodes, int32_t *n_edges);
 int or_mcts_search_ex(const int16_t *root, or_mt *m, const or_mcts_cfg *cfg, const double *noise,
                       int32_t *visits143, int32_t *n_nodes, int32_t *n_edges);
+int or_mcts_search_lim(const int16_t *root, or_mt *m, const or_mcts_cfg *cfg, const double *noise,
+                       int32_t *visits143, int32_t *n_nodes, int32_t *n_edges, int32_t *limit_flag,
+                       int32_t *deepest);
 
 /* Stub evaluator (integer formula over the encoder's inputs). */
 void or_stub_eval(const int16_t *st, float *policy143, double *value);

@@ -1,7 +1,8 @@
 """The C oracle under AddressSanitizer + UndefinedBehaviorSanitizer (SURVEY
 §5: sanitizers on the C restatement): oracle/asan_driver.c calls every entry
 point on small inputs (rule games, auto-reset, a caller's legal and illegal
-moves, masks, encoders, canonical keys, scoring, greedy moves, searches,
+moves, masks, encoders, canonical keys, scoring, greedy moves, searches
+(one bounded by max_nodes and max_depth: the undo and the table rebuild),
 rule play from a given state and from a stuck board);
 any report aborts the run.  The sanitized build must also compute what the
 optimised oracle computes (the driver's checksum, built twice)."""

@@ -331,3 +331,157 @@ def test_stuck_board_is_left_alone():
         w2, i2 = m.words()
         assert (w2 == words).all() and i2 == idx
 
+
+
+# ---------------------------------------------------------------- search limits
+# hz_mcts_create's max_nodes / max_depth restated in the oracle (or_mcts_cfg's
+# trailing fields, 0 = unlimited).  need = max(n_nodes, n_edges) of a fixture
+# row: the smallest max_nodes its unbounded search fits (max_edges = max_nodes).
+LIMIT_GROUP = (32, 2.0, 1, 0.25)   # the rows tests/test_mcts_limits_gpu.py searches
+LIMIT_NODES = 500                  # ... with this max_nodes
+LIMIT_NODES_EARLY = (250, 140)     # ... and these, where refusals change the stream and the visits
+LIMIT_DEPTH = 2                    # ... and this max_depth (test_mcts_limits_fixture_conditions)
+
+
+def limits_row(f, k, **kw):
+    """Row k of mcts.npz searched by the oracle: (action, visits, nodes, edges,
+    limit flag, deepest path, next MT word)."""
+    m = oracle.mt_seed(int(f["mt_seed"][k]))
+    r = oracle.mcts_search(
+        f["state"][k], m, int(f["sims"][k]), float(f["cpuct"][k]), eps=float(f["eps"][k]),
+        testing=bool(f["testing"][k]), tau0=int(f["tau0"][k]), ply=int(f["ply"][k]),
+        u=float(f["u"][k]), noise=f["noise"][k], with_limits=True, **kw)
+    return r + (oracle.mt_next32(m),)
+
+
+def same_search(r, s):
+    return r[0] == s[0] and (r[1] == s[1]).all() and r[2:] == s[2:]
+
+
+def limit_rows(f):
+    return [k for k in range(len(f["sims"])) if f["sims"][k] <= 64]
+
+
+def group_rows(f, key):
+    return [k for k in range(len(f["sims"]))
+            if (int(f["sims"][k]), float(f["cpuct"][k]), int(f["testing"][k]), float(f["eps"][k])) == key]
+
+
+def test_mcts_limits_that_fit_change_nothing():
+    """max_nodes == need (and need + 1000) is the unbounded search, which is
+    the fixture row: visits, action, counts, next MT word, flag 0."""
+    f = load("mcts.npz")
+    rows = limit_rows(f)
+    assert len(rows) == 57
+    for k in rows:
+        need = max(int(f["n_nodes"][k]), int(f["n_edges"][k]))
+        free = limits_row(f, k)
+        assert (free[1] == f["visits"][k]).all() and free[0] == f["action"][k] and free[4] == 0
+        assert free[2:4] == (f["n_nodes"][k], f["n_edges"][k]) and free[6] == f["next_word"][k]
+        for cap in (need, need + 1000):
+            assert same_search(limits_row(f, k, max_nodes=cap), free), (k, cap)
+
+
+def test_mcts_one_entry_short_refuses_an_expansion():
+    """max_nodes == need - 1: the flag is set, both counts stay within
+    max_nodes, and the root's visits still sum to sims - 1 (a refused leaf is
+    evaluated and backed up) -- unless the root's own expansion is what does
+    not fit (the three rows with 2 or 3 legal moves): then every simulation
+    tries it again, there are no edges and no visits.
+    Those rows are place_tile_3 roots, so they pin the stream rule where the
+    first refused leaf is known from outside: each refused attempt has replayed
+    the children's turn-end draws and kept them.  The stream is the one
+    or_step leaves after sims rounds over the legal moves (plus the no-visits
+    fallback's random.choice), not the unbounded row's."""
+    f = load("mcts.npz")
+    root_refused = []
+    for k in limit_rows(f):
+        need = max(int(f["n_nodes"][k]), int(f["n_edges"][k]))
+        if need < 3:
+            continue
+        sims = int(f["sims"][k])
+        a, visits, nn, ne, flag, _, nxt = limits_row(f, k, max_nodes=need - 1)
+        assert flag == 1 and nn <= need - 1 and ne <= need - 1, k
+        legal = np.flatnonzero(oracle.legal(f["state"][k]))
+        if 1 + len(legal) <= need - 1:
+            assert visits.sum() == sims - 1, k
+            continue
+        root_refused.append(k)
+        assert visits.sum() == 0 and (nn, ne) == (1, 0), k
+        assert f["state"][k][73] == 3 and nxt != f["next_word"][k], k
+        m = oracle.mt_seed(int(f["mt_seed"][k]))
+        for _ in range(sims):
+            for act in legal:
+                assert oracle.step(f["state"][k], int(act), m)[0] == 0
+        assert a == legal[oracle.lib().or_randbelow(m, len(legal))] and nxt == oracle.mt_next32(m), k
+    assert len(root_refused) >= 1
+    print("root refused:", root_refused)
+
+
+def test_mcts_depth_limit():
+    """max_depth >= the row's deepest path changes nothing; one less sets the
+    flag; max_depth 1 keeps every walk at depth 1 (the flag tells whether one
+    stood on an expanded child, as the unbounded search's first walk to depth 2
+    does) with the visits still summing to sims - 1."""
+    f = load("mcts.npz")
+    for k in limit_rows(f):
+        sims = int(f["sims"][k])
+        free = limits_row(f, k)
+        deep = free[5]
+        assert 1 <= deep <= sims - 1
+        for D in (deep, deep + 100):
+            assert same_search(limits_row(f, k, max_depth=D), free), (k, D)
+        if deep >= 2:
+            cut = limits_row(f, k, max_depth=deep - 1)
+            assert cut[4] == 1 and cut[5] == deep - 1 and cut[1].sum() == sims - 1, k
+        one = limits_row(f, k, max_depth=1)
+        assert one[5] == 1 and one[1].sum() == sims - 1, k
+        assert one[4] == int(deep >= 2), k
+
+
+def test_mcts_limits_fixture_conditions():
+    """What tests/test_mcts_limits_gpu.py needs of mcts.npz.  The group
+    (32 sims, cpuct 2, testing, eps 0.25) has 13 rows with needs 234, 508,
+    500, 439, 627, 482, 277, 562, 987, 741, 215, 4, 292: under max_nodes 500
+    eight fit (one, 492 nodes / 500 edges, exactly) and five do not (508 just
+    over).  Their deepest paths are 3, 3, 4, 4, 2, 3, 4, 2, 3, 2, 3, 1, 3:
+    max_depth 2 leaves four rows as they are and cuts nine (3 would leave ten
+    and cut three; 2 is taken for the larger number of cut boards)."""
+    f = load("mcts.npz")
+    rows = group_rows(f, LIMIT_GROUP)
+    need = [max(int(f["n_nodes"][k]), int(f["n_edges"][k])) for k in rows]
+    assert need == [234, 508, 500, 439, 627, 482, 277, 562, 987, 741, 215, 4, 292]
+    fit = [x <= LIMIT_NODES for x in need]
+    assert sum(fit) == 8 and len(fit) - sum(fit) == 5 and LIMIT_NODES in need and LIMIT_NODES + 8 in need
+    k = rows[need.index(LIMIT_NODES)]
+    assert (f["n_nodes"][k], f["n_edges"][k]) == (492, 500)
+    deep = [limits_row(f, k)[5] for k in rows]
+    assert deep == [3, 3, 4, 4, 2, 3, 4, 2, 3, 2, 3, 1, 3]
+    assert sum(d <= LIMIT_DEPTH for d in deep) >= 3 and sum(d > LIMIT_DEPTH for d in deep) >= 3
+    # at 500 the refused rows lose only late expansions: flag and counts differ
+    # from the unbounded search, visits, move and stream do not
+    for k, ok in zip(rows, fit):
+        r, free = limits_row(f, k, max_nodes=LIMIT_NODES), limits_row(f, k)
+        assert (r[4] == 0) == ok and (r[2:4] == free[2:4]) == ok, k
+        assert (r[1] == free[1]).all() and r[0] == free[0] and r[6] == free[6], k
+    # ... so the GPU tests also run the group at 250 and 140, where refusals
+    # come early: rows refused there whose next MT word is not the fixture's (a
+    # refused place_tile_3 leaf's draws kept, and made again on re-selection)
+    # and rows whose visits are not the fixture's, every one still backed up
+    want = {250: (10, [4, 16], [12, 16]), 140: (12, [4, 16, 24, 28, 36, 40], [12, 16, 36])}
+    assert tuple(want) == LIMIT_NODES_EARLY
+    for cap, (refused, other_word, other_visits) in want.items():
+        rs = {k: limits_row(f, k, max_nodes=cap) for k in rows}
+        flagged = [k for k in rows if rs[k][4]]
+        assert len(flagged) == refused and all((rs[k][4] == 0) == (x <= cap) for k, x in zip(rows, need))
+        assert [k for k in flagged if rs[k][6] != f["next_word"][k]] == other_word
+        assert [k for k in flagged if (rs[k][1] != f["visits"][k]).any()] == other_visits
+        assert all(rs[k][1].sum() == 31 for k in rows)
+    # ... and the three place_tile_3 roots whose own expansion does not fit
+    # need - 1 (test_mcts_one_entry_short_refuses_an_expansion), one per handle
+    shapes = [(int(f["n_nodes"][k]), int(f["n_edges"][k]), int(f["sims"][k]), int(f["state"][k][73]))
+              for k in range(len(f["sims"])) if max(f["n_nodes"][k], f["n_edges"][k]) in (3, 4)]
+    assert sorted(shapes) == [(3, 2, 8, 3), (4, 3, 32, 3), (4, 3, 64, 3), (4, 3, 200, 3)]
+    # the 8-simulation row where only the edge pool binds
+    k8 = [k for k in range(len(f["sims"])) if (f["n_nodes"][k], f["n_edges"][k], f["sims"][k]) == (267, 339, 8)]
+    assert len(k8) == 1
