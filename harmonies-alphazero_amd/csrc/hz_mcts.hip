@@ -1277,6 +1277,19 @@ __global__ void __launch_bounds__(kWave) k_root_noise(const int32_t *__restrict_
   }
 }
 
+// One uniform in (0, 1] per board (hz_playout_coin: the coin of playout-cap
+// randomization, no reference counterpart), from k_root_noise's generator and
+// board key under a salt of its own: neither the noise nor the move-choice
+// uniform moves by a bit.
+__global__ void __launch_bounds__(256) k_playout_coin(int n, uint64_t seed, uint64_t board_base, uint64_t move,
+                                                      double *__restrict__ coin) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  const uint64_t key = mix64(mix64(mix64(seed ^ 0x6A09E667F3BCC908ULL) ^ (board_base + (uint64_t)b)) ^ move);
+  NoiseStream s{mix64(key ^ 0x94D049BB133111EBULL), 0};
+  coin[b] = s.uniform();
+}
+
 // root visit counts by action (MCTS.py:355-376)
 __global__ void __launch_bounds__(kWave) k_result(hz_mcts m, int32_t *__restrict__ visits) {
   int b = blockIdx.x;
@@ -1687,6 +1700,14 @@ int hz_root_noise(const int32_t *count, int32_t n, uint64_t seed, uint64_t board
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_root_noise, dim3(n), dim3(kWave), 0, (hipStream_t)stream, count, n, seed, board_base, move,
                      alpha, noise, u);
+  return launch_err();
+}
+
+int hz_playout_coin(int32_t n, uint64_t seed, uint64_t board_base, uint64_t move, double *coin, void *stream) {
+  if (n < 0 || !coin) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_playout_coin, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, seed, board_base,
+                     move, coin);
   return launch_err();
 }
 

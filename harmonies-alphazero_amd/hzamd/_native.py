@@ -68,6 +68,7 @@ _SIGS = {
     "hz_mcts_result": ([_vp, _vp], _c.c_int),
     "hz_root_noise": ([_vp, _c.c_int32, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_double, _vp, _vp, _vp],
                       _c.c_int),
+    "hz_playout_coin": ([_c.c_int32, _c.c_uint64, _c.c_uint64, _c.c_uint64, _vp, _vp], _c.c_int),
     "hz_mcts_stats": ([_vp, _vp], _c.c_int),
     "hz_mcts_root_edges": ([_vp] * 7, _c.c_int),
     "hz_mcts_pv": ([_vp, _c.c_int32] + [_vp] * 5, _c.c_int),

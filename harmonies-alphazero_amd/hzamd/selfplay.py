@@ -48,6 +48,16 @@ class NoiseSource:
                   "hz_root_noise")
         return noise, u
 
+    def coin(self, step, n):
+        """One uniform in (0, 1] per board under the same key (hz_playout_coin),
+        f64 [n] on the device: move `step`'s coin for playout-cap
+        randomization; the noise and u of draw() do not depend on it."""
+        coin = torch.empty(n, dtype=torch.float64, device=self.device)
+        nat.check(nat.lib().hz_playout_coin(n, self.seed & (2**64 - 1), self.board_base & (2**64 - 1),
+                                            int(step) & (2**64 - 1), nat.ptr(coin), nat.stream_ptr(self.device)),
+                  "hz_playout_coin")
+        return coin
+
 
 class SelfPlay:
     def __init__(self, n_boards, evaluator, mcts_config=None, seed_base=0, device="cuda", max_plies=200,

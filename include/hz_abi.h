@@ -331,6 +331,13 @@ int hz_mcts_expand_backup_select_gather(hz_mcts *mcts, hz_env *env, const float 
  * not depend on the batch or the GPU count.  Enqueued on `stream`. */
 int hz_root_noise(const int32_t *count, int32_t n, uint64_t seed, uint64_t board_base, uint64_t move, double alpha,
                   double *noise, double *u, void *stream);
+/* Playout-cap coin (no reference counterpart; for a self-play that searches
+ * only a random share of its moves in full, as KataGo does): coin[n] (device)
+ * gets one uniform in (0, 1] per board from hz_root_noise's generator and key
+ * (seed, board_base + b, move) under a salt of its own, so hz_root_noise's
+ * noise and u are what they were and a board's coin depends on nothing but
+ * (seed, global board id, move).  Enqueued on `stream`. */
+int hz_playout_coin(int32_t n, uint64_t seed, uint64_t board_base, uint64_t move, double *coin, void *stream);
 /* root visit counts by action id: visits[n][143] (MCTS.py:355-376) */
 int hz_mcts_result(hz_mcts *mcts, int32_t *visits);
 /* per-board [nodes, edges, search generation, limit flag] -> counts[n][4].
