@@ -61,6 +61,17 @@ struct hz_mcts {
   int32_t *slot;         // [n]  row of board b in the gathered leaf batch, -1 = not evaluated
   int32_t *gidx_c;       // [n]  leaf_gidx of the gathered rows, in board order
   int64_t *eval_ctr;     // optional (hz_mcts_set_eval_counter): k_gather adds each simulation's row count
+  // rows of the policy / value tensors of the next expand call (hz_mcts_set_row_cap; 0: unchecked): a board whose
+  // row is at or past it reads neither, expands and backs up nothing and sets err[0]
+  int32_t row_cap;
+  int32_t *err;          // [1] device error word (hz_mcts_take_error): bit 0 = a row at or past row_cap
+  // per-board simulation budgets (hz_mcts_set_budget): budget == nullptr: no gate; else budget == budget_buf
+  int32_t *budget;       // [n] the gate's budgets (the handle's copy), or nullptr
+  int32_t *sims_done;    // [n] simulations select_board has given board b in this search (counted under the gate only)
+  int32_t *budget_buf;   // [n] owned; fixed address, so a captured simulation stays valid while its contents change
+  // per-board root noise (hz_mcts_set_root_noise_mask): nullptr: every board, else noise_mask == mask_buf
+  uint8_t *noise_mask;
+  uint8_t *mask_buf;     // [n] owned
 };
 
 namespace {
@@ -99,6 +110,7 @@ __global__ void __launch_bounds__(kWave) k_begin(hz_mcts m, const uint64_t *__re
   if (b >= m.n) return;
   int32_t *cnt = m.counts + (size_t)b * 4;
   bool act = !active || active[b];
+  m.sims_done[b] = 0;  // every board: one left out of this search reads 0, not its last search's count
   if (!act) {
     m.leaf[b] = -1;
     m.leaf_gidx[b] = -1;
@@ -107,6 +119,14 @@ __global__ void __launch_bounds__(kWave) k_begin(hz_mcts m, const uint64_t *__re
     return;
   }
   State s = load_state(game, n_env, b);
+  if (m.budget && !game_done(s.misc)) {
+    // under the gate a stuck root (no legal move, game not over) gets budget
+    // 0 in the handle's copy: every simulation of it would evaluate the root
+    // and change nothing (no edges, no visits, no draws), so its tree, flag
+    // and stream are those of any budget, and it takes no leaf row
+    uint64_t mk[3];
+    if (legal_mask(s, mk) == 0) m.budget[b] = 0;
+  }
   size_t nb = (size_t)b * m.max_nodes;
   store_node(m.node_state + nb * 6, s);
   CKey key = canon_key(s, !m.exact_keys);
@@ -198,13 +218,22 @@ __device__ __forceinline__ int select_board(const hz_mcts &m, int b, int lane, c
   const bool act = !active || active[b];
   const int n_nodes = cnt[0];
   int ne = m.node_ne[nb], e0 = m.node_e0[nb];  // the root
-  if (!act || n_nodes == 0) {
+  // the budget gate (hz_mcts_set_budget; same round trip): a board that has
+  // had its budget's simulations is not walked: no leaf, no leaf row, no
+  // draw, no backup.  Off (budget == nullptr): one scalar test.
+  int sims = 0, budget = 1;
+  if (m.budget) {
+    sims = m.sims_done[b];  // (written by this board's wave alone, in an earlier launch)
+    budget = m.budget[b];
+  }
+  if (!act || n_nodes == 0 || sims >= budget) {
     if (lane == 0) {
       m.leaf[b] = -1;
       m.leaf_gidx[b] = -1;
     }
     return -1;
   }
+  if (m.budget && lane == 0) m.sims_done[b] = sims + 1;  // (a refused expansion is a simulation too)
   int node = 0, d = 0;
   int32_t *path = m.path + (size_t)b * m.max_depth;
   bool term = false;                           // an active board's root is not terminal
@@ -715,10 +744,17 @@ __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts 
     double outcome = wc == 1 ? 1.0 : wc == 2 ? -1.0 : 0.0;
     v = (wc == 3) ? 0.0 : (leaf_player == 0 ? outcome : -outcome);
   } else {
+    // the evaluator's outputs have row_cap rows (hz_mcts_set_row_cap): a row
+    // at or past them is not read; the board expands and backs up nothing
+    // and the handle's error word says so (wave-uniform: row is a scalar)
+    if (m.row_cap && row >= (size_t)m.row_cap) {
+      if (lane == 0) atomicOr(m.err, 1);
+      return;
+    }
     v = (double)value[row];
     uint64_t mk[3];
     int nl = legal_mask(ls, mk);
-    bool noisy = leaf == 0 && !testing && noise;
+    bool noisy = leaf == 0 && !testing && noise && (!m.noise_mask || m.noise_mask[b]);
     HZ_XSTAMP(1)
     if (nl > 0 && nl <= kMaxChildren && leaf_ne == 0) {
       bool turn_end = phase_of(ls.misc) == PH_P3;
@@ -1524,13 +1560,18 @@ hz_mcts *hz_mcts_create(int32_t n_boards, int32_t max_nodes, int32_t max_depth, 
             alloc(&m->edge_hint, E) &&
             alloc(&m->ht, n * m->hcap) && alloc(&m->counts, n * 4) && alloc(&m->path, n * max_depth) &&
             alloc(&m->depth, n) && alloc(&m->leaf, n) && alloc(&m->leaf_gidx, n) && alloc(&m->slot, n) &&
-            alloc(&m->gidx_c, n);
+            alloc(&m->gidx_c, n) && alloc(&m->err, 1) && alloc(&m->sims_done, n) && alloc(&m->budget_buf, n) &&
+            alloc(&m->mask_buf, n);
   if (ok) {
     ok = hipMemset(m->ht, 0, n * m->hcap * sizeof(uint64_t)) == hipSuccess &&
          hipMemset(m->counts, 0, n * 4 * sizeof(int32_t)) == hipSuccess &&
          hipMemset(m->depth, 0, n * sizeof(int32_t)) == hipSuccess &&
          hipMemset(m->leaf, 0xff, n * sizeof(int32_t)) == hipSuccess &&
-         hipMemset(m->leaf_gidx, 0xff, n * sizeof(int32_t)) == hipSuccess;
+         hipMemset(m->leaf_gidx, 0xff, n * sizeof(int32_t)) == hipSuccess &&
+         hipMemset(m->err, 0, sizeof(int32_t)) == hipSuccess &&
+         hipMemset(m->sims_done, 0, n * sizeof(int32_t)) == hipSuccess &&
+         hipMemset(m->budget_buf, 0, n * sizeof(int32_t)) == hipSuccess &&
+         hipMemset(m->mask_buf, 0, n * sizeof(uint8_t)) == hipSuccess;
   }
   if (!ok) {
     hz_mcts_destroy(m);
@@ -1543,7 +1584,8 @@ void hz_mcts_destroy(hz_mcts *m) {
   if (!m) return;
   void *ptrs[] = {m->node_state, m->node_key, m->node_e0,   m->node_ne, m->edge_action, m->edge_child,
                   m->edge_n,     m->edge_w,    m->edge_p,    m->edge_player, m->edge_hint, m->ht, m->counts,
-                  m->path,       m->depth,     m->leaf,      m->leaf_gidx, m->slot, m->gidx_c};
+                  m->path,       m->depth,     m->leaf,      m->leaf_gidx, m->slot, m->gidx_c,
+                  m->err,        m->sims_done, m->budget_buf, m->mask_buf};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   free(m);
@@ -1564,6 +1606,48 @@ int hz_mcts_set_dedup_walk(hz_mcts *m, int32_t on) {
 int hz_mcts_set_gather_encode(hz_mcts *m, int32_t mode) {
   if (!m || mode < -1 || mode > 1) return -1;
   m->gather_mode = mode;
+  return 0;
+}
+
+int hz_mcts_set_row_cap(hz_mcts *m, int32_t rows) {
+  if (!m || rows < 0) return -1;
+  m->row_cap = rows;  // host state: the next expand launches carry it (a captured one keeps its capture's)
+  return 0;
+}
+
+int hz_mcts_take_error(hz_mcts *m, int32_t *out) {
+  if (!m || !out) return -1;
+  int32_t w = 0;
+  if (hipMemcpyAsync(&w, m->err, sizeof w, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+      hipStreamSynchronize(m->stream) != hipSuccess)
+    return 1;
+  if (w && hipMemsetAsync(m->err, 0, sizeof w, m->stream) != hipSuccess) return 1;
+  *out = w;
+  return 0;
+}
+
+int hz_mcts_set_budget(hz_mcts *m, const int32_t *budget) {
+  if (!m) return -1;
+  m->budget = nullptr;
+  if (!budget) return 0;
+  if (hipMemcpyAsync(m->budget_buf, budget, (size_t)m->n * sizeof(int32_t), hipMemcpyDeviceToDevice, m->stream))
+    return 1;
+  m->budget = m->budget_buf;
+  return 0;
+}
+
+int hz_mcts_sims_done(hz_mcts *m, int32_t *out) {
+  if (!m || !out) return -1;
+  return hipMemcpyAsync(out, m->sims_done, (size_t)m->n * sizeof(int32_t), hipMemcpyDeviceToDevice, m->stream) ? 1
+                                                                                                                : 0;
+}
+
+int hz_mcts_set_root_noise_mask(hz_mcts *m, const uint8_t *mask) {
+  if (!m) return -1;
+  m->noise_mask = nullptr;
+  if (!mask) return 0;
+  if (hipMemcpyAsync(m->mask_buf, mask, (size_t)m->n * sizeof(uint8_t), hipMemcpyDeviceToDevice, m->stream)) return 1;
+  m->noise_mask = m->mask_buf;
   return 0;
 }
 

@@ -69,6 +69,11 @@ _SIGS = {
     "hz_root_noise": ([_vp, _c.c_int32, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_double, _vp, _vp, _vp],
                       _c.c_int),
     "hz_playout_coin": ([_c.c_int32, _c.c_uint64, _c.c_uint64, _c.c_uint64, _vp, _vp], _c.c_int),
+    "hz_mcts_set_row_cap": ([_vp, _c.c_int32], _c.c_int),
+    "hz_mcts_take_error": ([_vp, _vp], _c.c_int),
+    "hz_mcts_set_budget": ([_vp, _vp], _c.c_int),
+    "hz_mcts_sims_done": ([_vp, _vp], _c.c_int),
+    "hz_mcts_set_root_noise_mask": ([_vp, _vp], _c.c_int),
     "hz_mcts_stats": ([_vp, _vp], _c.c_int),
     "hz_mcts_root_edges": ([_vp] * 7, _c.c_int),
     "hz_mcts_pv": ([_vp, _c.c_int32] + [_vp] * 5, _c.c_int),

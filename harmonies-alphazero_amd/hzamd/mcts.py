@@ -23,6 +23,7 @@ the first count[0] (a device int32) are live and rows[j] is row j's board:
 no host round trip per simulation (BatchedPredictor's HIP kernels take
 count as their live-row bound).
 """
+import ctypes
 import os
 
 import torch
@@ -99,6 +100,12 @@ class BatchedMCTS:
         self.limit_hits_total = torch.zeros(1, dtype=torch.int64, device=d)
         self._nil_pol = torch.zeros(1, ACTION_SIZE, dtype=torch.float32, device=d)
         self._nil_val = torch.zeros(1, dtype=torch.float32, device=d)
+        self._sims_done = torch.zeros(self.n, dtype=torch.int32, device=d)
+        # an expand call of this search got fewer policy rows than there are
+        # boards: only then can a row lie past them, and _finish() reads the
+        # handle's error word (hz_mcts_set_row_cap)
+        self._cap_risk = False
+        self._gate = (False, False)  # (budget gate on, root-noise mask on), as last set by search()
 
     def close(self):
         if getattr(self, "_h", None):
@@ -152,6 +159,7 @@ class BatchedMCTS:
         value = value.reshape(-1).to(dtype=torch.float32).contiguous()
         if noise is not None:
             noise = noise.to(device=self.device, dtype=torch.float64).contiguous()
+        self._set_row_cap(policy, value)
         fn = nat.lib().hz_mcts_expand_backup_gathered if gathered else nat.lib().hz_mcts_expand_backup
         nat.check(fn(self._h, self.env.handle, nat.ptr(policy), nat.ptr(value), nat.ptr(noise), float(eps),
                      int(bool(testing))), "hz_mcts_expand_backup")
@@ -165,6 +173,7 @@ class BatchedMCTS:
         value = value.reshape(-1).to(dtype=torch.float32).contiguous()
         if noise is not None:
             noise = noise.to(device=self.device, dtype=torch.float64).contiguous()
+        self._set_row_cap(policy, value)
         nat.check(nat.lib().hz_mcts_expand_backup_select(self._h, self.env.handle, nat.ptr(policy), nat.ptr(value),
                                                          nat.ptr(noise), float(eps), int(bool(testing)),
                                                          nat.ptr(active), float(cpuct)),
@@ -183,14 +192,52 @@ class BatchedMCTS:
         value = value.reshape(-1).to(dtype=torch.float32).contiguous()
         if noise is not None:
             noise = noise.to(device=self.device, dtype=torch.float64).contiguous()
+        self._set_row_cap(policy, value)
         nat.check(nat.lib().hz_mcts_expand_backup_select_gather(
             self._h, self.env.handle, nat.ptr(policy), nat.ptr(value), nat.ptr(noise), float(eps), int(bool(testing)),
             nat.ptr(active), float(cpuct), nat.ptr(self.board), nat.ptr(self.glob), nat.ptr(self.rows),
             nat.ptr(count_out), nat.ptr(count_prev), int(bool(add_prev))), "hz_mcts_expand_backup_select_gather")
 
+    def _set_row_cap(self, policy, value):
+        """Before every expand call: the kernel may read rows [0, cap) of
+        policy and value and no others (hz_mcts_set_row_cap); captured into a
+        graph, the cap is the capture's max_rows."""
+        cap = min(int(policy.shape[0]), int(value.numel()))
+        if not hasattr(nat.lib(), "hz_mcts_set_row_cap"):
+            return  # (an older A/B build named by HZ_LIB: unchecked, as it was)
+        nat.check(nat.lib().hz_mcts_set_row_cap(self._h, cap), "hz_mcts_set_row_cap")
+        if cap < self.n:
+            self._cap_risk = True
+
     def result(self):
         nat.check(nat.lib().hz_mcts_result(self._h, nat.ptr(self.visits)), "hz_mcts_result")
         return self.visits
+
+    def sims_done(self):
+        """Device int32 [n]: the simulations each board had in the last search
+        under a budget (hz_mcts_sims_done): min(budget, sims) where it was
+        searched, 0 on boards left out, on stuck roots and in a search
+        without a budget.  The handle's own tensor, rewritten by the next call."""
+        nat.check(nat.lib().hz_mcts_sims_done(self._h, nat.ptr(self._sims_done)), "hz_mcts_sims_done")
+        return self._sims_done
+
+    def _set_gate(self, budget, root_noise):
+        """The budget gate and the root-noise mask of the search about to
+        begin (None: off), copied into the handle in stream order."""
+        L = nat.lib()
+        if budget is None and root_noise is None and not hasattr(L, "hz_mcts_set_budget"):
+            return  # (an older A/B build named by HZ_LIB: it has no gate to clear)
+        if budget is not None:
+            budget = budget.to(device=self.device, dtype=torch.int32).contiguous()
+            if budget.shape != (self.n,):
+                raise ValueError(f"budget of shape {tuple(budget.shape)}, not ({self.n},)")
+        if root_noise is not None:
+            root_noise = root_noise.to(device=self.device, dtype=torch.uint8).contiguous()
+            if root_noise.shape != (self.n,):
+                raise ValueError(f"root_noise of shape {tuple(root_noise.shape)}, not ({self.n},)")
+        nat.check(L.hz_mcts_set_budget(self._h, nat.ptr(budget)), "hz_mcts_set_budget")
+        nat.check(L.hz_mcts_set_root_noise_mask(self._h, nat.ptr(root_noise)), "hz_mcts_set_root_noise_mask")
+        self._gate = (budget is not None, root_noise is not None)
 
     def stats(self):
         nat.check(nat.lib().hz_mcts_stats(self._h, nat.ptr(self.counts)), "hz_mcts_stats")
@@ -316,7 +363,7 @@ class BatchedMCTS:
         return g
 
     def search(self, evaluator, cpuct, active=None, noise=None, eps=0.25, testing=True, sims=None,
-               gather=True, graph=False, max_rows=None):
+               gather=True, graph=False, max_rows=None, budget=None, root_noise=None, tail=None):
         """get_best_action_and_pi's simulation loop (MCTS.py:288-352) for every
         active board; returns root visit counts int32 [n, 143].
 
@@ -334,32 +381,67 @@ class BatchedMCTS:
         max_rows (host int, device-row evaluators): an upper bound on the
         leaves a simulation can gather (e.g. the number of active boards);
         the evaluator then gets the first max_rows rows of the buffers, so
-        its kernels are sized (and the small-batch conv form chosen) by it."""
+        its kernels are sized (and the small-batch conv form chosen) by it.
+        A bound below a simulation's leaves is an error, not a read past the
+        evaluator's outputs: NativeError at the end of the search.
+
+        budget (int32 [n], optional): board b gets min(budget[b], sims)
+        simulations (hz_mcts_set_budget) and is, bit for bit, the search of
+        that many; sims_done() has the counts.  None: no gate (a handle
+        reused after a budgeted search searches in full).
+        root_noise (bool / uint8 [n], optional): the root mix only where set;
+        a board with 0 searches as testing=True does.
+
+        tail = (s0, k) (host ints, device-row evaluators): the caller's promise
+        that from simulation s0 on (counted from 0) at most k leaves are live,
+        e.g. once every board of a smaller budget is spent; from there the
+        evaluator gets the first min(max_rows, k) rows.  With graph=True the
+        tail is a second captured simulation.  A broken promise raises like a
+        wrong max_rows."""
         if active is not None:
             active = active.to(device=self.device, dtype=torch.uint8).contiguous()
+        self._sync()
+        self._set_gate(budget, root_noise)
         self.begin(active)
         self.eval_rows.zero_()
+        self._cap_risk = False
         device_rows = bool(getattr(evaluator, "device_rows", False))
         total = self.num_simulations if sims is None else int(sims)
+        s0, tail_rows = total, max_rows
+        if tail is not None and device_rows:
+            s0 = max(0, int(tail[0]))
+            tail_rows = max(1, min(self.n if max_rows is None else int(max_rows), int(tail[1])))
         if graph and gather and device_rows and getattr(evaluator, "capturable", False) and total > 1:
-            self._device_step(evaluator, cpuct, active, noise, eps, testing, max_rows)
+            self._device_step(evaluator, cpuct, active, noise, eps, testing, max_rows if s0 > 0 else tail_rows)
             # an evaluator with a graph_key (the network object and its weight
             # generation) lets the captured simulation be kept for the next
             # search with the same settings (the drop-in's one search per move);
             # only without an `active` mask, whose tensor the graph would bake in
             gk = getattr(evaluator, "graph_key", None)
+            # (a capture holds the handle by value: whether the gate and the
+            # mask are on, and each step's row cap, belong to the key)
+            head = min(max(s0 - 1, 0), total - 1)  # replays before the tail (simulation 0 ran eagerly)
+            steps = ((max_rows, head), (tail_rows, total - 1 - head))
             key = None if gk is None or active is not None else (
-                id(gk[0]), gk[1], float(cpuct), float(eps), bool(testing), max_rows)
+                id(gk[0]), gk[1], float(cpuct), float(eps), bool(testing), self._gate)
             cached = self._graph_cache
-            if key is not None and cached is not None and cached[0] == key:
-                g = cached[1]
-            else:
-                self._graph_cache = None
-                g = self._capture_step(evaluator, cpuct, active, eps, testing, max_rows)
-                if key is not None:
-                    self._graph_cache = (key, g, gk[0])  # holds the network: its id stays unique
-            for _ in range(total - 1):
-                g.replay()
+            if key is None or cached is None or cached[0] != key:
+                cached = self._graph_cache = None
+            graphs = {} if cached is None else cached[1]
+            wanted = {rows for rows, times in steps if times}
+            if len(wanted | set(graphs)) > 4:  # (row bounds that change from search to search: keep a few)
+                for rows in set(graphs) - wanted:
+                    del graphs[rows]
+            for rows, times in steps:
+                if times and rows not in graphs:
+                    graphs[rows] = self._capture_step(evaluator, cpuct, active, eps, testing, rows)
+            if key is not None and cached is None:
+                self._graph_cache = (key, graphs, gk[0])  # holds the network: its id stays unique
+            for rows, times in steps:
+                if times and rows is not None and rows < self.n:
+                    self._cap_risk = True  # (a cached capture: no expand call of this search set it)
+                for _ in range(times):
+                    graphs[rows].replay()
             return self._finish()
         if gather and total > 1 and self.n > 32 and self.fuse_select:
             # the next simulation's select rides in each expand/backup launch
@@ -375,7 +457,8 @@ class BatchedMCTS:
             board, glob, rows, count = self.select_gather(cpuct, active)
             bufs, cur = (self.count, self.count_b), 0
             for s in range(total):
-                policy, value = self._evaluate(evaluator, device_rows, board, glob, rows, count, max_rows)
+                policy, value = self._evaluate(evaluator, device_rows, board, glob, rows, count,
+                                               max_rows if s < s0 else tail_rows)
                 if s + 1 < total:
                     if fuse_gather:
                         self.expand_backup_select_gather(policy, value, cpuct, active, noise, eps, testing,
@@ -391,7 +474,7 @@ class BatchedMCTS:
                 self.eval_rows += count
                 count.zero_()
             return self._finish()
-        for _ in range(total):
+        for s in range(total):
             if not gather:
                 self.select(cpuct, active)
                 board, glob = self.encode_leaves()
@@ -400,7 +483,8 @@ class BatchedMCTS:
                 self.expand_backup(policy, value, noise, eps, testing)
                 continue
             board, glob, rows, count = self.select_gather(cpuct, active)  # (adds count to eval_rows)
-            policy, value = self._evaluate(evaluator, device_rows, board, glob, rows, count, max_rows)
+            policy, value = self._evaluate(evaluator, device_rows, board, glob, rows, count,
+                                           max_rows if s < s0 else tail_rows)
             self.expand_backup(policy, value, noise, eps, testing, gathered=True)
         return self._finish()
 
@@ -417,7 +501,9 @@ class BatchedMCTS:
     def _finish(self):
         """Root visits of the search just run, after making sure no leaf
         evaluation of it went through a timed-out split-tower hand-off (whose
-        NaN priors would have steered PUCT silently): NativeError if one did."""
+        NaN priors would have steered PUCT silently): NativeError if one did;
+        and, where an expand call had fewer rows than boards, that no board's
+        row lay past them (the handle's error word: one read per search)."""
         from .infer import check_split_timeouts
         self.eval_rows_total += self.eval_rows
         if self.count_edges:
@@ -428,6 +514,12 @@ class BatchedMCTS:
         if self.count_path:
             nat.check(nat.lib().hz_mcts_path_edges(self._h, nat.ptr(self.path_total)), "hz_mcts_path_edges")
         visits = self.result()
+        if self._cap_risk:
+            self._cap_risk = False
+            word = ctypes.c_int32(0)
+            nat.check(nat.lib().hz_mcts_take_error(self._h, ctypes.byref(word)), "hz_mcts_take_error")
+            if word.value:  # (cleared by the call: the next search starts clean)
+                raise nat.NativeError("leaf batch larger than the evaluator's rows")
         check_split_timeouts(self.device)
         return visits
 

@@ -13,6 +13,14 @@ Records stay on the device in compact form: state words int64 [T, 6, n],
 player int8 [T, n], visit counts int32 [T, n, 143], valid bool [T, n].
 `examples()` turns them into the reference's example tuples
 (board f32[38,5,7], glob f32[42], pi f32[143], z f32[1]).
+
+Playout-cap randomization (no reference counterpart; config keys
+`playout_cap_p` and `playout_cap_fast`, both absent by default): each move a
+coin per board (NoiseSource.coin) decides whether the board is searched in
+full (`num_simulations`, root noise; probability p) or fast
+(`playout_cap_fast` simulations, no noise) through BatchedMCTS.search's
+per-board budgets; the move is chosen as always, the records gain `full`,
+and only the full moves become training records.
 """
 import torch
 
@@ -24,6 +32,16 @@ MCTS_DEFAULT = {  # config.py:53-65 (the self-play config)
     "num_simulations": 400, "cpuct": 2, "dirichlet_alpha": 0.4, "dirichlet_epsilon": 0.25,
     "fpu_value": 0.25, "turns_until_tau0": 15, "action_size": 143, "testing": False,
 }
+
+
+def playout_budgets(coin, p, full_sims, fast_sims):
+    """The playout-cap rule for one move: (budget int32 [n], full bool [n])
+    from the boards' coins in (0, 1] (NoiseSource.coin).  A board is full iff
+    its coin is below p (a coin equal to p is not), and every board is at
+    p >= 1; full boards get full_sims simulations, the others fast_sims."""
+    full = coin < float(p) if float(p) < 1.0 else torch.ones_like(coin, dtype=torch.bool)
+    budget = torch.where(full, int(full_sims), int(fast_sims)).to(torch.int32)
+    return budget, full
 
 
 class NoiseSource:
@@ -84,9 +102,21 @@ class SelfPlay:
         # through a pinned buffer and an event recorded after that step
         self._n_active = self.n  # an upper bound on the active boards (sizes the network's launches) ...
         self._n_active_epoch = -1  # ... while the env's epoch (no game started since) is this
-        self._flags = torch.zeros(2, dtype=torch.int64, pin_memory=self.device.type == "cuda")
+        self._flags = torch.zeros(3, dtype=torch.int64, pin_memory=self.device.type == "cuda")
         self._flags_ev = None
         self._bad_dev = None
+        # playout caps: on when both keys are given
+        p, fast = self.cfg.get("playout_cap_p"), self.cfg.get("playout_cap_fast")
+        if (p is None) != (fast is None):
+            raise ValueError("playout_cap_p and playout_cap_fast go together")
+        self.playout_cap = None if p is None else (float(p), int(fast))
+        if self.playout_cap and not (0.0 <= self.playout_cap[0] <= 1.0 and self.playout_cap[1] >= 0):
+            raise ValueError(f"playout cap {self.playout_cap}: p outside 0..1 or a negative fast budget")
+        self.last_full = None  # bool [n] of the last move(): searched in full
+        # full boards of coming moves by move counter, an upper bound each (the
+        # coin of move k + 2 is drawn at move k and its count rides in _flags)
+        self._full_bound = {}
+        self._flags_full_step = None
 
     def move(self, ply, done=None, _bound=None):
         """One ply for every board that is still playing: search, choose,
@@ -113,8 +143,19 @@ class SelfPlay:
         # the leaf batch holds at most one row per active board: size the
         # network's launches by that (late in the games most boards are done);
         # an upper bound from an earlier move, so no host read waits here
+        step = self.step_counter - 1  # this move's counter
+        budget = full = tail = None
+        if self.playout_cap:
+            p, fast = self.playout_cap
+            budget, full = playout_budgets(self.noise.coin(step, n), p, cfg["num_simulations"], fast)
+            # once the fast boards are spent only full boards have leaves
+            k = self._full_bound.pop(step, None)
+            if k is not None and fast < cfg["num_simulations"]:
+                tail = (fast, k)
+            self.last_full = full
         v = self.mcts.search(self.evaluator, cfg["cpuct"], active=active, noise=noise,
-                             eps=cfg["dirichlet_epsilon"], testing=testing, max_rows=max(1, bound))
+                             eps=cfg["dirichlet_epsilon"], testing=testing, max_rows=max(1, bound),
+                             budget=budget, root_noise=full, tail=tail)
         if self.keep_root_value:
             self.last_root_value = self.mcts.root_edges()["value"]
         self.check_steps()  # the previous move's step, done long before this search runs
@@ -129,8 +170,15 @@ class SelfPlay:
         status = env.step(act)
         bad = active & (status != 0)
         # read back by the next move (or check_steps()) after its search is queued
-        flags = torch.stack([bad.sum(dtype=torch.int64), (~env.done()).sum(dtype=torch.int64)])
-        self._flags.copy_(flags, non_blocking=True)
+        # (with playout caps: the full boards of the move after next, whose
+        # coin depends on (seed, board, move) alone; the next move's search is
+        # queued before these flags are read)
+        flags = [bad.sum(dtype=torch.int64), (~env.done()).sum(dtype=torch.int64)]
+        if self.playout_cap:
+            flags.append(playout_budgets(self.noise.coin(step + 2, n), self.playout_cap[0], 1, 0)[1]
+                         .sum(dtype=torch.int64))
+            self._flags_full_step = step + 2
+        self._flags[:len(flags)].copy_(torch.stack(flags), non_blocking=True)
         self._flags_ev = torch.cuda.Event() if d.type == "cuda" else None
         if self._flags_ev is not None:
             self._flags_ev.record()
@@ -148,8 +196,10 @@ class SelfPlay:
             return
         if self._flags_ev is not None:
             self._flags_ev.synchronize()
-        nbad, nact = (int(x) for x in self._flags.tolist())
+        nbad, nact, nfull = (int(x) for x in self._flags.tolist())
         bad, self._bad_dev = self._bad_dev, None
+        if self.playout_cap:
+            self._full_bound = {self._flags_full_step: nfull}
         self._n_active, self._n_active_epoch = nact, self._flags_epoch
         if nbad:
             raise RuntimeError(f"self-play step failed on boards {torch.nonzero(bad).flatten().tolist()[:8]}")
@@ -165,6 +215,7 @@ class SelfPlay:
         visits = torch.zeros(T, n, 143, dtype=torch.int32, device=d)
         valid = torch.zeros(T, n, dtype=torch.bool, device=d)
         root_value = torch.zeros(T, n, dtype=torch.float64, device=d) if self.keep_root_value else None
+        full = torch.zeros(T, n, dtype=torch.bool, device=d) if self.playout_cap else None
         done = env.done()
         ply = 0
         while ply < T:
@@ -179,6 +230,8 @@ class SelfPlay:
             visits[ply] = v
             if root_value is not None:
                 root_value[ply] = self.last_root_value
+            if full is not None:
+                full[ply] = self.last_full
             done = env.done()
             ply += 1
         self.check_steps()
@@ -187,6 +240,8 @@ class SelfPlay:
                "valid": valid[:ply], "final": final, "plies": ply}
         if root_value is not None:
             rec["root_value"] = root_value[:ply]  # f64 [T, n], from the recorded player's side
+        if full is not None:
+            rec["full"] = full[:ply]  # bool [T, n]: the move was searched in full (playout caps)
         return rec
 
     def play_steady(self, moves, reset=True, progress=None):
@@ -217,6 +272,7 @@ class SelfPlay:
         plies = torch.zeros(M, n, dtype=torch.int16, device=d)
         none = torch.zeros(n, dtype=torch.bool, device=d)
         root_value = torch.zeros(M, n, dtype=torch.float64, device=d) if self.keep_root_value else None
+        full = torch.zeros(M, n, dtype=torch.bool, device=d) if self.playout_cap else None
         for m in range(M):
             self._n_active, self._n_active_epoch = n, env.epoch
             st, v, _ = self.move(ply, none, _bound=n)
@@ -224,6 +280,8 @@ class SelfPlay:
             visits[m] = v
             if root_value is not None:
                 root_value[m] = self.last_root_value
+            if full is not None:
+                full[m] = self.last_full
             games[m] = game.to(torch.int32)
             fin = env.export_state()
             over = env.done()
@@ -243,14 +301,24 @@ class SelfPlay:
                "outcome": outcome, "plies": plies, "moves": M}
         if root_value is not None:
             rec["root_value"] = root_value  # f64 [M, n], from the recorded player's side
+        if full is not None:
+            rec["full"] = full  # bool [M, n]: the move was searched in full (playout caps)
         return rec
 
-    def compact_steady(self, rec):
+    def _full_only(self, rec, full_only):
+        """The records' full-search mask when only those become training
+        records (the default with playout caps on), else None."""
+        if full_only is None:
+            full_only = self.playout_cap is not None
+        return rec["full"] if full_only and "full" in rec else None
+
+    def compact_steady(self, rec, full_only=None):
         """play_steady's records of the games that ended inside the run, in
         (move, board) order: as compact() (states, visits, pi, z from the
         recorded player's side, player, board), plus each record's game
         index, and per ended game its length (`lengths`: plies); with
-        keep_root_value also q f32 [M], as compact()."""
+        keep_root_value also q f32 [M], as compact().  full_only (default:
+        playout caps on): only the moves searched in full give records."""
         M, n, d = rec["moves"], self.n, self.device
         game = rec["game"].to(torch.int64)                         # [M, n]
         K = int(game.max().item()) + 1 if M else 1
@@ -261,6 +329,9 @@ class SelfPlay:
         res[key[em]] = rec["outcome"][em]
         has[key[em]] = True
         mask = has[key]                                            # records of ended games
+        full = self._full_only(rec, full_only)
+        if full is not None:
+            mask = mask & full
         player = rec["players"].to(torch.float32)
         out = res[key]
         z = torch.where(player == 0, out, -out)
@@ -280,15 +351,20 @@ class SelfPlay:
         win = (final[5] >> 46) & 3
         return torch.where(win == 1, 1, torch.where(win == 2, -1, 0)).to(torch.float32)
 
-    def compact(self, rec):
+    def compact(self, rec, full_only=None):
         """Flatten the valid records: states int64 [M, 6], visits int32
         [M, 143], pi f32 [M, 143], z f32 [M] (trainer.py:517-538), player
         int8 [M], board id int32 [M]; from records kept with keep_root_value
         also q f32 [M], the search's root value from the recorded player's
-        side like z (the recorded player is the root's mover)."""
+        side like z (the recorded player is the root's mover).  full_only
+        (default: playout caps on): only the moves searched in full give
+        records (rec["full"])."""
         out = self.outcomes(rec["final"])                       # [n]
         T = rec["plies"]
         mask = rec["valid"]                                      # [T, n]
+        full = self._full_only(rec, full_only)
+        if full is not None:
+            mask = mask & full
         player = rec["players"].to(torch.float32)
         z = torch.where(player == 0, out.unsqueeze(0), -out.unsqueeze(0))  # 0 stays 0 for draws
         states = rec["states"].permute(0, 2, 1)[mask]            # [M, 6]

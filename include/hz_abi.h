@@ -338,6 +338,46 @@ int hz_root_noise(const int32_t *count, int32_t n, uint64_t seed, uint64_t board
  * noise and u are what they were and a board's coin depends on nothing but
  * (seed, global board id, move).  Enqueued on `stream`. */
 int hz_playout_coin(int32_t n, uint64_t seed, uint64_t board_base, uint64_t move, double *coin, void *stream);
+/* ---- row capacity of the evaluator's outputs (no reference counterpart) -----
+ * rows = the number of rows of the policy / value tensors the next expand
+ * calls get (all four forms); 0 = unchecked.  Host state only: nothing is
+ * launched, a launch carries the value set before it, and a launch captured in
+ * a HIP graph keeps its capture's.  A board whose row (its own index, or its
+ * row of the gathered batch) is at or past the cap reads neither tensor,
+ * expands nothing, backs up nothing and sets bit 0 of the handle's device
+ * error word.  hz_mcts_take_error waits for the handle's stream, stores the
+ * word in *out (host) and clears it: a wrong bound is an error the caller
+ * sees, never a read past the tensors. */
+int hz_mcts_set_row_cap(hz_mcts *mcts, int32_t rows);
+int hz_mcts_take_error(hz_mcts *mcts, int32_t *out);
+/* ---- per-board simulation budgets (no reference counterpart) ----------------
+ * budget[n] (device int32; copied into the handle in stream order) gives
+ * board b at most budget[b] simulations per search; NULL turns the gate off
+ * (the default).  Under the gate every select (hz_mcts_select,
+ * hz_mcts_select_gather and the select inside hz_mcts_expand_backup_select /
+ * _select_gather) walks board b only if it is active, has a tree and has had
+ * fewer than budget[b] simulations since hz_mcts_begin, and counts the walk; a
+ * spent board has no leaf: it takes no leaf row, draws nothing from its stream
+ * and backs up nothing.  A refused expansion (max_nodes, max_depth) counts as
+ * a simulation; a negative budget is 0; a budget above the number of sim steps
+ * the caller runs is never reached.  hz_mcts_begin zeroes the counts, and
+ * gives a stuck root (no legal move, game not over) budget 0 in the handle's
+ * copy: its simulations would change nothing.  Call hz_mcts_set_budget before
+ * the hz_mcts_begin of each search.  hz_mcts_sims_done copies the counts to
+ * out[n] (device): 0 for boards left out and while the gate is off.
+ * hz_mcts_set_root_noise_mask: mask[n] (device uint8, copied; NULL = every
+ * board, the default): the root Dirichlet mix is applied to board b only if
+ * mask[b] != 0 (and !testing and noise != NULL, as before).
+ * The handle's buffers keep their addresses, so a captured simulation stays
+ * valid while budgets and mask change; whether the gate and the mask are on
+ * is part of what a capture holds.
+ * Exactness: under the gate, a board with budget k and mask bit r after S sim
+ * steps is bit for bit the search of min(k, S) simulations with testing = !r
+ * (MCTS.py:288-352; the oracle's mcts_search(sims = min(k, S))): visits, node
+ * and edge counts, limit flag and the board's stream. */
+int hz_mcts_set_budget(hz_mcts *mcts, const int32_t *budget);
+int hz_mcts_sims_done(hz_mcts *mcts, int32_t *out);
+int hz_mcts_set_root_noise_mask(hz_mcts *mcts, const uint8_t *mask);
 /* root visit counts by action id: visits[n][143] (MCTS.py:355-376) */
 int hz_mcts_result(hz_mcts *mcts, int32_t *visits);
 /* per-board [nodes, edges, search generation, limit flag] -> counts[n][4].
