@@ -106,6 +106,12 @@ class BatchedMCTS:
         # handle's error word (hz_mcts_set_row_cap)
         self._cap_risk = False
         self._gate = (False, False)  # (budget gate on, root-noise mask on), as last set by search()
+        # tree reuse (advance() / search(carry=True)): advance's info rows, and
+        # the edges and walked levels the search began with (count_edges and
+        # count_path add only what the search itself made)
+        self._carry_info = torch.zeros(self.n, 3, dtype=torch.int32, device=d)
+        self._edges_base = None
+        self._path_base = None
 
     def close(self):
         if getattr(self, "_h", None):
@@ -127,6 +133,43 @@ class BatchedMCTS:
     def begin(self, active=None):
         self._sync()
         nat.check(nat.lib().hz_mcts_begin(self._h, self.env.handle, nat.ptr(active)), "hz_mcts_begin")
+
+    def begin_carried(self, active=None, noise=None, eps=0.25, testing=True):
+        """begin() that keeps the trees advance() carried (hz_mcts_begin_carried):
+        a carried board whose node 0 still is the env's state starts from its
+        tree, its expanded root's priors mixed with the noise where the board
+        is noisy; every other active board starts fresh.  The carry is consumed."""
+        self._sync()
+        if noise is not None:
+            noise = noise.to(device=self.device, dtype=torch.float64).contiguous()
+        nat.check(nat.lib().hz_mcts_begin_carried(self._h, self.env.handle, nat.ptr(active), nat.ptr(noise),
+                                                  float(eps), int(bool(testing))), "hz_mcts_begin_carried")
+
+    def advance(self, action, active=None, headroom=None):
+        """Tree reuse, after env.step(action): each board keeps the subtree
+        below the move just played as the start of its next search
+        (hz_mcts_advance, whose rule include/hz_abi.h states), or drops its
+        tree: an inactive board, a move without a root edge, a terminal child,
+        a child whose state is not the env's (a turn end whose draws differ), or
+        a kept tree that leaves less than `headroom` free nodes or edges
+        (default 69 * num_simulations: the next search cannot hit max_nodes).
+        Returns device int32 [n] tensors {"nodes", "edges", "visits"} (kept
+        nodes, kept edges, the new root's visits; zeros where dropped): views
+        of the handle's own buffer, rewritten by the next call.  The carry is
+        taken up by the next search(carry=True) only."""
+        self._sync()
+        action = action.to(device=self.device, dtype=torch.int16).contiguous()
+        if action.shape != (self.n,):
+            raise ValueError(f"action of shape {tuple(action.shape)}, not ({self.n},)")
+        if active is not None:
+            active = active.to(device=self.device, dtype=torch.uint8).contiguous()
+        headroom = MAX_CHILDREN * self.num_simulations if headroom is None else int(headroom)
+        if headroom < 0:
+            raise ValueError(f"headroom {headroom} below 0")
+        nat.check(nat.lib().hz_mcts_advance(self._h, self.env.handle, nat.ptr(action), nat.ptr(active), headroom,
+                                            nat.ptr(self._carry_info)), "hz_mcts_advance")
+        info = self._carry_info
+        return {"nodes": info[:, 0], "edges": info[:, 1], "visits": info[:, 2]}
 
     def select(self, cpuct, active=None):
         nat.check(nat.lib().hz_mcts_select(self._h, nat.ptr(active), float(cpuct)), "hz_mcts_select")
@@ -363,7 +406,7 @@ class BatchedMCTS:
         return g
 
     def search(self, evaluator, cpuct, active=None, noise=None, eps=0.25, testing=True, sims=None,
-               gather=True, graph=False, max_rows=None, budget=None, root_noise=None, tail=None):
+               gather=True, graph=False, max_rows=None, budget=None, root_noise=None, tail=None, carry=False):
         """get_best_action_and_pi's simulation loop (MCTS.py:288-352) for every
         active board; returns root visit counts int32 [n, 143].
 
@@ -397,12 +440,26 @@ class BatchedMCTS:
         e.g. once every board of a smaller budget is spent; from there the
         evaluator gets the first min(max_rows, k) rows.  With graph=True the
         tail is a second captured simulation.  A broken promise raises like a
-        wrong max_rows."""
+        wrong max_rows.
+
+        carry: start from the trees the last advance() kept (begin_carried)
+        instead of empty ones; `sims` (or the budgets) count the new
+        simulations, the visits returned include the carried ones.  The
+        simulations themselves are the same launches in every search form."""
         if active is not None:
             active = active.to(device=self.device, dtype=torch.uint8).contiguous()
         self._sync()
         self._set_gate(budget, root_noise)
-        self.begin(active)
+        self._edges_base = self._path_base = None
+        if carry:
+            self.begin_carried(active, noise, eps, testing)
+            if self.count_edges:
+                self._edges_base = self.stats()[:, 1].sum(dtype=torch.int64)
+            if self.count_path:  # the carried trees' edge visits: levels earlier searches walked
+                self._path_base = torch.zeros(1, dtype=torch.int64, device=self.device)
+                nat.check(nat.lib().hz_mcts_path_edges(self._h, nat.ptr(self._path_base)), "hz_mcts_path_edges")
+        else:
+            self.begin(active)
         self.eval_rows.zero_()
         self._cap_risk = False
         device_rows = bool(getattr(evaluator, "device_rows", False))
@@ -508,11 +565,15 @@ class BatchedMCTS:
         self.eval_rows_total += self.eval_rows
         if self.count_edges:
             self.edges_total += self.stats()[:, 1].sum(dtype=torch.int64)
+            if self._edges_base is not None:  # a carried search: only the edges it created
+                self.edges_total -= self._edges_base
         if self.bounded:
             c = self.stats()  # (a board left out of this search has no nodes and keeps its last flag)
             self.limit_hits_total += ((c[:, 3] != 0) & (c[:, 0] > 0)).sum(dtype=torch.int64)
         if self.count_path:
             nat.check(nat.lib().hz_mcts_path_edges(self._h, nat.ptr(self.path_total)), "hz_mcts_path_edges")
+            if self._path_base is not None:  # a carried search: only the levels it walked
+                self.path_total -= self._path_base
         visits = self.result()
         if self._cap_risk:
             self._cap_risk = False

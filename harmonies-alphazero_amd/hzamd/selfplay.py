@@ -21,6 +21,15 @@ full (`num_simulations`, root noise; probability p) or fast
 (`playout_cap_fast` simulations, no noise) through BatchedMCTS.search's
 per-board budgets; the move is chosen as always, the records gain `full`,
 and only the full moves become training records.
+
+Tree reuse (no reference counterpart; config key `tree_reuse`, absent by
+default): after each step the search handle keeps the subtree below the move
+just played (BatchedMCTS.advance, whose rule include/hz_abi.h states) and the
+next move's search starts from it.  "add" runs `num_simulations` new
+simulations on top; "topup" gives board b
+clamp(num_simulations - carried visits, tree_reuse_min_sims, num_simulations)
+through the per-board budgets.  Visit counts and pi include the carried
+visits; the records gain `carried`.
 """
 import torch
 
@@ -32,6 +41,13 @@ MCTS_DEFAULT = {  # config.py:53-65 (the self-play config)
     "num_simulations": 400, "cpuct": 2, "dirichlet_alpha": 0.4, "dirichlet_epsilon": 0.25,
     "fpu_value": 0.25, "turns_until_tau0": 15, "action_size": 143, "testing": False,
 }
+
+
+def topup_budgets(carried, num_simulations, min_sims):
+    """The "topup" rule of tree reuse for one move: budget int32 [n] =
+    clamp(num_simulations - carried visits, min_sims, num_simulations)."""
+    left = int(num_simulations) - carried.to(torch.int64)
+    return left.clamp(min(int(min_sims), int(num_simulations)), int(num_simulations)).to(torch.int32)
 
 
 def playout_budgets(coin, p, full_sims, fast_sims):
@@ -85,7 +101,22 @@ class SelfPlay:
         self.env = env or BatchedEnv(n_boards, seed_base=seed_base, device=self.device)
         self.n = self.env.n
         self.evaluator = evaluator
-        self.mcts = BatchedMCTS(self.env, self.cfg["num_simulations"], exact_keys=exact_keys)
+        # tree reuse: on when the key is given; the pools get room for a carried tree
+        # next to a whole search (a kept tree that leaves less is dropped, so no search overflows)
+        self.tree_reuse = self.cfg.get("tree_reuse")
+        if self.tree_reuse not in (None, "add", "topup"):
+            raise ValueError(f"tree_reuse {self.tree_reuse!r}: not 'add' or 'topup'")
+        self.reuse_min_sims = int(self.cfg.get("tree_reuse_min_sims", 1))
+        pool = float(self.cfg.get("tree_reuse_pool", 2.0))
+        if self.tree_reuse and (pool < 1.0 or self.reuse_min_sims < 0):
+            raise ValueError("tree_reuse_pool below 1 or a negative tree_reuse_min_sims")
+        if self.tree_reuse and (self.cfg.get("playout_cap_p") is not None or
+                                self.cfg.get("playout_cap_fast") is not None):
+            raise ValueError("tree_reuse and playout caps do not combine")
+        max_nodes = int(pool * (1 + MAX_CHILDREN * self.cfg["num_simulations"])) if self.tree_reuse else None
+        self.mcts = BatchedMCTS(self.env, self.cfg["num_simulations"], max_nodes=max_nodes, exact_keys=exact_keys)
+        self._carried = None  # (state words after the last step, the visits advance() kept), with tree reuse
+        self.last_carried = None  # int32 [n] of the last move(): the root visits its search started with
         self.max_plies = int(max_plies)
         self.noise = NoiseSource(seed_base, self.device)
         self.keep_noise = False
@@ -153,9 +184,21 @@ class SelfPlay:
             if k is not None and fast < cfg["num_simulations"]:
                 tail = (fast, k)
             self.last_full = full
+        if self.tree_reuse:
+            # the visits carried into this search: the last advance()'s, where the
+            # board still is in the state that step left (the handle makes the same
+            # check: a reset or import in between starts the board fresh)
+            if self._carried is None:
+                carried = torch.zeros(n, dtype=torch.int32, device=d)
+            else:
+                same = (st == self._carried[0]).all(0) & active
+                carried = torch.where(same, self._carried[1], torch.zeros_like(self._carried[1]))
+            self.last_carried = carried
+            if self.tree_reuse == "topup":
+                budget = topup_budgets(carried, cfg["num_simulations"], self.reuse_min_sims)
         v = self.mcts.search(self.evaluator, cfg["cpuct"], active=active, noise=noise,
                              eps=cfg["dirichlet_epsilon"], testing=testing, max_rows=max(1, bound),
-                             budget=budget, root_noise=full, tail=tail)
+                             budget=budget, root_noise=full, tail=tail, carry=self.tree_reuse is not None)
         if self.keep_root_value:
             self.last_root_value = self.mcts.root_edges()["value"]
         self.check_steps()  # the previous move's step, done long before this search runs
@@ -168,6 +211,8 @@ class SelfPlay:
             self.noise_log.append((noise.clone(), u.clone(), act.clone()))
         act = torch.where(active, act, torch.full_like(act, -1)).to(torch.int16)
         status = env.step(act)
+        if self.tree_reuse:
+            self._carried = (env.export_state(), self.mcts.advance(act, active)["visits"].clone())
         bad = active & (status != 0)
         # read back by the next move (or check_steps()) after its search is queued
         # (with playout caps: the full boards of the move after next, whose
@@ -216,6 +261,7 @@ class SelfPlay:
         valid = torch.zeros(T, n, dtype=torch.bool, device=d)
         root_value = torch.zeros(T, n, dtype=torch.float64, device=d) if self.keep_root_value else None
         full = torch.zeros(T, n, dtype=torch.bool, device=d) if self.playout_cap else None
+        carried = torch.zeros(T, n, dtype=torch.int32, device=d) if self.tree_reuse else None
         done = env.done()
         ply = 0
         while ply < T:
@@ -232,6 +278,8 @@ class SelfPlay:
                 root_value[ply] = self.last_root_value
             if full is not None:
                 full[ply] = self.last_full
+            if carried is not None:
+                carried[ply] = self.last_carried
             done = env.done()
             ply += 1
         self.check_steps()
@@ -242,6 +290,8 @@ class SelfPlay:
             rec["root_value"] = root_value[:ply]  # f64 [T, n], from the recorded player's side
         if full is not None:
             rec["full"] = full[:ply]  # bool [T, n]: the move was searched in full (playout caps)
+        if carried is not None:
+            rec["carried"] = carried[:ply]  # int32 [T, n]: the root visits the search started with (tree reuse)
         return rec
 
     def play_steady(self, moves, reset=True, progress=None):
@@ -273,6 +323,7 @@ class SelfPlay:
         none = torch.zeros(n, dtype=torch.bool, device=d)
         root_value = torch.zeros(M, n, dtype=torch.float64, device=d) if self.keep_root_value else None
         full = torch.zeros(M, n, dtype=torch.bool, device=d) if self.playout_cap else None
+        carried = torch.zeros(M, n, dtype=torch.int32, device=d) if self.tree_reuse else None
         for m in range(M):
             self._n_active, self._n_active_epoch = n, env.epoch
             st, v, _ = self.move(ply, none, _bound=n)
@@ -282,6 +333,8 @@ class SelfPlay:
                 root_value[m] = self.last_root_value
             if full is not None:
                 full[m] = self.last_full
+            if carried is not None:
+                carried[m] = self.last_carried
             games[m] = game.to(torch.int32)
             fin = env.export_state()
             over = env.done()
@@ -303,6 +356,8 @@ class SelfPlay:
             rec["root_value"] = root_value  # f64 [M, n], from the recorded player's side
         if full is not None:
             rec["full"] = full  # bool [M, n]: the move was searched in full (playout caps)
+        if carried is not None:
+            rec["carried"] = carried  # int32 [M, n]: the root visits the search started with (tree reuse)
         return rec
 
     def _full_only(self, rec, full_only):

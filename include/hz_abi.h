@@ -378,6 +378,64 @@ int hz_mcts_take_error(hz_mcts *mcts, int32_t *out);
 int hz_mcts_set_budget(hz_mcts *mcts, const int32_t *budget);
 int hz_mcts_sims_done(hz_mcts *mcts, int32_t *out);
 int hz_mcts_set_root_noise_mask(hz_mcts *mcts, const uint8_t *mask);
+/* ---- tree reuse: the searched subtree carried into the next search ----------
+ * No reference counterpart (MCTS.py:288 builds a fresh Node per call): this is
+ * the build's defined behaviour, off unless the caller asks for it, pinned by
+ * tests/test_mcts_carry_gpu.py against the host model tests/mcts_carry_model.py.
+ *
+ * hz_mcts_advance is called after hz_step has applied action[n] (device int16)
+ * to the env.  Board b is CARRIED iff all of these hold:
+ *  - active[b] != 0 (NULL: every board), its last search left a tree, and
+ *    action[b] >= 0;
+ *  - the root has an edge for action[b];
+ *  - that edge's child c is not terminal;
+ *  - node_state[c] equals the env's current state of b in all six words.  This
+ *    is the rule, not an optimisation: a place_tile_3 child refilled its pile
+ *    from draws taken when it was expanded, hz_step draws again from where the
+ *    stream then stands, so a turn end carries only when the draws agree; pile
+ *    choice and the first two placements are deterministic and carry;
+ *  - kept nodes + headroom <= max_nodes and kept edges + headroom <= max_edges
+ *    (headroom >= 0, else -1; 69 * sims cannot overflow in the next search).
+ * Otherwise it is DROPPED: carry flag 0, counts[b][0..1] = 0, info[b] = {0,0,0}.
+ * For a carried board the tree becomes the sub-DAG reachable from c.  The result
+ * is defined by this rule, not by a traversal order:
+ *  - Nodes: c becomes node 0; the other kept nodes take ids 1.. in ascending old
+ *    id.  State and canonical key move with their node.
+ *  - Edges: the edge blocks of the kept expanded nodes keep their relative pool
+ *    order and are packed from 0.  A node's first edge and every edge's child
+ *    are renumbered (a node without edges has first edge 0); action, N, W, P and
+ *    mover move unchanged, bit for bit.
+ *  - The generation counts[b][2] is incremented and every kept node entered into
+ *    the hash table again.  Dropped nodes are gone: a later expansion that would
+ *    have transposed onto one makes a new node.
+ *  - The walk's hints are rebuilt from the moved nodes.
+ *  - counts[b] = {kept nodes, kept edges, generation, 0}; info[b] (device int32
+ *    [n][3]) = {kept nodes, kept edges, sum of N over the new root's edges}; the
+ *    board's carry flag is set in the handle.
+ * The move is done in place with two int32 [n][max_nodes] scratch arrays the
+ * first call allocates (no second node pool).  One launch, no synchronisation.
+ *
+ * hz_mcts_begin_carried starts the next search in place of hz_mcts_begin:
+ *  - a board whose carry flag is set and whose node 0 still equals the env's
+ *    state (checked again: a reset or import in between drops the carry) keeps
+ *    its tree; its limit flag and simulation count are cleared, and the stuck-
+ *    root budget rule of hz_mcts_begin applies unchanged;
+ *  - if that root is expanded and the board is noisy (!testing, noise != NULL,
+ *    no mask or mask[b]), the root priors are mixed once with the expansion's
+ *    arithmetic: P = f32(f64(f32(1 - eps) * P) + eps * noise[b*69 + i]), i the
+ *    rank of the edge's action among the root's legal moves (not the edge index:
+ *    a skipped self-loop child shifts it).  A carried root without edges is
+ *    expanded by the first simulation and mixed there, as any root;
+ *  - every other active board gets exactly what hz_mcts_begin does;
+ *  - the flag is consumed either way: a second hz_mcts_begin_carried without an
+ *    hz_mcts_advance starts fresh.
+ * hz_mcts_begin always starts fresh and clears the flags.  The simulations of a
+ * carried search are the ones of any search: nothing in select, expand or backup
+ * knows about the carry. */
+int hz_mcts_advance(hz_mcts *mcts, hz_env *env, const int16_t *action, const uint8_t *active, int32_t headroom,
+                    int32_t *info);
+int hz_mcts_begin_carried(hz_mcts *mcts, hz_env *env, const uint8_t *active, const double *noise, double eps,
+                          int32_t testing);
 /* root visit counts by action id: visits[n][143] (MCTS.py:355-376) */
 int hz_mcts_result(hz_mcts *mcts, int32_t *visits);
 /* per-board [nodes, edges, search generation, limit flag] -> counts[n][4].
