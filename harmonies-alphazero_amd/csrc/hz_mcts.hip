@@ -76,6 +76,16 @@ struct hz_mcts {
   uint8_t *carry;        // [n] board b's tree is the subtree hz_mcts_advance kept (consumed by the next begin)
   int32_t *adv_remap;    // [n][max_nodes] advance's scratch: reach marks, then old node id -> new id (-1: dropped)
   int32_t *adv_queue;    // [n][max_nodes] advance's scratch: the kept expanded nodes, in discovery order
+  // the Gumbel root (hz_mcts_set_gumbel; allocated by its first call): gumbel == nullptr: gate off, else == gumbel_buf
+  double *gumbel;        // [n][69] G by legal rank (the handle's copy), or nullptr
+  double *gumbel_buf;    // [n][69] owned; fixed address (a captured simulation stays valid while its contents change)
+  double *g_score;       // [n][69] G + log P by root edge index, written where node 0's edges are
+  float *root_value;     // [n] the network's value of node 0, written where node 0 is expanded
+  // [g_considered + 1][g_nroot] considered-visit table: owned, allocated once for the largest table the ABI
+  // admits (70 x 32767 int16, 4.6 MB), so its address is fixed for the handle's life like the others'
+  int16_t *g_table;
+  int32_t g_considered, g_nroot;
+  double g_c_visit, g_c_scale;
 };
 
 namespace {
@@ -208,11 +218,100 @@ constexpr int32_t kMaxNodesHint = 1 << 24;
 __device__ __forceinline__ int32_t edge_hint_of(int e0, int ne, bool term) {
   return (int32_t)((uint32_t)e0 << 8 | (term ? (uint32_t)kHintTerm : 0u) | (uint32_t)ne);
 }
+// ------------------------------------------------------------ the Gumbel root
+// The root rule of hz_mcts_set_gumbel (include/hz_abi.h states it; no
+// reference counterpart).  Lane l holds root edges l and l + 64.  The two
+// fp64 sums are the xor butterfly: the lane's partial is edge l's term plus
+// edge l + 64's (0.0 for an edge that is absent or unvisited), then
+// v = v + v[lane ^ off] for off = 1, 2, 4, 8, 16, 32; minima and maxima are
+// exact in any order.  These run once per simulation and board, under the
+// gate only: plain cross-lane moves, not the walk's DPP forms.
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) v = __dadd_rn(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ double wave_min_d(double v) {
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) v = fmin(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ double wave_max_d(double v) {
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) v = fmax(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ int wave_max_i(int v) {
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) v = max(v, __shfl_xor(v, o));
+  return v;
+}
+// G + log P of one root edge: the one place the transcendental is taken (the
+// expansion of node 0 stores it in g_score; the select, the result and
+// hz_mcts_root_gumbel_scores read that array); -inf where P is 0
+__device__ __forceinline__ double gumbel_edge_score(double g, float p) { return __dadd_rn(g, log((double)p)); }
+constexpr double kGumbelFloor = -1e9;
+constexpr int32_t kGumbelTableMax = (kMaxChildren + 1) * 32767;  // entries of the largest table hz_mcts_set_gumbel admits
+// sigma of the lane's two edges from the root's statistics (ne edges, t = sum
+// N), the completed-Q mix v_mix and the largest N
+__device__ __forceinline__ void gumbel_sigma(const hz_mcts &m, int lane, int ne, int t, int n0, int n1, double w0,
+                                             double w1, float p0, float p1, double v_root, double &sg0, double &sg1,
+                                             double &v_mix, int &max_n) {
+  const bool in0 = lane < ne, in1 = lane + kWave < ne;
+  const bool vis0 = in0 && n0 > 0, vis1 = in1 && n1 > 0;
+  const double q0 = vis0 ? __ddiv_rn(w0, (double)n0) : 0.0, q1 = vis1 ? __ddiv_rn(w1, (double)n1) : 0.0;
+  const double sp = wave_sum_d(__dadd_rn(vis0 ? (double)p0 : 0.0, vis1 ? (double)p1 : 0.0));
+  const double spq =
+      wave_sum_d(__dadd_rn(vis0 ? __dmul_rn((double)p0, q0) : 0.0, vis1 ? __dmul_rn((double)p1, q1) : 0.0));
+  const double wq = sp > 0.0 ? __ddiv_rn(spq, sp) : 0.0;
+  v_mix = __ddiv_rn(__dadd_rn(v_root, __dmul_rn((double)t, wq)), (double)(t + 1));
+  max_n = wave_max_i(max(in0 ? n0 : 0, in1 ? n1 : 0));
+  const double c0 = vis0 ? q0 : v_mix, c1 = vis1 ? q1 : v_mix;  // completed Q
+  const double mn = wave_min_d(fmin(in0 ? c0 : INFINITY, in1 ? c1 : INFINITY));
+  const double mx = wave_max_d(fmax(in0 ? c0 : -INFINITY, in1 ? c1 : -INFINITY));
+  const double den = fmax(__dsub_rn(mx, mn), 1e-8);
+  const double scale = __dmul_rn(__dadd_rn(m.g_c_visit, (double)max_n), m.g_c_scale);
+  sg0 = in0 ? __dmul_rn(scale, __ddiv_rn(__dsub_rn(c0, mn), den)) : 0.0;
+  sg1 = in1 ? __dmul_rn(scale, __ddiv_rn(__dsub_rn(c1, mn), den)) : 0.0;
+}
+// The root's choice of one simulation: among the edges whose N is the table's
+// considered-visit count (every edge if none is), the first with the largest
+// max(-1e9, (G + log P) + sigma).  Leaves (best, bi) for wave_argmax.
+__device__ __forceinline__ void gumbel_root_pick(const hz_mcts &m, int lane, int ne, int t, int n0, int n1, double w0,
+                                                 double w1, float p0, float p1, double v_root, double gs0, double gs1,
+                                                 double &best, int &bi) {
+  double sg0, sg1, v_mix;
+  int max_n;
+  gumbel_sigma(m, lane, ne, t, n0, n1, w0, w1, p0, p1, v_root, sg0, sg1, v_mix, max_n);
+  const int mc = min(m.g_considered, ne);
+  const int col = min(max(t, 0), m.g_nroot - 1);
+  const int cv = m.g_table[(size_t)mc * m.g_nroot + col];
+  const bool in0 = lane < ne, in1 = lane + kWave < ne;
+  bool cand0 = in0 && n0 == cv, cand1 = in1 && n1 == cv;
+  if (__ballot(cand0 || cand1) == 0ull) {
+    cand0 = in0;
+    cand1 = in1;
+  }
+  best = -INFINITY;
+  bi = 0x7fffffff;
+  if (cand0) {
+    best = fmax(kGumbelFloor, __dadd_rn(gs0, sg0));
+    bi = lane;
+  }
+  if (cand1) {
+    const double v = fmax(kGumbelFloor, __dadd_rn(gs1, sg1));
+    if (v > best) { best = v; bi = lane + kWave; }
+  }
+}
+
 // Fresh: the edges' N and W are read past the CU's L1 (relaxed agent-scope
 // loads), for a walk in the launch whose backup just added to them at L2
 // Returns the leaf's encoder index (b * max_nodes + leaf, wave-uniform), -1
 // when the board is inactive or its leaf is terminal (no network row)
-template <bool Fresh = false>
+// Gum: the launch of a handle whose Gumbel gate is on (hz_mcts_set_gumbel):
+// the root's choice is gumbel_root_pick's, every other level's is PUCT's.  A
+// handle with the gate off launches the instantiations without the branch.
+template <bool Fresh = false, bool Gum = false>
 __device__ __forceinline__ int select_board(const hz_mcts &m, int b, int lane, const uint8_t *__restrict__ active,
                                             float cpuct) {
   int32_t *cnt = m.counts + (size_t)b * 4;
@@ -279,20 +378,37 @@ __device__ __forceinline__ int select_board(const hz_mcts &m, int b, int lane, c
       h1 = m.edge_hint[eb + e0 + lane + kWave];
     }
     const int ns = wave_sum_i(n0 + n1);
-    double sqrt_ns = __dsqrt_rn(ns > 1 ? (double)ns : 1.0);
     double best = -INFINITY;
     int bi = 0x7fffffff;
-    if (lane < ne) {
-      double u = __ddiv_rn(__dmul_rn((double)__fmul_rn(cpuct, p0), sqrt_ns), (double)(1 + n0));
-      double q = n0 ? __ddiv_rn(w0, (double)n0) : 0.0;
-      best = __dadd_rn(q, u);
-      bi = lane;
-    }
-    if (lane + kWave < ne) {
-      double u = __ddiv_rn(__dmul_rn((double)__fmul_rn(cpuct, p1), sqrt_ns), (double)(1 + n1));
-      double q = n1 ? __ddiv_rn(w1, (double)n1) : 0.0;
-      double v = __dadd_rn(q, u);
-      if (v > best) { best = v; bi = lane + kWave; }
+    // (a root has at most kMaxChildren edges: the expansion refuses more)
+    if (Gum && d == 0 && ne <= kMaxChildren) {  // (Gum: the host launches this form only while m.gumbel is set)
+      // the scores and the root's value were stored by the expansion of node
+      // 0, in this launch (Fresh) or an earlier one
+      const double *gs = m.g_score + (size_t)b * kMaxChildren;
+      auto ld_s = [&](int i) {
+        return Fresh ? __longlong_as_double((long long)__hip_atomic_load(
+                           reinterpret_cast<const unsigned long long *>(gs + i), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT))
+                     : gs[i];
+      };
+      const double gs0 = lane < ne ? ld_s(lane) : 0.0, gs1 = lane + kWave < ne ? ld_s(lane + kWave) : 0.0;
+      const float vr = Fresh ? __hip_atomic_load(&m.root_value[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                             : m.root_value[b];
+      gumbel_root_pick(m, lane, ne, ns, n0, n1, w0, w1, p0, p1, (double)vr, gs0, gs1, best, bi);
+    } else {
+      double sqrt_ns = __dsqrt_rn(ns > 1 ? (double)ns : 1.0);
+      if (lane < ne) {
+        double u = __ddiv_rn(__dmul_rn((double)__fmul_rn(cpuct, p0), sqrt_ns), (double)(1 + n0));
+        double q = n0 ? __ddiv_rn(w0, (double)n0) : 0.0;
+        best = __dadd_rn(q, u);
+        bi = lane;
+      }
+      if (lane + kWave < ne) {
+        double u = __ddiv_rn(__dmul_rn((double)__fmul_rn(cpuct, p1), sqrt_ns), (double)(1 + n1));
+        double q = n1 ? __ddiv_rn(w1, (double)n1) : 0.0;
+        double v = __dadd_rn(q, u);
+        if (v > best) { best = v; bi = lane + kWave; }
+      }
     }
     wave_argmax(best, bi);
     int sel = e0 + bi;
@@ -320,8 +436,9 @@ __device__ __forceinline__ int select_board(const hz_mcts &m, int b, int lane, c
   return gidx;
 }
 
+template <bool Gum>
 __global__ void __launch_bounds__(kWave) k_select(hz_mcts m, const uint8_t *__restrict__ active, float cpuct) {
-  select_board(m, blockIdx.x, threadIdx.x, active, cpuct);
+  select_board<false, Gum>(m, blockIdx.x, threadIdx.x, active, cpuct);
 }
 
 // ------------------------------------------------------------ gather leaves
@@ -470,6 +587,7 @@ __global__ void __launch_bounds__(kGEThreads) k_gather_encode(hz_mcts m, int32_t
 constexpr int kFusedMax = 32;
 constexpr int kFusedWaves = 16;
 static_assert(kFusedMax <= 2 * kFusedWaves && kFusedMax <= kWave, "one pair per wave, one gather wave");
+template <bool Gum>
 __global__ void __launch_bounds__(kFusedWaves * kWave) k_select_gather_encode(hz_mcts m,
                                                                            const uint8_t *__restrict__ active,
                                                                            float cpuct, int32_t *__restrict__ rows,
@@ -480,7 +598,7 @@ __global__ void __launch_bounds__(kFusedWaves * kWave) k_select_gather_encode(hz
   __shared__ float sval[kFusedWaves][76];
   __shared__ int32_t s_count;
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int b = w; b < m.n; b += kFusedWaves) select_board(m, b, lane, active, cpuct);
+  for (int b = w; b < m.n; b += kFusedWaves) select_board<false, Gum>(m, b, lane, active, cpuct);
   __syncthreads();  // every board's leaf_gidx (written by its wave) is visible to the workgroup
   if (w == 0) {
     const int g = lane < m.n ? m.leaf_gidx[lane] : -1;
@@ -706,6 +824,9 @@ static_assert(sizeof(uint64_t) * kChildLds * 6 >= sizeof(uint32_t) * kMT, "the s
 // expand_leaf (MCTS.py:151-218) + back_fill (:220-266) + the root Dirichlet
 // mix (:308-327).  noise[b*69 + i] is the i-th legal move's Dirichlet sample.
 // (board b, one wave; the kernel below adds the next simulation's select)
+// Gum (a handle whose Gumbel gate is on): node 0's expansion also stores the
+// network's value of the root and each root edge's G + log P.
+template <bool Gum>
 __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts &m, uint32_t *__restrict__ mtw,
                                                     int32_t *__restrict__ mtcur, int32_t *__restrict__ wtag,
                                                     const float *__restrict__ policy,
@@ -756,6 +877,7 @@ __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts 
       return;
     }
     v = (double)value[row];
+    if (Gum && leaf == 0 && lane == 0) m.root_value[b] = value[row];
     uint64_t mk[3];
     int nl = legal_mask(ls, mk);
     bool noisy = leaf == 0 && !testing && noise && (!m.noise_mask || m.noise_mask[b]);
@@ -1087,6 +1209,10 @@ __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts 
             m.edge_w[eb + e] = 0.0;
             m.edge_p[eb + e] = p;
             m.edge_player[eb + e] = (uint8_t)leaf_player;
+            // (c is the move's legal rank, c < nl <= 69; the edge's index within the root is below n_edges <= nl)
+            if (Gum && leaf == 0)
+              m.g_score[(size_t)b * kMaxChildren + (L.flag[c] >> 4)] =
+                  gumbel_edge_score(m.gumbel[(size_t)b * kMaxChildren + c], p);
             // the child node's edges and terminal mark: an existing node's
             // from the probe; a new node has no edges, and is terminal as the
             // state it was created from (a sibling duplicate's: its target's)
@@ -1149,7 +1275,7 @@ __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts 
 // WaveSlot (BPW > 1): each wave takes its row with its own atomic add as
 // soon as its walk is done, instead of the workgroup's one add after a
 // barrier that waits for the workgroup's slowest wave (A/B: HZ_SLOT_WAVE)
-template <int Waves, bool Sel, bool Gather = false, int BPW = 1, bool WaveSlot = false>  // Waves: minimum waves per SIMD the register allocation must allow (3: none forced)
+template <int Waves, bool Sel, bool Gum, bool Gather = false, int BPW = 1, bool WaveSlot = false>  // Waves: minimum waves per SIMD the register allocation must allow (3: none forced)
 __global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_eu(Waves, 8))) k_expand_backup(hz_mcts m, uint32_t *__restrict__ mtw,
                                                          int32_t *__restrict__ mtcur,
                                                          int32_t *__restrict__ wtag,
@@ -1172,7 +1298,7 @@ __global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_e
   const int b = (int)blockIdx.x * BPW + w;
   const bool live = BPW == 1 || b < m.n;
   if (live)
-    expand_backup_board(L, m, mtw, mtcur, wtag, policy, value, noise, eps, one_minus_eps, testing, row_of, prio, b, lane,
+    expand_backup_board<Gum>(L, m, mtw, mtcur, wtag, policy, value, noise, eps, one_minus_eps, testing, row_of, prio, b, lane,
                         Sel);
   if (Sel) {
     __builtin_amdgcn_s_setprio(0);
@@ -1184,7 +1310,7 @@ __global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_e
     // cache maintenance) before the walk's loads issue, so the walk does not
     // rest on same-address requests reaching L2 in issue order
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    const int g = live ? select_board<true>(m, b, lane, active, cpuct) : -1;
+    const int g = live ? select_board<true, Gum>(m, b, lane, active, cpuct) : -1;
     // Gather: the leaf's six state words loaded and its row built in the
     // lane's registers (encode_one_values) before the row-slot barriers,
     // under the wait for the workgroup's slowest wave; after them only the
@@ -1330,6 +1456,23 @@ __global__ void __launch_bounds__(256) k_playout_coin(int n, uint64_t seed, uint
   coin[b] = s.uniform();
 }
 
+// One standard Gumbel per board and legal rank (hz_root_gumbel; no reference
+// counterpart): g = -log(-log u), u = (k + 1/2) 2^-52 for a 52-bit k, so u
+// lies strictly inside (0, 1) and g is finite; from k_root_noise's generator
+// and board key under a salt of its own (the noise, the move-choice uniform
+// and the coin keep their bits).
+__global__ void __launch_bounds__(kWave) k_root_gumbel(int n, uint64_t seed, uint64_t board_base, uint64_t move,
+                                                       double *__restrict__ out) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (b >= n) return;
+  const uint64_t key = mix64(mix64(mix64(seed ^ 0x6A09E667F3BCC908ULL) ^ (board_base + (uint64_t)b)) ^ move);
+  for (int c = lane; c < kMaxChildren; c += kWave) {
+    const uint64_t z = mix64(mix64(key ^ (0xA0761D6478BD642FULL * (uint64_t)(c + 1))) + 0x9E3779B97F4A7C15ULL);
+    const double u = ((double)(z >> 12) + 0.5) * 0x1.0p-52;
+    out[(size_t)b * kMaxChildren + c] = -log(-log(u));
+  }
+}
+
 // root visit counts by action (MCTS.py:355-376)
 __global__ void __launch_bounds__(kWave) k_result(hz_mcts m, int32_t *__restrict__ visits) {
   int b = blockIdx.x;
@@ -1471,6 +1614,99 @@ __global__ void __launch_bounds__(kWave) k_pv(hz_mcts m, int max_len, int16_t *_
     player[ob + i] = 0;
   }
   if (lane == 0) len[b] = d;
+}
+
+// The root's edges for the two Gumbel reports: at most kMaxChildren of them
+// (g_score has that many slots per board), inside the board's counts, on a
+// board the search began; else none.
+__device__ __forceinline__ int gumbel_root_edges(const hz_mcts &m, int b, int &e0) {
+  const int32_t *cnt = m.counts + (size_t)b * 4;
+  const int n_nodes = cnt[0], n_edges = cnt[1];
+  e0 = 0;
+  const int ne = checked_counts(m, n_nodes, n_edges) ? checked_edges(m, (size_t)b * m.max_nodes, 0, n_edges, e0) : 0;
+  return ne <= kMaxChildren ? ne : 0;
+}
+
+// hz_mcts_root_gumbel_scores: G + log P by root edge index (0.0 past the root's edges)
+__global__ void __launch_bounds__(kWave) k_gumbel_scores(hz_mcts m, double *__restrict__ out) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int e0;
+  const int ne = gumbel_root_edges(m, b, e0);
+  for (int i = lane; i < kMaxChildren; i += kWave)
+    out[(size_t)b * kMaxChildren + i] = i < ne ? m.g_score[(size_t)b * kMaxChildren + i] : 0.0;
+}
+
+// hz_mcts_gumbel_result: after the search, the move (the first edge with the
+// largest score among the most visited), the improved policy softmax(log P +
+// sigma) over the root's edges by action id (the maximum subtracted first;
+// should every prior be 0, the softmax of sigma alone) and v_mix.  A root
+// without edges: action -1, a zero row, value 0.
+__global__ void __launch_bounds__(kWave) k_gumbel_result(hz_mcts m, int16_t *__restrict__ action,
+                                                         float *__restrict__ pi, double *__restrict__ value) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  float *row = pi + (size_t)b * kActions;
+  for (int a = lane; a < kActions; a += kWave) row[a] = 0.f;
+  __syncthreads();  // the zeros before the edges' entries (one wave: ordering only)
+  int e0;
+  const int ne = gumbel_root_edges(m, b, e0);
+  if (ne == 0) {
+    if (lane == 0) {
+      action[b] = -1;
+      value[b] = 0.0;
+    }
+    return;
+  }
+  const size_t eb = (size_t)b * m.max_edges + e0, gb = (size_t)b * kMaxChildren;
+  const bool in0 = lane < ne, in1 = lane + kWave < ne;
+  int n0 = 0, n1 = 0, a0 = -1, a1 = -1;
+  double w0 = 0.0, w1 = 0.0, gs0 = 0.0, gs1 = 0.0;
+  float p0 = 0.f, p1 = 0.f;
+  if (in0) {
+    n0 = m.edge_n[eb + lane];
+    w0 = m.edge_w[eb + lane];
+    p0 = m.edge_p[eb + lane];
+    a0 = m.edge_action[eb + lane];
+    gs0 = m.g_score[gb + lane];
+  }
+  if (in1) {
+    n1 = m.edge_n[eb + lane + kWave];
+    w1 = m.edge_w[eb + lane + kWave];
+    p1 = m.edge_p[eb + lane + kWave];
+    a1 = m.edge_action[eb + lane + kWave];
+    gs1 = m.g_score[gb + lane + kWave];
+  }
+  const int t = wave_sum_i(n0 + n1);
+  double sg0, sg1, v_mix;
+  int max_n;
+  gumbel_sigma(m, lane, ne, t, n0, n1, w0, w1, p0, p1, (double)m.root_value[b], sg0, sg1, v_mix, max_n);
+  double best = -INFINITY;
+  int bi = 0x7fffffff;
+  if (in0 && n0 == max_n) {
+    best = fmax(kGumbelFloor, __dadd_rn(gs0, sg0));
+    bi = lane;
+  }
+  if (in1 && n1 == max_n) {
+    const double v = fmax(kGumbelFloor, __dadd_rn(gs1, sg1));
+    if (v > best) { best = v; bi = lane + kWave; }
+  }
+  wave_argmax(best, bi);
+  const int act = __shfl(bi < kWave ? a0 : a1, bi & (kWave - 1));
+  // the improved policy
+  double l0 = in0 ? __dadd_rn(log((double)p0), sg0) : -INFINITY, l1 = in1 ? __dadd_rn(log((double)p1), sg1) : -INFINITY;
+  double mx = wave_max_d(fmax(l0, l1));
+  if (mx == -INFINITY) {
+    l0 = in0 ? sg0 : -INFINITY;
+    l1 = in1 ? sg1 : -INFINITY;
+    mx = wave_max_d(fmax(l0, l1));
+  }
+  const double x0 = in0 ? exp(__dsub_rn(l0, mx)) : 0.0, x1 = in1 ? exp(__dsub_rn(l1, mx)) : 0.0;
+  const double sum = wave_sum_d(__dadd_rn(x0, x1));
+  if (in0 && a0 >= 0 && a0 < kActions) row[a0] = (float)__ddiv_rn(x0, sum);
+  if (in1 && a1 >= 0 && a1 < kActions) row[a1] = (float)__ddiv_rn(x1, sum);
+  if (lane == 0) {
+    action[b] = (int16_t)act;
+    value[b] = v_mix;
+  }
 }
 
 // -------------------------------------------------------------- tree reuse
@@ -1931,7 +2167,8 @@ void hz_mcts_destroy(hz_mcts *m) {
                   m->edge_n,     m->edge_w,    m->edge_p,    m->edge_player, m->edge_hint, m->ht, m->counts,
                   m->path,       m->depth,     m->leaf,      m->leaf_gidx, m->slot, m->gidx_c,
                   m->err,        m->sims_done, m->budget_buf, m->mask_buf,
-                  m->carry,      m->adv_remap, m->adv_queue};
+                  m->carry,      m->adv_remap, m->adv_queue,
+                  m->gumbel_buf, m->g_score,   m->root_value, m->g_table};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   free(m);
@@ -1997,6 +2234,60 @@ int hz_mcts_set_root_noise_mask(hz_mcts *m, const uint8_t *mask) {
   return 0;
 }
 
+int hz_mcts_set_gumbel(hz_mcts *m, const double *g, const int16_t *table, int32_t max_considered, int32_t n_root,
+                       double c_visit, double c_scale) {
+  if (!m) return -1;
+  m->gumbel = nullptr;
+  if (!g) return 0;
+  if (!table || max_considered < 1 || max_considered > kMaxChildren || n_root < 1 || n_root > 32767 ||
+      !(c_visit >= 0.0) || !(c_scale >= 0.0))
+    return -1;
+  const size_t n = (size_t)m->n;
+  if (!m->gumbel_buf) {  // first use: every buffer at its final size and address, freed by hz_mcts_destroy only
+    const bool ok = alloc(&m->gumbel_buf, n * kMaxChildren) && alloc(&m->g_score, n * kMaxChildren) &&
+                    alloc(&m->root_value, n) && alloc(&m->g_table, (size_t)kGumbelTableMax) &&
+                    hipMemsetAsync(m->g_score, 0, n * kMaxChildren * sizeof(double), m->stream) == hipSuccess &&
+                    hipMemsetAsync(m->root_value, 0, n * sizeof(float), m->stream) == hipSuccess;
+    if (!ok) {
+      for (void *p : {(void *)m->gumbel_buf, (void *)m->g_score, (void *)m->root_value, (void *)m->g_table})
+        if (p) (void)hipFree(p);
+      m->gumbel_buf = m->g_score = nullptr;
+      m->root_value = nullptr;
+      m->g_table = nullptr;
+      return 1;
+    }
+  }
+  const int32_t entries = (max_considered + 1) * n_root;  // <= kGumbelTableMax, by the checks above
+  if (hipMemcpyAsync(m->gumbel_buf, g, n * kMaxChildren * sizeof(double), hipMemcpyDeviceToDevice, m->stream) ||
+      hipMemcpyAsync(m->g_table, table, (size_t)entries * sizeof(int16_t), hipMemcpyDeviceToDevice, m->stream))
+    return 1;
+  m->g_considered = max_considered;
+  m->g_nroot = n_root;
+  m->g_c_visit = c_visit;
+  m->g_c_scale = c_scale;
+  m->gumbel = m->gumbel_buf;
+  return 0;
+}
+
+int hz_mcts_root_gumbel_scores(hz_mcts *m, double *out) {
+  if (!m || !out || !m->gumbel) return -1;
+  hipLaunchKernelGGL(k_gumbel_scores, dim3(m->n), dim3(kWave), 0, m->stream, *m, out);
+  return launch_err();
+}
+
+int hz_mcts_gumbel_result(hz_mcts *m, int16_t *action, float *pi, double *value) {
+  if (!m || !action || !pi || !value || !m->gumbel) return -1;
+  hipLaunchKernelGGL(k_gumbel_result, dim3(m->n), dim3(kWave), 0, m->stream, *m, action, pi, value);
+  return launch_err();
+}
+
+int hz_root_gumbel(int32_t n, uint64_t seed, uint64_t board_base, uint64_t move, double *out, void *stream) {
+  if (n < 0 || !out) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_root_gumbel, dim3(n), dim3(kWave), 0, (hipStream_t)stream, n, seed, board_base, move, out);
+  return launch_err();
+}
+
 int hz_mcts_set_stream(hz_mcts *m, void *stream) {
   if (!m) return -1;
   m->stream = (hipStream_t)stream;
@@ -2043,7 +2334,8 @@ int hz_mcts_begin_carried(hz_mcts *m, hz_env *env, const uint8_t *active, const 
 
 int hz_mcts_select(hz_mcts *m, const uint8_t *active, float cpuct) {
   if (!m) return -1;
-  hipLaunchKernelGGL(k_select, dim3(m->n), dim3(kWave), 0, m->stream, *m, active, cpuct);
+  if (m->gumbel) hipLaunchKernelGGL(k_select<true>, dim3(m->n), dim3(kWave), 0, m->stream, *m, active, cpuct);
+  else hipLaunchKernelGGL(k_select<false>, dim3(m->n), dim3(kWave), 0, m->stream, *m, active, cpuct);
   return launch_err();
 }
 
@@ -2060,8 +2352,12 @@ int hz_mcts_select_gather(hz_mcts *m, const uint8_t *active, float cpuct, float 
     const int rc = hz_mcts_select(m, active, cpuct);
     return rc ? rc : hz_mcts_gather_leaves(m, board, glob, rows, count);
   }
-  hipLaunchKernelGGL(k_select_gather_encode, dim3(1), dim3(kFusedWaves * kWave), 0, m->stream, *m, active, cpuct,
-                     rows, count, board, glob);
+  if (m->gumbel)
+    hipLaunchKernelGGL(k_select_gather_encode<true>, dim3(1), dim3(kFusedWaves * kWave), 0, m->stream, *m, active,
+                       cpuct, rows, count, board, glob);
+  else
+    hipLaunchKernelGGL(k_select_gather_encode<false>, dim3(1), dim3(kFusedWaves * kWave), 0, m->stream, *m, active,
+                       cpuct, rows, count, board, glob);
   return launch_err();
 }
 
@@ -2109,10 +2405,16 @@ static int expand_backup(hz_mcts *m, hz_env *env, const float *policy, const flo
   uint32_t *mt = nullptr;
   int32_t *mt_pos = nullptr, *win_tag = nullptr;
   if (hz_env_stream_ptrs(env, &mt, &mt_pos, &win_tag)) return 1;
-#define HZ_EXPAND_LAUNCH(W, S, G, BP, ...)                                                                      \
-  hipLaunchKernelGGL((k_expand_backup<W, S, G, BP, ##__VA_ARGS__>), dim3((m->n + (BP) - 1) / (BP)), dim3(kWave * (BP)), \
+#define HZ_EXPAND_LAUNCH_G(W, S, GUM, G, BP, ...)                                                               \
+  hipLaunchKernelGGL((k_expand_backup<W, S, GUM, G, BP, ##__VA_ARGS__>), dim3((m->n + (BP) - 1) / (BP)), dim3(kWave * (BP)), \
                      0, m->stream, *m, mt, mt_pos, win_tag, policy, value, noise, eps, ome, testing, slot, prio, active, cpuct, \
                      board, glob, rows, count_out, count_prev, add_prev)
+  // (the Gumbel gate picks the instantiation: with it off the kernels carry none of its code)
+#define HZ_EXPAND_LAUNCH(W, S, G, BP, ...)                                  \
+  do {                                                                      \
+    if (m->gumbel) HZ_EXPAND_LAUNCH_G(W, S, true, G, BP, ##__VA_ARGS__);     \
+    else HZ_EXPAND_LAUNCH_G(W, S, false, G, BP, ##__VA_ARGS__);              \
+  } while (0)
   const bool gat = sel && count_out;
   if (waves == 4) {
     if (gat && gather_bpw() == 8) HZ_EXPAND_LAUNCH(4, true, true, 8);
@@ -2127,6 +2429,7 @@ static int expand_backup(hz_mcts *m, hz_env *env, const float *policy, const flo
     else HZ_EXPAND_LAUNCH(3, false, false, 1);
   }
 #undef HZ_EXPAND_LAUNCH
+#undef HZ_EXPAND_LAUNCH_G
   return launch_err();
 }
 

@@ -74,6 +74,10 @@ _SIGS = {
     "hz_mcts_set_budget": ([_vp, _vp], _c.c_int),
     "hz_mcts_sims_done": ([_vp, _vp], _c.c_int),
     "hz_mcts_set_root_noise_mask": ([_vp, _vp], _c.c_int),
+    "hz_root_gumbel": ([_c.c_int32, _c.c_uint64, _c.c_uint64, _c.c_uint64, _vp, _vp], _c.c_int),
+    "hz_mcts_set_gumbel": ([_vp, _vp, _vp, _c.c_int32, _c.c_int32, _c.c_double, _c.c_double], _c.c_int),
+    "hz_mcts_root_gumbel_scores": ([_vp, _vp], _c.c_int),
+    "hz_mcts_gumbel_result": ([_vp, _vp, _vp, _vp], _c.c_int),
     "hz_mcts_advance": ([_vp, _vp, _vp, _vp, _c.c_int32, _vp], _c.c_int),
     "hz_mcts_begin_carried": ([_vp, _vp, _vp, _vp, _c.c_double, _c.c_int32], _c.c_int),
     "hz_mcts_stats": ([_vp, _vp], _c.c_int),

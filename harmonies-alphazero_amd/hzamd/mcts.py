@@ -34,6 +34,35 @@ from .env import ACTION_SIZE
 MAX_CHILDREN = 69
 MAX_NODES_END = 1 << 24  # hz_mcts_create refuses max_nodes from here on (an edge id must fit 24 bits)
 DEFAULT_MAX_DEPTH = 192
+GUMBEL_DEFAULT = {"max_considered": 16, "c_visit": 50.0, "c_scale": 1.0}  # the paper's setting, not tuned here
+
+
+def considered_visit_table(max_considered, n_root):
+    """The Gumbel root's considered-visit table (include/hz_abi.h,
+    hz_mcts_set_gumbel): int16 numpy [max_considered + 1, n_root]; row m is the
+    paper's sequential-halving sequence for m considered actions and n_root
+    root visits (rows 0 and 1: 0, 1, 2, ...)."""
+    import math
+
+    import numpy as np
+    max_considered, n_root = int(max_considered), int(n_root)
+    if max_considered < 1 or not 1 <= n_root <= 32767:
+        raise ValueError(f"max_considered {max_considered} below 1 or n_root {n_root} outside 1..32767")
+    table = np.zeros((max_considered + 1, n_root), np.int16)
+    for m in range(max_considered + 1):
+        if m <= 1:
+            table[m] = np.arange(n_root)
+            continue
+        log2m = math.ceil(math.log2(m))
+        seq, visits, k = [], [0] * m, m
+        while len(seq) < n_root:
+            for _ in range(max(1, int(n_root / (log2m * k)))):
+                seq.extend(visits[:k])
+                for i in range(k):
+                    visits[i] += 1
+            k = max(2, k // 2)
+        table[m] = seq[:n_root]
+    return table
 
 
 class BatchedMCTS:
@@ -105,7 +134,9 @@ class BatchedMCTS:
         # boards: only then can a row lie past them, and _finish() reads the
         # handle's error word (hz_mcts_set_row_cap)
         self._cap_risk = False
-        self._gate = (False, False)  # (budget gate on, root-noise mask on), as last set by search()
+        # (budget gate on, root-noise mask on, the Gumbel gate's settings or None), as last set by search()
+        self._gate = (False, False, None)
+        self._gumbel_tables = {}  # (max_considered, n_root) -> the device table (built once per shape)
         # tree reuse (advance() / search(carry=True)): advance's info rows, and
         # the edges and walked levels the search began with (count_edges and
         # count_path add only what the search itself made)
@@ -264,10 +295,70 @@ class BatchedMCTS:
         nat.check(nat.lib().hz_mcts_sims_done(self._h, nat.ptr(self._sims_done)), "hz_mcts_sims_done")
         return self._sims_done
 
-    def _set_gate(self, budget, root_noise):
-        """The budget gate and the root-noise mask of the search about to
-        begin (None: off), copied into the handle in stream order."""
+    def _set_gumbel(self, gumbel, total, max_considered, c_visit, c_scale):
+        """The Gumbel gate of the search about to begin (gumbel None: off),
+        copied into the handle in stream order; returns the gate's settings
+        (what a captured simulation holds of it) or None."""
         L = nat.lib()
+        if gumbel is None:
+            if hasattr(L, "hz_mcts_set_gumbel"):  # (an older A/B build named by HZ_LIB has no gate to clear)
+                nat.check(L.hz_mcts_set_gumbel(self._h, None, None, 0, 0, 0.0, 0.0), "hz_mcts_set_gumbel")
+            return None
+        gumbel = gumbel.to(device=self.device, dtype=torch.float64).contiguous()
+        if gumbel.shape != (self.n, MAX_CHILDREN):
+            raise ValueError(f"gumbel of shape {tuple(gumbel.shape)}, not ({self.n}, {MAX_CHILDREN})")
+        mc = GUMBEL_DEFAULT["max_considered"] if max_considered is None else int(max_considered)
+        cv = GUMBEL_DEFAULT["c_visit"] if c_visit is None else float(c_visit)
+        cs = GUMBEL_DEFAULT["c_scale"] if c_scale is None else float(c_scale)
+        if not 1 <= mc <= MAX_CHILDREN or not cv >= 0.0 or not cs >= 0.0:
+            raise ValueError(f"max_considered {mc} outside 1..{MAX_CHILDREN}, or a negative c_visit / c_scale")
+        n_root = max(1, int(total) - 1)  # simulation 1 expands the root and visits no edge
+        table = self._gumbel_tables.get((mc, n_root))
+        if table is None:
+            if len(self._gumbel_tables) >= 8:
+                self._gumbel_tables.clear()
+            table = self._gumbel_tables[(mc, n_root)] = torch.from_numpy(
+                considered_visit_table(mc, n_root)).to(self.device)
+        nat.check(L.hz_mcts_set_gumbel(self._h, nat.ptr(gumbel), nat.ptr(table), mc, n_root, cv, cs),
+                  "hz_mcts_set_gumbel")
+        return (mc, n_root, cv, cs)
+
+    def gumbel_result(self):
+        """After search(root="gumbel") (hz_mcts_gumbel_result): device tensors
+        action int16 [n] (the move of the first edge with the largest score
+        among the most visited; -1 for a root without edges), pi f32 [n, 143]
+        (the improved policy softmax(log P + sigma) over the root's edges, a
+        zero row where there are none) and value f64 [n] (v_mix, from the
+        root mover's side).  The handle's own tensors, rewritten by the next call."""
+        if self._gate[2] is None:
+            raise ValueError("gumbel_result() after a search without root='gumbel'")
+        r = self._report.get("gumbel")
+        if r is None:
+            z = self._zeros
+            r = self._report["gumbel"] = {"action": z(torch.int16, self.n), "pi": z(torch.float32, self.n, ACTION_SIZE),
+                                          "value": z(torch.float64, self.n)}
+        nat.check(nat.lib().hz_mcts_gumbel_result(self._h, nat.ptr(r["action"]), nat.ptr(r["pi"]),
+                                                  nat.ptr(r["value"])), "hz_mcts_gumbel_result")
+        return dict(r)
+
+    def root_gumbel_scores(self):
+        """After search(root="gumbel"): device f64 [n, 69], G + log P per root
+        edge in edge order (hz_mcts_root_gumbel_scores: the values the root's
+        select used; -inf where P is 0, 0.0 past the root's edges)."""
+        if self._gate[2] is None:
+            raise ValueError("root_gumbel_scores() after a search without root='gumbel'")
+        r = self._report.get("gumbel_scores")
+        if r is None:
+            r = self._report["gumbel_scores"] = self._zeros(torch.float64, self.n, MAX_CHILDREN)
+        nat.check(nat.lib().hz_mcts_root_gumbel_scores(self._h, nat.ptr(r)), "hz_mcts_root_gumbel_scores")
+        return r
+
+    def _set_gate(self, budget, root_noise, gumbel=None):
+        """The budget gate and the root-noise mask of the search about to
+        begin (None: off), copied into the handle in stream order; gumbel:
+        the Gumbel gate's settings as _set_gumbel returned them."""
+        L = nat.lib()
+        self._gate = (self._gate[0], self._gate[1], gumbel)
         if budget is None and root_noise is None and not hasattr(L, "hz_mcts_set_budget"):
             return  # (an older A/B build named by HZ_LIB: it has no gate to clear)
         if budget is not None:
@@ -280,7 +371,7 @@ class BatchedMCTS:
                 raise ValueError(f"root_noise of shape {tuple(root_noise.shape)}, not ({self.n},)")
         nat.check(L.hz_mcts_set_budget(self._h, nat.ptr(budget)), "hz_mcts_set_budget")
         nat.check(L.hz_mcts_set_root_noise_mask(self._h, nat.ptr(root_noise)), "hz_mcts_set_root_noise_mask")
-        self._gate = (budget is not None, root_noise is not None)
+        self._gate = (budget is not None, root_noise is not None, gumbel)
 
     def stats(self):
         nat.check(nat.lib().hz_mcts_stats(self._h, nat.ptr(self.counts)), "hz_mcts_stats")
@@ -406,7 +497,8 @@ class BatchedMCTS:
         return g
 
     def search(self, evaluator, cpuct, active=None, noise=None, eps=0.25, testing=True, sims=None,
-               gather=True, graph=False, max_rows=None, budget=None, root_noise=None, tail=None, carry=False):
+               gather=True, graph=False, max_rows=None, budget=None, root_noise=None, tail=None, carry=False,
+               root=None, gumbel=None, max_considered=None, c_visit=None, c_scale=None):
         """get_best_action_and_pi's simulation loop (MCTS.py:288-352) for every
         active board; returns root visit counts int32 [n, 143].
 
@@ -445,11 +537,32 @@ class BatchedMCTS:
         carry: start from the trees the last advance() kept (begin_carried)
         instead of empty ones; `sims` (or the budgets) count the new
         simulations, the visits returned include the carried ones.  The
-        simulations themselves are the same launches in every search form."""
+        simulations themselves are the same launches in every search form.
+
+        root="gumbel" with gumbel=G (f64 [n, 69], one Gumbel per board and
+        legal rank: NoiseSource.gumbel): the root's choice is sequential
+        halving over the top max_considered actions by G + log P (+ sigma of
+        the completed Q, constants c_visit and c_scale; hz_mcts_set_gumbel
+        states the rule), for a search of `sims` simulations; below the root
+        the search is PUCT as always.  gumbel_result() then has the move, the
+        improved policy and v_mix; the visits returned are the search's.  In
+        every search form; not with noise=, root_noise=, budget=, tail= or
+        carry=True (ValueError).  A search without root= clears the gate."""
+        if root not in (None, "gumbel"):
+            raise ValueError(f"root {root!r}: not None or 'gumbel'")
+        if root is None and (gumbel is not None or max_considered is not None or c_visit is not None or
+                             c_scale is not None):
+            raise ValueError("gumbel=, max_considered=, c_visit= and c_scale= go with root='gumbel'")
+        if root == "gumbel":
+            if gumbel is None:
+                raise ValueError("root='gumbel' needs gumbel= (NoiseSource.gumbel)")
+            if noise is not None or root_noise is not None or budget is not None or tail is not None or carry:
+                raise ValueError("root='gumbel' does not combine with noise=, root_noise=, budget=, tail= or carry=True")
         if active is not None:
             active = active.to(device=self.device, dtype=torch.uint8).contiguous()
         self._sync()
-        self._set_gate(budget, root_noise)
+        self._set_gate(budget, root_noise, self._set_gumbel(
+            gumbel, self.num_simulations if sims is None else int(sims), max_considered, c_visit, c_scale))
         self._edges_base = self._path_base = None
         if carry:
             self.begin_carried(active, noise, eps, testing)

@@ -30,6 +30,14 @@ simulations on top; "topup" gives board b
 clamp(num_simulations - carried visits, tree_reuse_min_sims, num_simulations)
 through the per-board budgets.  Visit counts and pi include the carried
 visits; the records gain `carried`.
+
+The Gumbel root (no reference counterpart; config key `root_policy`:
+"gumbel", absent by default, with `gumbel_max_considered`, `gumbel_c_visit`,
+`gumbel_c_scale`): the root of every search is sequential halving over the
+top-m actions by Gumbel + log prior (BatchedMCTS.search(root="gumbel"), whose
+rule include/hz_abi.h states) instead of PUCT with Dirichlet noise; the move
+is the search's own at every ply, and the visit slots of the records hold the
+improved policy as rint(pi' * 65535), so pi = N / sum N rebuilds it.
 """
 import torch
 
@@ -92,6 +100,16 @@ class NoiseSource:
                   "hz_playout_coin")
         return coin
 
+    def gumbel(self, step, n):
+        """One standard Gumbel per board and legal rank under the same key
+        (hz_root_gumbel), f64 [n, 69] on the device: move `step`'s draws for
+        BatchedMCTS.search(root="gumbel"); draw() and coin() do not depend on it."""
+        g = torch.empty(n, MAX_CHILDREN, dtype=torch.float64, device=self.device)
+        nat.check(nat.lib().hz_root_gumbel(n, self.seed & (2**64 - 1), self.board_base & (2**64 - 1),
+                                           int(step) & (2**64 - 1), nat.ptr(g), nat.stream_ptr(self.device)),
+                  "hz_root_gumbel")
+        return g
+
 
 class SelfPlay:
     def __init__(self, n_boards, evaluator, mcts_config=None, seed_base=0, device="cuda", max_plies=200,
@@ -113,6 +131,18 @@ class SelfPlay:
         if self.tree_reuse and (self.cfg.get("playout_cap_p") is not None or
                                 self.cfg.get("playout_cap_fast") is not None):
             raise ValueError("tree_reuse and playout caps do not combine")
+        # the Gumbel root: on when root_policy is "gumbel" (absent: PUCT with Dirichlet noise, as always)
+        policy = self.cfg.get("root_policy")
+        if policy not in (None, "puct", "gumbel"):
+            raise ValueError(f"root_policy {policy!r}: not 'puct' or 'gumbel'")
+        self.gumbel = None
+        if policy == "gumbel":
+            if self.tree_reuse or self.cfg.get("playout_cap_p") is not None or \
+                    self.cfg.get("playout_cap_fast") is not None:
+                raise ValueError("root_policy 'gumbel' does not combine with playout caps or tree_reuse")
+            self.gumbel = {"max_considered": self.cfg.get("gumbel_max_considered"),
+                           "c_visit": self.cfg.get("gumbel_c_visit"), "c_scale": self.cfg.get("gumbel_c_scale")}
+        self.last_gumbel = None  # gumbel_result() of the last move(), with the Gumbel root
         max_nodes = int(pool * (1 + MAX_CHILDREN * self.cfg["num_simulations"])) if self.tree_reuse else None
         self.mcts = BatchedMCTS(self.env, self.cfg["num_simulations"], max_nodes=max_nodes, exact_keys=exact_keys)
         self._carried = None  # (state words after the last step, the visits advance() kept), with tree reuse
@@ -168,6 +198,8 @@ class SelfPlay:
             bound = n if _bound is None else int(_bound)
         active = ~done
         st = env.export_state()
+        if self.gumbel is not None:
+            return self._gumbel_move(st, active, bound)
         _, count = env.legal_mask()
         noise, u = self.noise.draw(self.step_counter, count, cfg["dirichlet_alpha"])
         self.step_counter += 1
@@ -209,6 +241,38 @@ class SelfPlay:
         act = choose_actions(v, explore, u)
         if self.keep_noise:
             self.noise_log.append((noise.clone(), u.clone(), act.clone()))
+        self._step(act, active, step)
+        return st, v, active
+
+    def _gumbel_move(self, st, active, bound):
+        """move() with the Gumbel root (root_policy "gumbel"): no Dirichlet
+        noise, the move is the search's own at every ply (the tau switch does
+        not apply), and the visit slots of the records hold the improved
+        policy as rint(pi' * 65535), so pi = N / sum N rebuilds pi' to within
+        the quantisation.  keep_root_value records the search's v_mix.  An
+        active board whose root has no edges (stuck) gets the search's -1, as
+        zero visits give it under PUCT: env.step reports the no-op and the next
+        check_steps() raises for that board, under either root policy."""
+        cfg = self.cfg
+        step = self.step_counter
+        g = self.noise.gumbel(step, self.n)
+        self.step_counter += 1
+        self.mcts.search(self.evaluator, cfg["cpuct"], active=active, testing=True, max_rows=max(1, bound),
+                         root="gumbel", gumbel=g, **self.gumbel)
+        res = self.last_gumbel = self.mcts.gumbel_result()
+        if self.keep_root_value:
+            self.last_root_value = res["value"]
+        self.check_steps()  # the previous move's step, done long before this search runs
+        act = res["action"].to(torch.int64)
+        v = torch.round(res["pi"].to(torch.float64) * 65535.0).to(torch.int32)
+        if self.keep_noise:
+            self.noise_log.append((g.clone(), None, act.clone()))
+        self._step(act, active, step)
+        return st, v, active
+
+    def _step(self, act, active, step):
+        """The chosen moves applied; the step's status queued for the next move()."""
+        env, n, d = self.env, self.n, self.device
         act = torch.where(active, act, torch.full_like(act, -1)).to(torch.int16)
         status = env.step(act)
         if self.tree_reuse:
@@ -229,7 +293,6 @@ class SelfPlay:
             self._flags_ev.record()
         self._bad_dev = bad
         self._flags_epoch = env.epoch
-        return st, v, active
 
     def _active_bound(self):
         return self._n_active if self.env.epoch == self._n_active_epoch else self.n

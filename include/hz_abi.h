@@ -378,6 +378,71 @@ int hz_mcts_take_error(hz_mcts *mcts, int32_t *out);
 int hz_mcts_set_budget(hz_mcts *mcts, const int32_t *budget);
 int hz_mcts_sims_done(hz_mcts *mcts, int32_t *out);
 int hz_mcts_set_root_noise_mask(hz_mcts *mcts, const uint8_t *mask);
+/* ---- the Gumbel root: sequential halving, improved-policy targets ------------
+ * No reference counterpart ("Policy improvement by planning with Gumbel",
+ * Danihelka et al., ICLR 2022): the build's defined behaviour, off by default,
+ * pinned by tests/mcts_gumbel_model.py.  Only the root's choice changes; below
+ * the root the walk, the expansion and the backup are PUCT's, bit for bit.
+ * Everything that decides an edge is fp64 arithmetic in the order stated here.
+ *
+ * hz_root_gumbel: out[n][69] (device) gets one standard Gumbel per board and
+ * legal rank, g = -log(-log u) with u = (k + 1/2) 2^-52 for a 52-bit k (strictly
+ * inside (0, 1): every g is finite), from hz_root_noise's generator and key
+ * (seed, board_base + b, move) under a salt of its own: the noise, the
+ * move-choice uniform and the coin keep their bits, and a board's draws do not
+ * depend on the batch or on how board_base splits it.  Enqueued on `stream`.
+ *
+ * hz_mcts_set_gumbel: g[n][69] (device f64, G by legal rank) and table
+ * (device int16 [max_considered + 1][n_root]) are copied in stream order into
+ * buffers the handle owns; g == NULL turns the gate off (the default).  Call it
+ * before the hz_mcts_begin of each search.  The buffers are allocated by the
+ * first call (the table's for the largest table admitted, 70 x 32767 int16 =
+ * 4.6 MB) and keep their addresses until hz_mcts_destroy, so a captured
+ * simulation stays valid while G and the table change; whether the gate is on,
+ * the table's shape and the two constants are held by value in a capture: a
+ * capture is to be replayed only under the settings it was captured with
+ * (each call rewrites the table's contents).  1 <= max_considered <= 69,
+ * 1 <= n_root <= 32767, c_visit >= 0, c_scale >= 0.  The gate does not combine
+ * with root noise, budgets or a carried tree (the callers refuse those).
+ *   The table, built by the caller for a search of S simulations (n_root =
+ * S - 1: simulation 1 expands the root and visits no edge): row m is the
+ * paper's considered-visit sequence for m actions and n_root visits.  With
+ * k = m and every slot's counter 0, while the row is short: max(1, int(n_root /
+ * (ceil(log2 m) k))) rounds, each appending the counters of slots 0 .. k - 1
+ * and then incrementing them; then k = max(2, k / 2).  Rows 0 and 1 are
+ * 0, 1, 2, ...  (m 4, 8 visits): 0 0 0 0 1 1 2 2.
+ *   Under the gate node 0's expansion also stores the network's fp32 value of
+ * the root (v_root) and, per root edge e, score0_e = G[rank of e's move among
+ * the legal moves] + log((double)P_e) (the device's log, taken this once; -inf
+ * where P_e is 0).  hz_mcts_root_gumbel_scores copies score0 to out[n][69]
+ * (device f64, by root edge index, 0.0 past the root's edges).
+ *   Root select (level 0 of the walk, a root with ne > 0 edges; edges in
+ * ascending index): t = sum N; m = min(max_considered, ne); cv =
+ * table[m][min(t, n_root - 1)]; edge e is a candidate iff N_e == cv (if no edge
+ * is, every edge is: a search longer than the table); score_e = max(-1e9,
+ * score0_e + sigma_e); the first candidate with the largest score wins.
+ *   sigma: q_e = W_e / N_e on visited edges; sp = sum (double)P_e and spq =
+ * sum (double)P_e * q_e over the visited edges; v_mix = (v_root + t * (sp > 0 ?
+ * spq / sp : 0)) / (t + 1); the completed q_e is q_e where visited, else v_mix;
+ * mn, mx its minimum and maximum over the root's edges; sigma_e = ((c_visit +
+ * max N) * c_scale) * ((q_e - mn) / max(mx - mn, 1e-8)).  Every operation is
+ * one IEEE fp64 operation, none fused.  The two sums are xor butterflies over
+ * 64 lanes: lane l starts with edge l's term plus edge l + 64's (0.0 for an
+ * absent or unvisited edge), then v[l] = v[l] + v[l ^ off] for off = 1, 2, 4,
+ * 8, 16, 32 (every lane ends with the same sum).
+ *   hz_mcts_gumbel_result, after the search (device outputs): action[n] int16 =
+ * the move of the first edge with the largest score among those with N_e ==
+ * max N; pi[n][143] f32 = softmax over the root's edges of log P_e + sigma_e
+ * (fp64, the maximum subtracted, the sum a butterfly as above; zero off the
+ * root's edges; should every P_e be 0, the softmax of sigma alone); value[n]
+ * f64 = v_mix.  A root without edges (stuck, terminal, left out of the search,
+ * or with more than 69): action -1, a zero row, value 0.  Both reports return
+ * -1 while the gate is off. */
+int hz_root_gumbel(int32_t n, uint64_t seed, uint64_t board_base, uint64_t move, double *out, void *stream);
+int hz_mcts_set_gumbel(hz_mcts *mcts, const double *g, const int16_t *table, int32_t max_considered, int32_t n_root,
+                       double c_visit, double c_scale);
+int hz_mcts_root_gumbel_scores(hz_mcts *mcts, double *out);
+int hz_mcts_gumbel_result(hz_mcts *mcts, int16_t *action, float *pi, double *value);
 /* ---- tree reuse: the searched subtree carried into the next search ----------
  * No reference counterpart (MCTS.py:288 builds a fresh Node per call): this is
  * the build's defined behaviour, off unless the caller asks for it, pinned by
