@@ -758,12 +758,8 @@ static int launch_play2(hz_env *e, int32_t max_plies, int32_t *games_done, int32
   a.seed = e->seed;
   a.n = e->n;
   a.max_plies = max_plies;
-  a.draws = e->seed_ahead;
   a.err = e->wait_err;
   a.spin = e->spin_limit;
-  a.fell_lim = e->p2_fell_lim;
-  for (int k = 0; k < kP2Play - 1; k++) a.cut[k] = e->p2_cut[k];
-  for (int k = 0; k <= kP2Draw; k++) a.dcut[k] = e->p2_dcut[k];
   a.seed_base = e->seed_base;
   a.nrow = (long)e->nrow;
   a.games_done = games_done;
@@ -773,36 +769,58 @@ static int launch_play2(hz_env *e, int32_t max_plies, int32_t *games_done, int32
   a.ep_in = e->p2_ep[w];
   a.ep_out = e->p2_ep[r];
   auto sl = [c](int s) { return ((c - s) % kP2Stream + kP2Stream) % kP2Stream; };
-  for (int s = 1; s < kP2Stages; s++) {
+  for (int s = 1; s < kP2SDraw; s++) {
     a.s_mt[s] = e->p2_s[sl(s)];
     a.s_tag[s] = e->p2_s_tag[sl(s)];
-    a.s_cur[s] = e->p2_s_cur[sl(s)];
   }
   a.s_idx_last = sl(kP2Last);
   a.p1h_w = e->p2_p1h[r];
-  a.p1h_r = e->p2_p1h[w];
   a.p1t_w = e->p2_p1t[r];
-  a.p1t_r = e->p2_p1t[w];
   a.p2h_w = e->p2_p2h[r];
-  a.p2h_r = e->p2_p2h[w];
   a.p3h_w = e->p2_p3h[r];
-  a.p3h_r = e->p2_p3h[w];
-  for (int k = 0; k < kP2Draw - 1; k++) {
-    a.x_w[k] = e->p2_x[k][r];
-    a.x_r[k] = e->p2_x[k][w];
+  // what each wave of a seed block decides by and starts from (P2a, P2b, P2c)
+  a.seed_tag[0] = e->p2_p1t[w];
+  a.seed_tag[1] = a.s_tag[2];
+  a.seed_tag[2] = a.s_tag[3];
+  a.seed_h[0] = e->p2_p1h[w];
+  a.seed_h[1] = e->p2_p2h[w];
+  a.seed_h[2] = e->p2_p3h[w];
+  // one record per draw stage and per play stage (P2DrawArgs, P2PlayArgs).  A
+  // first stage has no previous one: its `in` names the second stage's, valid
+  // memory that it reads and discards.
+  const int draws = e->seed_ahead;
+  for (int k = 0; k < kP2Draw; k++) {
+    P2DrawArgs &d = a.dr[k];
+    const int s = kP2SDraw + k;
+    d.slot = e->p2_s[sl(s)];
+    d.stag = e->p2_s_tag[sl(s)];
+    d.cur = e->p2_s_cur[sl(s)];
+    d.in = e->p2_x[k > 0 ? k - 1 : 0][w];
+    d.out = k == kP2Draw - 1 ? e->p2_pl[c % kP2Ring] : e->p2_x[k][r];
+    d.d0 = e->p2_dcut[k];
+    d.d1 = k == kP2Draw - 1 ? draws : std::min(draws, e->p2_dcut[k + 1]);
   }
-  a.pl_w = e->p2_pl[c % kP2Ring];
   a.h_w = e->p2_h[c % kP2Ring];
   a.ht_w = e->p2_h_tag[c % kP2Ring];
-  for (int st = 0; st < kP2Play; st++) {  // written by call c - 1 - st
-    const int k = (c + kP2Ring - 1 - st) % kP2Ring;
-    a.pl_r[st] = e->p2_pl[k];
-    a.h_r[st] = e->p2_h[k];
-    a.ht_r[st] = e->p2_h_tag[k];
-  }
-  for (int st = 0; st < kP2Play - 1; st++) {
-    a.m_w[st] = e->p2_m[st][r];
-    a.m_r[st] = e->p2_m[st][w];
+  for (int st = 0; st < kP2Play; st++) {
+    P2PlayArgs &p = a.pp[st];
+    const bool last = st == kP2Play - 1;
+    const int s = kP2SPlay + st;
+    const int k = (c + kP2Ring - 1 - st) % kP2Ring;  // the script and the hashes written by call c - 1 - st
+    p.ep = last ? e->episode : e->p2_ep[w];
+    p.ep_off = last ? 0 : kP2Play - 1 - st;
+    p.g0 = st > 0 ? e->p2_cut[st - 1] : 0;
+    p.g_end = last ? max_plies : std::min(e->p2_cut[st], max_plies);
+    p.fell_lim = e->p2_fell_lim;
+    p.ptag = e->p2_pl[k].tag;
+    p.pk = e->p2_pl[k].k;
+    p.q = st > 0 ? e->p2_m[st - 1][w].q : e->p2_pl[k].q;
+    p.h = e->p2_h[k];
+    p.ht = e->p2_h_tag[k];
+    p.slot = e->p2_s[sl(s)];
+    p.cur = e->p2_s_cur[sl(s)];
+    p.in = e->p2_m[st > 0 ? st - 1 : 0][w];  // play stage st - 1 -> st, by call parity
+    p.out = e->p2_m[last ? 0 : st][r];       // (the last stage writes none)
   }
   const int nblk = grid_for(e->n);
   hipLaunchKernelGGL(k_play2, dim3(4 * nblk), dim3(kStageThreads), kResetLds, e->stream, a, nblk);

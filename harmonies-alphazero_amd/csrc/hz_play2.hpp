@@ -156,49 +156,80 @@ constexpr int kP2Stamps = 48;  // stamp slots per board in k_play2 (tools/p2_rol
     if (g_stamps && b < a.n) g_stamps[(size_t)b * kP2Stamps + (slot)] = __builtin_amdgcn_s_memtime() - (t0); \
     __builtin_amdgcn_sched_barrier(0);                                                                           \
   } while (0)
+// a value in hand before the next stamp (an opening's arguments, a load's
+// result): the stamp then says when it arrived
+#define P2_USE_V(x) asm volatile("" ::"v"(x))
+#define P2_USE_S(x) asm volatile("" ::"s"(x))
 #else
 #define P2_PHASE(slot, t0) \
   do {                     \
   } while (0)
+#define P2_USE_V(x) \
+  do {              \
+  } while (0)
+#define P2_USE_S(x) \
+  do {              \
+  } while (0)
 #endif
 static_assert(4 * kP2WinRows * kWinStride * 4 <= (int)kResetLds, "a window per wave of a draw block");
 
+// What a stage's opening needs of the kernel's arguments is one contiguous
+// record per stage, indexed by the wave's stage: a wave fetches it with
+// scalar loads issued together and waits once (p2_draw_args, p2_play_args),
+// where an argument block indexed field by field (s_tag[4 + stage], then
+// x_r[stage - 1], ...) cost a scalar round trip per field, each between two
+// vector ones.  launch_play2 fills them.
+struct P2DrawArgs {          // draw stage k
+  const uint32_t *slot;      // its stream slot, its tag and its cursor table
+  const int32_t *stag;
+  int32_t *cur;
+  P2Draw in, out;            // the previous draw stage's script (k = 0: any valid one, read and discarded) and this one's
+  int d0, d1;                // draws [d0, d1)
+};
+struct P2PlayArgs {          // play stage st
+  const int32_t *ep;         // the episode counter the stage's episode follows from: ep_in, the last stage the board's own
+  int ep_off;                // episode = ep[b] + ep_off
+  int g0;                    // the ply it expects to start at: cut[st - 1], 0 for the first
+  int g_end;                 // its last ply's end: min(cut[st], max_plies), max_plies for the last
+  int fell_lim;              // slot rows it may draw from (HZ_P2_FELL_LIMIT; at most kP2Twist)
+  const int32_t *ptag, *pk;  // the last draw stage's script: tag and draws done (written st + 1 calls before)
+  const uint64_t *q;         // [4][nrow] the script: the draw stage's (st = 0), else what the previous play stage left of it
+  const uint32_t *h;         // [kRulePlies][nrow] the episode's rule hashes
+  const int32_t *ht;         // [nrow] their episode
+  uint32_t *slot;            // the stream slot and its cursor table
+  const int32_t *cur;
+  P2Mid in, out;             // the previous play stage's state (st = 0: any valid one, read and discarded) and this one's
+};
 struct P2Args {
   uint64_t *st;
   uint32_t *mt;
   int32_t *pos, *ply, *episode;
   uint64_t *seed;
-  int n, max_plies, draws;
-  int cut[kP2Play - 1];
-  int dcut[kP2Draw + 1];      // draw stage k: draws [dcut[k], dcut[k + 1])
+  int n, max_plies;
   uint64_t seed_base;
   long nrow;
   int32_t *games_done, *steps_done, *mt_src;
   int32_t *win_tag;           // [nrow] PlyWin's tags: the last play stage sets its board's to none
   const int32_t *ep_in;
   int32_t *ep_out;
-  uint32_t *s_mt[kP2Stages];  // the stream slot of each stage this call ([0], P1: none)
-  int32_t *s_tag[kP2Stages];  // [nrow] episode * 8 + 3 P2a / 4 P2b / 5 seeded, rows 0-223 twisted
-  int32_t *s_cur[kP2Stages];  // [kAheadDraws + 1][nrow] cursor before draw 0 and after each draw
+  P2DrawArgs dr[kP2Draw];
+  P2PlayArgs pp[kP2Play];
+  uint32_t *s_mt[kP2SDraw];   // the stream slots of the pass-2 stages this call ([0], P1: none)
+  int32_t *s_tag[kP2SDraw];   // [nrow] episode * 8 + 3 P2a / 4 P2b / 5 seeded, rows 0-223 twisted
+  // what wave k of a seed block reads before its barrier, k = 0 P2a, 1 P2b, 2 P2c (and the twist)
+  const int32_t *seed_tag[3]; // [nrow] the tag it decides by: P1's (episode * 8 + 2), s_tag[2], s_tag[3]
+  const uint32_t *seed_h[3];  // the hand-off: [nrow] P1 -> P2a: pass 1's row-1 word after its 624th step; [4][nrow]
+                              // P2a -> P2b and P2b -> P2c: pass 2's last value, pass 1's row-1 word, row 2's final
+                              // word, pass 1's word of the stage's last row
   int s_idx_last;             // the last play stage's slot index (materialize: mt_src = 2 + index)
-  uint32_t *p1h_w;            // [nrow] P1 -> P2a: pass 1's row-1 word after its 624th step
-  const uint32_t *p1h_r;
-  int32_t *p1t_w;             // [nrow] its tag: episode * 8 + 2
-  const int32_t *p1t_r;
-  uint32_t *p2h_w;            // [4][nrow] P2a -> P2b: pass 2's last value, pass 1's row-1 word, row 2's final word,
-  const uint32_t *p2h_r;      //           pass 1's word of P2a's last row
-  uint32_t *p3h_w;            // [4][nrow] P2b -> P2c: the same
-  const uint32_t *p3h_r;
-  P2Draw x_w[kP2Draw - 1], x_r[kP2Draw - 1];  // D1 -> D2 -> ... (tag: episode * 8 + stages done)
-  P2Draw pl_w, pl_r[kP2Play];     // the last draw stage's script: written this call; read by play stage st (st + 1 calls later)
-  P2Mid m_w[kP2Play - 1], m_r[kP2Play - 1];  // play stage st -> st + 1 (written / read this call)
-  uint32_t *h_w;                  // [kRulePlies][nrow] rule hashes
-  const uint32_t *h_r[kP2Play];
+  uint32_t *p1h_w;            // [nrow] P1's hand-off as written this call, and its tag
+  int32_t *p1t_w;
+  uint32_t *p2h_w;            // [4][nrow] P2a's
+  uint32_t *p3h_w;            // [4][nrow] P2b's
+  uint32_t *h_w;                  // [kRulePlies][nrow] rule hashes (read by play stage st st + 1 calls later)
   int32_t *ht_w;                  // [nrow] their episode
-  const int32_t *ht_r[kP2Play];
   int32_t *err;                   // the env's wait-error word
   int spin;                       // spin bound of the twist wave's waits
-  int fell_lim;                   // slot rows a play stage may draw from (HZ_P2_FELL_LIMIT; at most kP2Twist)
 };
 
 // PlayDraw for the prepared stages: the pile script in registers, then (a
@@ -231,10 +262,13 @@ struct PlayDraw2 : PileScript {
 // the rule policy's plies [g, g_end) of one board (k_rollout's ply loop, no
 // reset, no recording): turn pairs while the wave allows, single plies
 // otherwise; hashes from a pipeline slot when `hs` (row stride nr) holds the
-// episode's, else computed.  Returns the plies played.
+// episode's, else computed.  h0 (if not null): the slot's rows [h0_g, h0_g + 8)
+// of this board, h0_g wave-uniform, loaded by the caller with its opening;
+// they serve as the first pair read ahead when every lane has the slot's
+// hashes.  Returns the plies played.
 template <class Draw>
 __device__ __forceinline__ int p2_plies(State &s, Draw &draw, int g, int g_end, uint64_t rkey, const uint32_t *hs,
-                                        size_t nr) {
+                                        size_t nr, const uint32_t *h0 = nullptr, int h0_g = -1) {
   const int g0 = g;
   auto hash = [&](int ply) -> uint32_t { return hs && ply < kRulePlies ? hs[(size_t)ply * nr] : rule_h32(rkey, ply); };
   // the next turn pair's hashes, read one pair ahead (a slot's are in HBM).
@@ -243,6 +277,11 @@ __device__ __forceinline__ int p2_plies(State &s, Draw &draw, int g, int g_end, 
   const bool all_hs = __all(hs != nullptr);
   uint32_t hn[8];
   int hn_g = -1;  // (wave-uniform)
+  if (h0 && all_hs) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) hn[j] = h0[j];
+    hn_g = h0_g;
+  }
   while (g < g_end) {
     if (phase_of(s.misc) == PH_OVER) break;
     if (__all(g + 8 <= g_end && turn_pair_safe(s))) {
@@ -310,6 +349,33 @@ __device__ __forceinline__ uint4 p2_ld4(const uint32_t *p) {
   }
   return *reinterpret_cast<const uint4 *>(p);
 }
+// An opening's load of a lane's element of a wave-uniform array: `off` is the
+// lane's byte offset (32 bits), so the address is the array's scalar
+// registers plus one vector register shared by the batch's loads, with no
+// vector address arithmetic (and none of its waits) between them.
+// (The arrays are in global memory, and the load says so: behind p2_row's
+// statement the compiler no longer knows, and a flat load's wait is for every
+// load that is out.)
+template <class T>
+__device__ __forceinline__ T p2_at(const T *base, uint32_t off) {
+  typedef __attribute__((address_space(1))) const char GlobalByte;
+  typedef __attribute__((address_space(1))) const T GlobalT;
+  return *(GlobalT *)((GlobalByte *)base + off);
+}
+// a row of such an array, its address kept in scalar registers (the compiler
+// otherwise adds the lane's offset first and the rows to that, in vector
+// registers, between the loads)
+template <class T>
+__device__ __forceinline__ const T *p2_row(const T *base, size_t row_words) {
+  const T *p = base + row_words;
+  asm volatile("" : "+s"(p));
+  return p;
+}
+// The order of an opening, for the compiler: no load crosses a fence, and
+// p2_fence_use(x) is the first use of a loaded x, so whatever depends on x
+// comes after the loads issued before it.
+__device__ __forceinline__ void p2_fence() { asm volatile("" ::: "memory"); }
+__device__ __forceinline__ void p2_fence_use(int &x) { asm volatile("" : "+v"(x)::"memory"); }
 // a store read by another stage in a later call only: write-through (sc1)
 // like the slot stores (HZ_P2_AUX), so the kernel's end has no dirty lines
 // of it to write back
@@ -593,11 +659,12 @@ __device__ __forceinline__ void p2_tail(const P2Out &o, int lane, uint32_t &prev
 // only by the twist, which needs from each row r only its twist part
 // (rows r and r + 1's words): P2a and P2b store that instead of the final
 // word (one step late, when row r + 1 is known), so the twist is one xor
-// per word with the far row.  (e, ok: the board's episode and whether the
-// stage's input is this episode's, read by every wave of the block before
-// its barrier, so before P2c rewrites its tag.)
+// per word with the far row.  (e, ok, hw: the board's episode, whether the
+// stage's input is this episode's, and the hand-off's words, read by every
+// wave of the block before its barrier, so before P2c rewrites its tag.)
 template <int K>  // 0 P2a, 1 P2b, 2 P2c
-__device__ __forceinline__ void p2_third(const P2Args &a, int b0, int lane, int e, bool ok, int *s_prog) {
+__device__ __forceinline__ void p2_third(const P2Args &a, int b0, int lane, int e, bool ok, const uint32_t (&hw)[4],
+                                         int *s_prog) {
   const int b = b0 + lane;
   const bool act = b < a.n;
   const size_t nr = (size_t)a.nrow;
@@ -612,15 +679,14 @@ __device__ __forceinline__ void p2_third(const P2Args &a, int b0, int lane, int 
   p2_keys(episode_seed(a.seed_base, b, e), kA, kB);
   uint32_t prev, first1, row2, q;
   if (K == 0) {
-    first1 = act ? a.p1h_r[b] : 0u;
+    first1 = act ? hw[0] : 0u;
     prev = first1;
     q = p1_row1(kA, kB);
   } else {
-    const uint32_t *h = K == 1 ? a.p2h_r : a.p3h_r;
-    prev = act ? h[b] : 0u;
-    first1 = act ? h[nr + b] : 0u;
-    row2 = act ? h[2 * nr + b] : 0u;
-    q = act ? h[3 * nr + b] : 0u;
+    prev = act ? hw[0] : 0u;
+    first1 = act ? hw[1] : 0u;
+    row2 = act ? hw[2] : 0u;
+    q = act ? hw[3] : 0u;
   }
   const __amdgpu_buffer_rsrc_t rs = p2_slot_rsrc(slot, b0, nr);
   const int row_bytes = __builtin_amdgcn_readfirstlane((int)(nr * 4));
@@ -756,15 +822,41 @@ __device__ __forceinline__ void p2_seed(const P2Args &a, int blk) {
   const int b0 = blk * kBlock, b = b0 + lane;
   const bool act = b < a.n;
   if (tid == 0) s_prog = 0;
-  // each stage's episode and decision (and P2c's for the twist wave), read
-  // before the barrier, so before any wave rewrites a tag
-  const int k = w < 3 ? w : 2;
-  const int e = act ? a.ep_in[b] + kP2Last - 1 - k : 0;
-  const bool ok = act && (k == 0 ? a.p1t_r[b] : a.s_tag[1 + k][b]) == e * 8 + 2 + k;
+  // each stage's episode, decision and hand-off (P2c's episode and decision
+  // for the twist wave), read before the barrier, so before any wave
+  // rewrites a tag.  One round trip: the wave's stage is a scalar, so its
+  // tag's and its hand-off's addresses come from the arguments with scalar
+  // loads, and the episode counter, the tag and the hand-off's four words
+  // are loaded together, from a clamped board index (a lane past n reads
+  // board n - 1's, valid memory, and discards them), and compared after.
+  // (P2a's hand-off is one word: its four loads are of that word.)
+  const int wv = __builtin_amdgcn_readfirstlane(w);
+  const int k = wv < 3 ? wv : 2;
+  const int32_t *tagp = a.seed_tag[k];
+  const uint32_t *hp = a.seed_h[k];
+  const int32_t *ep_in = a.ep_in;
+  const int n = a.n;
+  const size_t hrow = k == 0 ? 0 : (size_t)a.nrow;
+  asm volatile("" ::"s"(tagp), "s"(hp), "s"(ep_in), "s"(n), "s"(hrow));  // (one scalar batch: p2_draw_args)
+  __builtin_amdgcn_sched_barrier(0);
+  const int bc = min(b, n - 1);
+  const int hb = wv < 3 ? bc : b0;  // (the twist wave uses no hand-off: one address for the wave)
+  const uint32_t *hrp[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) hrp[i] = p2_row(hp, i * hrow);
+  p2_fence();
+  int ep = p2_at(ep_in, (uint32_t)bc * 4u);
+  const int tag = p2_at(tagp, (uint32_t)bc * 4u);
+  uint32_t hw[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) hw[i] = p2_at(hrp[i], (uint32_t)hb * 4u);
+  p2_fence_use(ep);
+  const int e = act ? ep + kP2Last - 1 - k : 0;
+  const bool ok = act && tag == e * 8 + 2 + k;
   __syncthreads();
-  if (w == 0) p2_third<0>(a, b0, lane, e, ok, &s_prog);
-  else if (w == 1) p2_third<1>(a, b0, lane, e, ok, &s_prog);
-  else if (w == 2) p2_third<2>(a, b0, lane, e, ok, &s_prog);
+  if (w == 0) p2_third<0>(a, b0, lane, e, ok, hw, &s_prog);
+  else if (w == 1) p2_third<1>(a, b0, lane, e, ok, hw, &s_prog);
+  else if (w == 2) p2_third<2>(a, b0, lane, e, ok, hw, &s_prog);
   else p2_twist(a, b0, lane, __any(ok), &s_prog);
 }
 
@@ -773,6 +865,36 @@ __device__ __forceinline__ void p2_seed(const P2Args &a, int blk) {
 // cursor (the wave's 64 boards, staged here); `in` (stage > 0) holds the
 // draws so far, `out` gets them plus these; the cursors go to the slot's
 // cursor table
+// A stage's part of the arguments, and the common ones its opening needs, in
+// scalar registers: the loads are issued together and the empty statement,
+// which takes every value, waits for them once (scalar loads return out of
+// order: one wait for all that are out).  Left to itself the compiler
+// fetches each where it is first used, a scalar round trip between two
+// vector ones.
+__device__ __forceinline__ P2DrawArgs p2_draw_args(const P2Args &a, int stage, int &n, size_t &nr,
+                                                   const int32_t *&ep_in) {
+  const P2DrawArgs r = a.dr[stage];
+  n = a.n;
+  nr = (size_t)a.nrow;
+  ep_in = a.ep_in;
+  asm volatile("" ::"s"(r.slot), "s"(r.stag), "s"(r.cur), "s"(r.in.tag), "s"(r.in.k), "s"(r.in.q), "s"(r.in.bag),
+               "s"(r.in.c), "s"(r.out.tag), "s"(r.out.k), "s"(r.out.q), "s"(r.out.bag), "s"(r.out.c), "s"(r.d0),
+               "s"(r.d1), "s"(n), "s"(nr), "s"(ep_in));
+  __builtin_amdgcn_sched_barrier(0);
+  return r;
+}
+__device__ __forceinline__ P2PlayArgs p2_play_args(const P2Args &a, int st, int &n, size_t &nr, uint64_t &seed_base) {
+  const P2PlayArgs r = a.pp[st];
+  n = a.n;
+  nr = (size_t)a.nrow;
+  seed_base = a.seed_base;
+  asm volatile("" ::"s"(r.ep), "s"(r.ep_off), "s"(r.g0), "s"(r.g_end), "s"(r.ptag), "s"(r.pk), "s"(r.q), "s"(r.h),
+               "s"(r.ht), "s"(r.slot), "s"(r.cur), "s"(r.in.tag), "s"(r.in.st), "s"(r.in.q), "s"(r.in.i),
+               "s"(r.out.tag), "s"(r.out.st), "s"(r.out.q), "s"(r.out.i), "s"(n), "s"(nr), "s"(seed_base),
+               "s"(r.fell_lim));
+  __builtin_amdgcn_sched_barrier(0);
+  return r;
+}
 __device__ __forceinline__ int wave_min_i(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
@@ -781,15 +903,26 @@ __device__ __forceinline__ int wave_min_i(int v) {
 __device__ __forceinline__ void p2_draw_stage(const P2Args &a, int b0, int lane, int stage, int base) {
   const int b = b0 + lane;
   HZ_DIAG_T0(t0);
-  const bool act = b < a.n;
-  const size_t nr = (size_t)a.nrow;
-  const int d0 = a.dcut[stage], d1 = stage == kP2Draw - 1 ? a.draws : min(a.draws, a.dcut[stage + 1]);
-  const int e = act ? a.ep_in[b] + kP2Last - kP2SDraw - stage : 0;
-  const uint32_t *slot = a.s_mt[kP2SDraw + stage];
-  int32_t *cur = a.s_cur[kP2SDraw + stage] + b;
-  const P2Draw &in = a.x_r[stage > 0 ? stage - 1 : 0];
-  const P2Draw &out = stage == kP2Draw - 1 ? a.pl_w : a.x_w[stage < kP2Draw - 1 ? stage : 0];
-  bool ok = act && a.s_tag[kP2SDraw + stage][b] == e * 8 + 5;
+  // The opening is one scalar batch and one vector batch.  Scalar: the
+  // stage's record and the three common arguments, loaded together and
+  // waited for once (p2_draw_args).  Vector: the episode counter, the slot's
+  // tag and the previous stage's hand-off (tag, draws, cursor, bag, script),
+  // then the window's 24 loads, all issued before the first wait and in that
+  // order, so the small ones are back (vmcnt counts in order) while the
+  // window is still in flight; the tags are compared after.  No guard: a
+  // lane past n reads board n - 1's words (valid memory in every array,
+  // whether sized n or nrow) and discards them; D1, which has no previous
+  // stage, reads one board's hand-off of D2's input and discards it.
+  int n;
+  size_t nr;
+  const int32_t *ep_in;
+  const P2DrawArgs r = p2_draw_args(a, stage, n, nr, ep_in);
+  if (stage == 1) P2_PHASE(33, t0);
+  const int d0 = r.d0, d1 = r.d1;
+  const bool act = b < n;
+  const uint32_t *slot = r.slot;
+  int32_t *cur = r.cur + b;
+  const P2Draw &in = r.in, &out = r.out;
   int k0 = 0, c0 = kP2Ahead;
   uint64_t bag = initial_bag(), q[kAheadWords] = {0, 0, 0, 0};
   // the window: rows [r0, r0 + kP2Win), 16-B loads (four boards of a row per
@@ -813,19 +946,43 @@ __device__ __forceinline__ void p2_draw_stage(const P2Args &a, int b0, int lane,
   // the kernel's arguments): every draw of a script is from a bag of more
   // than 21 tiles, so it consumes at least three words, and a board that has
   // made d0 draws stands at row 3 d0 or later.  So the window's loads go out
-  // with the tags' and the hand-off's, one round trip instead of two (rows of
+  // behind the tags' and the hand-off's, in the same round trip (rows of
   // another episode are never read: !ok).  HZ_P2_STATIC_WIN=0 (A/B builds):
   // from the wave's lowest cursor, known only after the hand-off arrived.
   const int rs = kP2StaticWin ? __builtin_amdgcn_readfirstlane((3 * d0) & ~3) : 0;
-  if (kP2StaticWin || stage == 0) win_load(rs);
-  if (stage > 0 && act) {  // (one round trip: used only if the tag matches)
-    const int itag = in.tag[b];
-    k0 = in.k[b];
-    c0 = in.c[b];
-    bag = in.bag[b];
+  const int bc = min(b, n - 1), bi = stage > 0 ? bc : b0;
+  const uint32_t o4 = (uint32_t)bc * 4u, i4 = (uint32_t)bi * 4u, i8 = i4 * 2u;
+  const uint64_t *iqr[kAheadWords];
 #pragma unroll
-    for (int i = 0; i < kAheadWords; i++) q[i] = in.q[(size_t)i * nr + b];
+  for (int i = 0; i < kAheadWords; i++) iqr[i] = p2_row(in.q, (size_t)i * nr);
+  p2_fence();
+  int ep = p2_at(ep_in, o4);
+  const int stag = p2_at(r.stag, o4);
+  const int itag = p2_at(in.tag, i4), ik = p2_at(in.k, i4), ic = p2_at(in.c, i4);
+  const uint64_t ibag = p2_at(in.bag, i8);
+  uint64_t iq[kAheadWords];
+#pragma unroll
+  for (int i = 0; i < kAheadWords; i++) iq[i] = p2_at(iqr[i], i8);
+  p2_fence();
+  if (kP2StaticWin || stage == 0) win_load(rs);
+  p2_fence_use(ep);
+  if (stage == 1) {
+    P2_USE_V(ep);
+    P2_PHASE(34, t0);
+  }
+  const int e = act ? ep + kP2Last - kP2SDraw - stage : 0;
+  bool ok = act && stag == e * 8 + 5;
+  if (stage > 0) {
+    k0 = ik;
+    c0 = ic;
+    bag = ibag;
+#pragma unroll
+    for (int i = 0; i < kAheadWords; i++) q[i] = iq[i];
     ok = ok && itag == e * 8 + stage;
+  }
+  if (stage == 1) {
+    P2_USE_V((int)ok);
+    P2_PHASE(26, t0);
   }
   bool draws = ok && k0 >= d0 && d0 < d1;
   int r0 = rs;
@@ -920,19 +1077,8 @@ __device__ __forceinline__ void p2_mid_put(const P2Mid &m, size_t nr, int b, con
   p2_st(&m.i[2 * nr + b], d.fell ? d.gm.cursor() : -1);
   p2_st(&m.tag[b], e);
 }
-// the previous play stage's state; the draw source continues its script
-// (nd entries, cursors in `cur`) or the slot stream it fell onto
-__device__ __forceinline__ PlayDraw2 p2_mid_get(const P2Mid &m, size_t nr, int b, State &s, int &g, int nd,
-                                               uint32_t *slot, const int32_t *cur, int fell_lim) {
-#pragma unroll
-  for (int k = 0; k < 4; k++) s.pl[k] = m.st[(size_t)k * nr + b];
-  s.piles = m.st[4 * nr + b];
-  s.misc = m.st[5 * nr + b];
-  const int d = m.i[b], fc = m.i[2 * nr + b];
-  g = m.i[nr + b];
-  return PlayDraw2{{m.q[b], m.q[nr + b], m.q[2 * nr + b], m.q[3 * nr + b], d, nd}, fc >= 0,
-                   MTR(slot, (int)nr, fc >= 0 ? fc : 0, fell_lim), cur + (size_t)nd * nr};
-}
+// (read back by the next play stage's opening, p2_play: m.i is script entries
+// used, plies played, the slot stream's cursor if the game fell onto it)
 
 // Play stage st on episode ep + kP2Play - 1 - st (the last stage: the rest of
 // episode ep, or all of it).  In a play block (in_block) wave w runs stage
@@ -946,46 +1092,104 @@ __device__ __forceinline__ void p2_play(const P2Args &a, int blk, int st, bool i
   __shared__ uint64_t s_lds_mask;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int b0 = blk * kBlock, b = b0 + lane;
-  const bool act = b < a.n;
-  const uint64_t actmask = __ballot(act);
-  const int nb = a.n - b0 < kBlock ? a.n - b0 : kBlock;
-  const size_t nr = (size_t)a.nrow;
   HZ_DIAG_T0(t0);
   const bool last = st == kP2Play - 1;
+  // The opening is one scalar batch and one vector batch.  Scalar: the
+  // stage's record and n, nrow (p2_play_args).  Vector, all issued before the
+  // first wait and used only after it: the episode counter, the script's tag
+  // and length, the previous stage's tag, the hashes' episode, the script,
+  // the previous stage's state, and the eight hash rows of the turn pair the
+  // stage expects to start with, [g0, g0 + 8) (g0 = the cut before it, an
+  // argument; p2_plies takes them as its first pair read ahead, and uses
+  // them only if every lane has the slot's hashes and stands at g0).  No
+  // guard: a lane past n reads board n - 1's words (valid memory in every
+  // array, whether sized n or nrow) and discards them; the first stage,
+  // which has no previous one, reads one board's state of the second stage's
+  // input and discards it.  The tags are compared after.
+  int n;
+  size_t nr;
+  uint64_t seed_base;
+  const P2PlayArgs r = p2_play_args(a, st, n, nr, seed_base);
+  const int fell_lim = r.fell_lim;
+  if (last) P2_PHASE(38, t0);
+  const bool act = b < n;
+  const uint64_t actmask = __ballot(act);
+  const int nb = n - b0 < kBlock ? n - b0 : kBlock;
+  const int bc = min(b, n - 1), bi = st > 0 ? bc : b0;
+  const uint32_t c4 = (uint32_t)bc * 4u, c8 = c4 * 2u, i4 = (uint32_t)bi * 4u, i8 = i4 * 2u;
+  // (a pair past the hash table, cuts up to 2^20 are accepted, is not loaded early: the rows of ply 0, unused)
+  const bool h0_fits = r.g0 + 8 <= kRulePlies;
+  const int h0_g = h0_fits ? r.g0 : -1;
+  const size_t h0_row = h0_fits ? (size_t)r.g0 : 0;
+  const uint64_t *qr[4], *str[6];
+  const int32_t *ir[3];
+  const uint32_t *hr[8];
+#pragma unroll
+  for (int k = 0; k < 4; k++) qr[k] = p2_row(r.q, (size_t)k * nr);
+#pragma unroll
+  for (int k = 0; k < 6; k++) str[k] = p2_row(r.in.st, (size_t)k * nr);
+#pragma unroll
+  for (int k = 0; k < 3; k++) ir[k] = p2_row(r.in.i, (size_t)k * nr);
+#pragma unroll
+  for (int j = 0; j < 8; j++) hr[j] = p2_row(r.h, (h0_row + j) * nr);
+  p2_fence();
+  int ep = p2_at(r.ep, c4);
+  const int ptag = p2_at(r.ptag, c4), nd = p2_at(r.pk, c4), itag = p2_at(r.in.tag, i4), htg = p2_at(r.ht, c4);
+  const int id = p2_at(ir[0], i4), ig = p2_at(ir[1], i4), ifc = p2_at(ir[2], i4);
+  uint64_t sq[4], ist[6];
+#pragma unroll
+  for (int k = 0; k < 4; k++) sq[k] = p2_at(qr[k], c8);
+#pragma unroll
+  for (int k = 0; k < 6; k++) ist[k] = p2_at(str[k], i8);
+  uint32_t h0[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) h0[j] = p2_at(hr[j], c4);
+  p2_fence_use(ep);
+  if (last) {
+    P2_USE_V(ep);
+    P2_PHASE(39, t0);
+  }
   bool lds_used = false;
   if (act) {
-    const int e = last ? a.episode[b] : a.ep_in[b] + kP2Play - 1 - st;
-    const P2Draw &pl = a.pl_r[st];
-    const uint32_t *hsrc = a.h_r[st];
-    const int32_t *htag = a.ht_r[st];
-    uint32_t *slot = a.s_mt[kP2SPlay + st] + b;
-    const int32_t *cur = a.s_cur[kP2SPlay + st] + b;
-    const int g_end = last ? a.max_plies : min(a.cut[st < kP2Play - 1 ? st : 0], a.max_plies);
-    const uint64_t sd = episode_seed(a.seed_base, b, e), rk = rule_key(sd);
-    // every input's loads issued together (used only if the tags match)
-    const int ptag = pl.tag[b], nd = pl.k[b];
-    const int mtag = st > 0 ? a.m_r[st - 1].tag[b] : e;
-    const uint32_t *hs = htag[b] == e ? hsrc + b : nullptr;
+    const int e = ep + r.ep_off;
+    const P2Mid &mo = r.out;
+    uint32_t *slot = r.slot + b;
+    const int32_t *cur = r.cur + b;
+    const int g_end = r.g_end;
+    const uint64_t sd = episode_seed(seed_base, b, e), rk = rule_key(sd);
+    const int mtag = st > 0 ? itag : e;
+    const uint32_t *hs = htg == e ? r.h + b : nullptr;
     State s;
     int g = 0;
-    PlayDraw2 draw = st == 0 ? PlayDraw2{{pl.q[b], pl.q[nr + b], pl.q[2 * nr + b], pl.q[3 * nr + b], 0, nd}, false,
-                                         MTR(slot, (int)nr, 0, a.fell_lim), cur + (size_t)nd * nr}
-                             : p2_mid_get(a.m_r[st - 1], nr, b, s, g, nd, slot, cur, a.fell_lim);
+    PlayDraw2 draw{{sq[0], sq[1], sq[2], sq[3], 0, nd}, false, MTR(slot, (int)nr, 0, fell_lim), cur + (size_t)nd * nr};
+    if (st > 0) {  // the previous play stage's state; the draw source continues its script or the slot stream it fell onto
+#pragma unroll
+      for (int k = 0; k < 4; k++) s.pl[k] = ist[k];
+      s.piles = ist[4];
+      s.misc = ist[5];
+      g = ig;
+      draw.d = id;
+      draw.fell = ifc >= 0;
+      draw.gm = MTR(slot, (int)nr, ifc >= 0 ? ifc : 0, fell_lim);
+    }
     bool prep = ptag == e * 8 + kP2Draw && mtag == e;
+    if (last) {
+      P2_USE_V((int)prep);
+      P2_PHASE(42, t0);
+    }
     if (prep) {
       if (st == 0) {
         if (__all(nd >= 5)) draw.scripted_reset(s);
         else reset_state(s, draw);
       }
       P2_PHASE(16 + 2 * st, t0);
-      g += p2_plies(s, draw, g, g_end, rk, hs, nr);
+      g += p2_plies(s, draw, g, g_end, rk, hs, nr, h0, h0_g);
       P2_PHASE(17 + 2 * st, t0);
       // a game that drew past the slot's rows: its draws since are not the
       // stream's, so the board counts as unprepared from here on
       if (draw.lost()) prep = false;
     }
     if (!last) {
-      const P2Mid &mo = a.m_w[st < kP2Play - 1 ? st : 0];
       if (prep) p2_mid_put(mo, nr, b, s, draw, g, e);
       else mo.tag[b] = -1;
     } else {

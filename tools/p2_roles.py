@@ -25,7 +25,9 @@ for pipe in (1, 2):
               20: "playC_loaded", 21: "playC_plies", 22: "playD_loaded", 23: "playD_plies",
               24: "playE_loaded", 25: "playE_plies", 27: "playE_scored",
               28: "D1_staged", 29: "D2_staged", 30: "D3_staged", 31: "D4_staged", 32: "D5_staged",
-              35: "twist_go", 36: "twist_it1", 37: "twist_looped", 38: "twist_done_seen"} if pipe == 2 else
+              35: "twist_go", 36: "twist_it1", 37: "twist_looped",
+              # an opening taken apart, on D2 and playE (tools/p2_span.py)
+              33: "D2_args", 34: "D2_ep", 26: "D2_tags", 38: "playE_args", 39: "playE_ep", 42: "playE_tags"} if pipe == 2 else
              {5: "play", 6: "draw2", 15: "draw1", 7: "seed"})
     for only in (-1, 0, 1, 2, 3) if pipe == 2 else (-1,):
         L.hz_diag_set_role_only(-1)

@@ -90,7 +90,10 @@ out["cus_used"] = len(per_cu)
 ph = stamps.cpu().numpy().astype(np.int64)
 pnames = {16: "playA_loaded", 17: "playA_plies", 24: "playE_loaded", 25: "playE_plies", 27: "playE_scored",
           28: "D1_staged", 29: "D2_staged", 30: "D3_staged", 31: "D4_staged", 32: "D5_staged",
-          35: "twist_go", 36: "twist_it1", 37: "twist_looped"}
+          35: "twist_go", 36: "twist_it1", 37: "twist_looped",
+          # an opening taken apart, on D2 and playE: the stage's arguments in scalar registers, the
+          # episode counter's load back, the tags compared (then D2_staged / playE_loaded: every input in hand)
+          33: "D2_args", 34: "D2_ep", 26: "D2_tags", 38: "playE_args", 39: "playE_ep", 42: "playE_tags"}
 out["phases_last_column"] = {nm: [float(ph[:, k].max()), float(np.median(ph[:, k]))] for k, nm in pnames.items()}
 out["longest"] = max((v["dur_max"], k) for k, v in waves.items())
 env.close()
