@@ -7,6 +7,7 @@
 // (AoS: node j at 6*j + w).  idx[j] < 0 encodes an all-zero record.
 #pragma once
 #include "hz_device.hpp"
+#include "hz_sym.hpp"
 
 namespace hz {
 
@@ -89,12 +90,15 @@ __device__ __forceinline__ float glob_value(const uint64_t *__restrict__ st, lon
 // float4.  Glob: the wave also writes its pair's global features (small
 // batches: one launch instead of two; at 4096 items two launches measured
 // faster).  Only the wave's own LDS rows are touched, so a wave barrier
-// separates the two phases.
-template <bool Glob>
+// separates the two phases.  Sym: item j is encoded under the board symmetry
+// sym[j] & 3 (NULL: the identity): each channel's cell set is permuted
+// (hz_sym.hpp) before it is spread to the grid; the global vector holds no
+// coordinate.  Without Sym the code is what it was.
+template <bool Glob, bool Sym = false>
 __device__ __forceinline__ void encode_pair(const uint64_t *__restrict__ st, long word_stride, long item_stride,
                                             const int32_t *__restrict__ idx, int m, float *__restrict__ board,
                                             float *__restrict__ glob, int lane, long j0, uint64_t *smask,
-                                            float *sval) {
+                                            float *sval, const uint8_t *__restrict__ sym = nullptr) {
   bool live = j0 < m;
 #pragma unroll
   for (int r = 0; r < 2; r++) {
@@ -127,6 +131,7 @@ __device__ __forceinline__ void encode_pair(const uint64_t *__restrict__ st, lon
                            ((code & 8) ? b3 : n3);
             m23 |= ((set >> code) & 1u) ? hit : 0u;
           }
+          if constexpr (Sym) m23 = sym_cells(m23, sym ? sym[jb] & 3 : 0);
           mask = to_grid35(m23);
           val = 1.f;
         } else {

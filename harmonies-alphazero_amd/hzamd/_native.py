@@ -39,6 +39,8 @@ _SIGS = {
     "hz_rule_actions": ([_vp, _vp, _vp, _vp], _c.c_int),
     "hz_rule_ply": ([_vp, _vp, _vp, _vp, _vp], _c.c_int),
     "hz_encode_states": ([_vp, _c.c_int64, _c.c_int64, _vp, _c.c_int32, _vp, _vp, _vp], _c.c_int),
+    "hz_sym_records": ([_vp, _c.c_int64, _vp, _vp, _vp], _c.c_int),
+    "hz_train_batch": ([_vp, _vp, _vp, _c.c_int32, _vp, _vp, _vp, _vp, _vp], _c.c_int),
     "hz_rollout": ([_vp, _c.c_int32, _c.c_int32, _vp, _vp, _vp, _vp, _vp], _c.c_int),
     "hz_play": ([_vp, _c.c_int32, _c.c_int32, _vp, _vp, _vp, _vp, _vp], _c.c_int),
     "hz_env_set_seed_ahead": ([_vp, _c.c_int32], _c.c_int),

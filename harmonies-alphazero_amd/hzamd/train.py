@@ -36,6 +36,71 @@ class RecordSource:
         return board, glob, hd.pi_of(visits), z.reshape(-1, 1)
 
 
+def train_batch(records, idx, sym=None):
+    """One training batch from packed records int64 [M, 42] on the GPU in one
+    launch (hz_train_batch): item j is record idx[j] (idx None: record j; a
+    negative index yields zeros) under the board symmetry sym[j] (uint8, None:
+    the identity; hzamd.symmetry).  Returns (board, glob, pi, z[m, 1]); with
+    sym None the bits of RecordSource.batch."""
+    from . import _native as nat
+    dev = records.device
+    rec = records.contiguous()
+    if idx is not None:
+        idx = idx.to(device=dev, dtype=torch.int32).contiguous()
+    if sym is not None:
+        sym = sym.to(device=dev, dtype=torch.uint8).contiguous()
+    m = rec.shape[0] if idx is None else idx.shape[0]
+    if sym is not None and sym.shape[0] != m:
+        raise ValueError(f"{sym.shape[0]} symmetries for {m} items")
+    board = torch.empty(m, 38, 5, 7, dtype=torch.float32, device=dev)
+    glob = torch.empty(m, 42, dtype=torch.float32, device=dev)
+    pi = torch.empty(m, 143, dtype=torch.float32, device=dev)
+    z = torch.empty(m, 1, dtype=torch.float32, device=dev)
+    if m:
+        nat.check(nat.lib().hz_train_batch(nat.ptr(rec), nat.ptr(idx), nat.ptr(sym), m, nat.ptr(board),
+                                           nat.ptr(glob), nat.ptr(pi), nat.ptr(z), nat.stream_ptr(dev)),
+                  "hz_train_batch")
+    return board, glob, pi, z
+
+
+SYMMETRY_MODES = ("random", "all")
+
+
+class SymRecordSource:
+    """Packed records int64 [M, 42] on the GPU, each standing for its four
+    symmetric images (hzamd.symmetry); a batch is one hz_train_batch launch.
+      mode "random": M items; every batch() draws one symmetry per item from
+                     `generator` and keeps the draw in last_sym (uint8, on
+                     the device): a fresh image per example and epoch.
+      mode "all":    4 M items; item i is record i >> 2 under symmetry i & 3."""
+
+    def __init__(self, records, mode, generator=None):
+        if mode not in SYMMETRY_MODES:
+            raise ValueError(f"symmetry mode {mode!r}: expected one of {SYMMETRY_MODES}")
+        self.records = records.contiguous()
+        self.mode = mode
+        self.generator = generator
+        self.last_sym = None
+
+    def __len__(self):
+        m = self.records.shape[0]
+        return 4 * m if self.mode == "all" else m
+
+    @property
+    def device(self):
+        return self.records.device
+
+    def batch(self, idx):
+        if self.mode == "all":
+            sym = (idx & 3).to(torch.uint8)
+            idx = idx >> 2
+        else:
+            sym = torch.randint(0, 4, (idx.shape[0],), device=self.device, generator=self.generator,
+                                dtype=torch.uint8)
+        self.last_sym = sym
+        return train_batch(self.records, idx, sym)
+
+
 def featurize(records):
     """All packed records -> TensorSource (board, glob, pi, z) on their device,
     in one pass of the HIP encoder (≈6 KB per example; the reference's

@@ -32,7 +32,7 @@ from . import distributed as hd
 from .manager import ModelManager
 from .mcts import BatchedPredictor
 from .selfplay import SelfPlay
-from .train import featurize, training_phase
+from .train import SYMMETRY_MODES, SymRecordSource, featurize, training_phase
 
 
 def _dist():
@@ -46,6 +46,12 @@ class Trainer:
         self.mcts_config = mcts_config
         self.self_play_config = self_play_config
         self.training_config = training_config
+        # "symmetry": absent / "none" trains on the records as they are;
+        # "random" / "all" on their symmetric images (hzamd.train.SymRecordSource)
+        sym = training_config.get("symmetry")
+        if sym is not None and sym != "none" and sym not in SYMMETRY_MODES:
+            raise ValueError(f"training_config['symmetry'] = {sym!r}: expected 'none', 'random' or 'all'")
+        self.symmetry = None if sym in (None, "none") else sym
         self.eval_mcts_config = dict(arena.MCTS_EVAL, **(eval_mcts_config or {}))
         self.seed_base = int(seed_base)
         self.log = log
@@ -104,8 +110,10 @@ class Trainer:
     def execute_training_phase(self):
         res = None
         if self.rank == 0:
-            res = training_phase(self.model_manager, featurize(self.replay_buffer.records()),
-                                 self.self_play_config["epochs_per_iter"], self.training_config["batch_size"])
+            records = self.replay_buffer.records()
+            source = featurize(records) if self.symmetry is None else SymRecordSource(records, self.symmetry)
+            res = training_phase(self.model_manager, source, self.self_play_config["epochs_per_iter"],
+                                 self.training_config["batch_size"])
         if _dist():
             hd.broadcast_weights(self.model_manager.model, src=0)
         self.last_training = res

@@ -111,6 +111,48 @@ int hz_encode(hz_env *env, const int32_t *idx, int32_t m, float *board, float *g
 int hz_encode_states(const uint64_t *states, int64_t word_stride, int64_t item_stride, const int32_t *idx,
                      int32_t m, float *board, float *glob, void *stream);
 
+/* ---- board symmetries ---------------------------------------------------- */
+/* The 23-cell board has four automorphisms, and each is an automorphism of
+ * the whole game: placement rules and all five scorers see only stacks and
+ * adjacency; piles, hand, bag and the chance stream never see a coordinate.
+ * Group element g in 0..3 maps an axial coordinate (tensor position x = q + 3,
+ * y = r + 2):
+ *   g = 0  (q, r)          (x, y)
+ *   g = 1  (-q, -r)        (6 - x, 4 - y)          the half turn
+ *   g = 2  (q + r, -r)     (x + y - 2, 4 - y)      a reflection
+ *   g = 3  (-q - r, r)     (8 - x - y, y)          the other reflection
+ * a after b is a ^ b (Klein four-group): every element is its own inverse.
+ * With cells indexed as everywhere (c = index into sorted(VALID_HEXES)),
+ * perm[g][c] is the index of the image of cell c:
+ *   perm[1][c] = 22 - c
+ *   perm[2] = 4 1 5 9 0 2 6 10 14 3 7 11 15 19 8 12 16 20 22 13 17 21 18
+ *   perm[3][c] = 22 - perm[2][c]
+ * State:  for both players the stack code at cell c moves to cell perm[g][c]:
+ *         in each of the four plane words, bits 0..22 and bits 32..54 are
+ *         permuted and every other bit is kept; piles and misc are untouched.
+ * Action: a < 5 is unchanged; 5 + 23 t + c maps to 5 + 23 t + perm[g][c].
+ * Record (42 int64: six state words | 143 u16 slots | int8 z | int8 player):
+ *         the state words as above, the slots permuted by the action map
+ *         (visit counts and quantised policies alike), z and player kept.
+ * Both calls below are asynchronous on `stream`, allocate nothing and do not
+ * synchronize; records need only their natural 8-byte alignment. */
+
+/* out[j] = record rec[j] under symmetry sym[j] & 3 (sym NULL = identity, a plain copy).
+ * out may equal rec (each record is read whole before it is written). m = 0 is a no-op.
+ * <0: m < 0, or m > 0 with a NULL rec / out; nothing enqueued. */
+int hz_sym_records(const int64_t *rec, int64_t m, const uint8_t *sym, int64_t *out, void *stream);
+
+/* One training batch from packed records in one launch: item j is record idx[j]
+ * (idx NULL = j; idx[j] < 0 yields zeros everywhere) under symmetry sym[j] & 3
+ * (NULL = identity):
+ *   board[m][38][5][7], glob[m][42]  = hz_encode_states of the transformed state,
+ *   pi[m][143] = (float)((double)v[a] / (double)sum v), all zeros where the sum is 0
+ *                (the bits of hzamd.distributed.pi_of),
+ *   z[m]       = (float)(int8) z byte.
+ * <0: m < 0 or a NULL output; nothing enqueued. */
+int hz_train_batch(const int64_t *rec, const int32_t *idx, const uint8_t *sym, int32_t m,
+                   float *board, float *glob, float *pi, float *z, void *stream);
+
 /* Build-defined deterministic policy used by the env benchmark and the golden
  * traces: pick legal action k = ((splitmix64(seed, ply) >> 32) * L) >> 32 in
  * ascending action order.  Writes action[b] (-1 if no legal move). */
