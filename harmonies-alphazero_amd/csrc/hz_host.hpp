@@ -1,4 +1,5 @@
-// hz_host.hpp — the host layer the three .hip files share: no device code.
+// hz_host.hpp — the host layer every .hip unit of libhz shares (csrc/units.mk
+// names them): no device code.
 //
 //   env_int / env_pick / env_clamped / env_cuts(_n), Setting : the environment knobs
 //   DevBufsT<Dev>                                        : owner of device buffers

@@ -17,108 +17,27 @@
 //                            table is never cleared)
 // Arithmetic follows the reference's NumPy/Python types exactly (see select
 // and expand) so that visit counts are bit-identical to the CPU engine.
-#include <hip/hip_runtime.h>
-
-#include <cstdlib>
+// This unit holds the simulation (begin, select, gather, expand + backup) and
+// the handle's create, destroy and setters; hz_mcts.hpp says where the rest is.
+#include "hz_mcts.hpp"
 
 #include "../../include/hz_abi.h"
-#include "hz_device.hpp"
 #include "hz_encode.hpp"
-#include "hz_host.hpp"
 
 using namespace hz;
 using namespace hz_host;
+using namespace hz_tree;
 
 struct hz_env;  // defined in hz_env.hip; accessed through the ABI getters
 
-struct hz_mcts {
-  int32_t n, max_nodes, max_edges, hcap, max_depth;
-  int32_t exact_keys;
-  int32_t dedup_walk;    // hz_mcts_set_dedup_walk (tests): every sibling dedup takes the serial walk
-  int32_t gather_mode;   // hz_mcts_set_gather_encode: -1 process default (HZ_GATHER_ENCODE), 0 layered, 1 fused
-  hipStream_t stream;
-  uint64_t *node_state;  // [n][max_nodes][6]
-  uint64_t *node_key;    // [n][max_nodes][8] canonical key (a probe compares it whole: no key rebuilt)
-  int32_t *node_e0;      // [n][max_nodes]
-  int32_t *node_ne;      // [n][max_nodes]
-  int16_t *edge_action;  // [n][max_edges]
-  int32_t *edge_child;   // [n][max_edges]
-  int32_t *edge_n;       // [n][max_edges]
-  double *edge_w;        // [n][max_edges]
-  float *edge_p;         // [n][max_edges]
-  uint8_t *edge_player;  // [n][max_edges]
-  // [n][max_edges] the child node's e0 << 8 | terminal << 7 | ne as far as
-  // known: ne = 0 means "not expanded when last seen" (select then reads the
-  // node itself and repairs the hint), so the walk takes one memory round
-  // trip per level (edges + hints) instead of two (node, then its edges)
-  int32_t *edge_hint;
-  uint64_t *ht;          // [n][hcap]
-  int32_t *counts;       // [n][4]: nodes, edges, generation, overflow
-  int32_t *path;         // [n][max_depth]
-  int32_t *depth;        // [n]
-  int32_t *leaf;         // [n]  leaf node of the current simulation, -1 = inactive
-  int32_t *leaf_gidx;    // [n]  b*max_nodes + leaf for the encoder, -1 = no eval
-  int32_t *slot;         // [n]  row of board b in the gathered leaf batch, -1 = not evaluated
-  int32_t *gidx_c;       // [n]  leaf_gidx of the gathered rows, in board order
-  int64_t *eval_ctr;     // optional (hz_mcts_set_eval_counter): k_gather adds each simulation's row count
-  // rows of the policy / value tensors of the next expand call (hz_mcts_set_row_cap; 0: unchecked): a board whose
-  // row is at or past it reads neither, expands and backs up nothing and sets err[0]
-  int32_t row_cap;
-  int32_t *err;          // [1] device error word (hz_mcts_take_error): bit 0 = a row at or past row_cap
-  // per-board simulation budgets (hz_mcts_set_budget): budget == nullptr: no gate; else budget == budget_buf
-  int32_t *budget;       // [n] the gate's budgets (the handle's copy), or nullptr
-  int32_t *sims_done;    // [n] simulations select_board has given board b in this search (counted under the gate only)
-  int32_t *budget_buf;   // [n] owned; fixed address, so a captured simulation stays valid while its contents change
-  // per-board root noise (hz_mcts_set_root_noise_mask): nullptr: every board, else noise_mask == mask_buf
-  uint8_t *noise_mask;
-  uint8_t *mask_buf;     // [n] owned
-  // tree reuse (hz_mcts_advance; allocated by its first call, nullptr on a handle that never advanced)
-  uint8_t *carry;        // [n] board b's tree is the subtree hz_mcts_advance kept (consumed by the next begin)
-  int32_t *adv_remap;    // [n][max_nodes] advance's scratch: reach marks, then old node id -> new id (-1: dropped)
-  int32_t *adv_queue;    // [n][max_nodes] advance's scratch: the kept expanded nodes, in discovery order
-  // the Gumbel root (hz_mcts_set_gumbel; allocated by its first call): gumbel == nullptr: gate off, else == gumbel_buf
-  double *gumbel;        // [n][69] G by legal rank (the handle's copy), or nullptr
-  double *gumbel_buf;    // [n][69] owned; fixed address (a captured simulation stays valid while its contents change)
-  double *g_score;       // [n][69] G + log P by root edge index, written where node 0's edges are
-  float *root_value;     // [n] the network's value of node 0, written where node 0 is expanded
-  // [g_considered + 1][g_nroot] considered-visit table: owned, allocated once for the largest table the ABI
-  // admits (70 x 32767 int16, 4.6 MB), so its address is fixed for the handle's life like the others'
-  int16_t *g_table;
-  int32_t g_considered, g_nroot;
-  double g_c_visit, g_c_scale;
-};
-
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kMaxChildren = 69;  // measured max legal moves
-constexpr int kChildSlots = 128;  // two per lane (loop bound: lanes c and c + 64)
 constexpr int kChildLds = 72;     // LDS rows per child array: every access has c < nl <= kMaxChildren
 constexpr int kDedupSlots = 128;  // sibling-dedup table (load factor <= 69/128)
 
-__device__ __forceinline__ uint64_t ht_entry(int gen, int node) {
-  return ((uint64_t)(uint32_t)gen << 32) | (uint32_t)node;
-}
-
-__device__ __forceinline__ State load_node(const uint64_t *ns) {
-  State s;
-#pragma unroll
-  for (int k = 0; k < 4; k++) s.pl[k] = ns[k];
-  s.piles = ns[4];
-  s.misc = ns[5];
-  return s;
-}
-
-__device__ __forceinline__ void store_node(uint64_t *ns, const State &s) {
-#pragma unroll
-  for (int k = 0; k < 4; k++) ns[k] = s.pl[k];
-  ns[4] = s.piles;
-  ns[5] = s.misc;
-}
-
 // ------------------------------------------------------------------- begin
 // Fresh tree per move (MCTS.py:288-289): node 0 = the board's game state.
-__global__ void __launch_bounds__(kWave) k_begin(hz_mcts m, const uint64_t *__restrict__ game, int n_env,
+__global__ void __launch_bounds__(kWave) k_begin(hz_mcts_args m, const uint64_t *__restrict__ game, int n_env,
                                                  const uint8_t *__restrict__ active) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= m.n) return;
@@ -169,115 +88,10 @@ __global__ void __launch_bounds__(kWave) k_begin(hz_mcts m, const uint64_t *__re
 // transposition target expanded through another parent since) is checked
 // against the node and repaired; a terminal child (never expanded) needs no
 // check.
-constexpr int kHintNe = 127, kHintTerm = 128;
-// Wave reductions of the walk: within each row of 16 lanes by DPP moves (a
-// VALU operand modifier: quad_perm xor 1, xor 2, then row_ror 4, 8), across
-// the four rows by two ds_bpermute rounds (xor 16, 32): 2 LDS-crossbar
-// round trips per reduction instead of 6.  Every lane ends with the result.
-template <int Ctrl>
-__device__ __forceinline__ int dpp_mov(int v) {
-  return __builtin_amdgcn_update_dpp(0, v, Ctrl, 0xf, 0xf, false);
-}
-constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppRor4 = 0x124, kDppRor8 = 0x128;
-__device__ __forceinline__ int wave_sum_i(int v) {
-  v += dpp_mov<kDppXor1>(v);
-  v += dpp_mov<kDppXor2>(v);
-  v += dpp_mov<kDppRor4>(v);
-  v += dpp_mov<kDppRor8>(v);
-  v += __shfl_xor(v, 16);
-  v += __shfl_xor(v, 32);
-  return v;
-}
-// (value, index): the largest value, the smallest index among equal values
-// (MCTS.py:102-121's first strict '>' in insertion order); associative and
-// commutative, so the reduction order does not change the result
-__device__ __forceinline__ void argmax_take(double ob, int oi, double &best, int &bi) {
-  if (ob > best || (ob == best && oi < bi)) {
-    best = ob;
-    bi = oi;
-  }
-}
-template <int Ctrl>
-__device__ __forceinline__ void argmax_dpp(double &best, int &bi) {
-  const long long b = __double_as_longlong(best);
-  const int lo = dpp_mov<Ctrl>((int)b), hi = dpp_mov<Ctrl>((int)(b >> 32)), oi = dpp_mov<Ctrl>(bi);
-  argmax_take(__longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo)), oi, best,
-              bi);
-}
-__device__ __forceinline__ void wave_argmax(double &best, int &bi) {
-  argmax_dpp<kDppXor1>(best, bi);
-  argmax_dpp<kDppXor2>(best, bi);
-  argmax_dpp<kDppRor4>(best, bi);
-  argmax_dpp<kDppRor8>(best, bi);
-#pragma unroll
-  for (int o = 16; o < kWave; o <<= 1) argmax_take(__shfl_xor(best, o), __shfl_xor(bi, o), best, bi);
-}
-// edge_hint = first edge << 8 | terminal << 7 | edge count: the first edge
-// must fit in 24 bits, so hz_mcts_create refuses max_nodes >= kMaxNodesHint
-constexpr int32_t kMaxNodesHint = 1 << 24;
-__device__ __forceinline__ int32_t edge_hint_of(int e0, int ne, bool term) {
-  return (int32_t)((uint32_t)e0 << 8 | (term ? (uint32_t)kHintTerm : 0u) | (uint32_t)ne);
-}
-// ------------------------------------------------------------ the Gumbel root
-// The root rule of hz_mcts_set_gumbel (include/hz_abi.h states it; no
-// reference counterpart).  Lane l holds root edges l and l + 64.  The two
-// fp64 sums are the xor butterfly: the lane's partial is edge l's term plus
-// edge l + 64's (0.0 for an edge that is absent or unvisited), then
-// v = v + v[lane ^ off] for off = 1, 2, 4, 8, 16, 32; minima and maxima are
-// exact in any order.  These run once per simulation and board, under the
-// gate only: plain cross-lane moves, not the walk's DPP forms.
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) v = __dadd_rn(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ double wave_min_d(double v) {
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) v = fmin(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-// G + log P of one root edge: the one place the transcendental is taken (the
-// expansion of node 0 stores it in g_score; the select, the result and
-// hz_mcts_root_gumbel_scores read that array); -inf where P is 0
-__device__ __forceinline__ double gumbel_edge_score(double g, float p) { return __dadd_rn(g, log((double)p)); }
-constexpr double kGumbelFloor = -1e9;
-constexpr int32_t kGumbelTableMax = (kMaxChildren + 1) * 32767;  // entries of the largest table hz_mcts_set_gumbel admits
-// sigma of the lane's two edges from the root's statistics (ne edges, t = sum
-// N), the completed-Q mix v_mix and the largest N
-__device__ __forceinline__ void gumbel_sigma(const hz_mcts &m, int lane, int ne, int t, int n0, int n1, double w0,
-                                             double w1, float p0, float p1, double v_root, double &sg0, double &sg1,
-                                             double &v_mix, int &max_n) {
-  const bool in0 = lane < ne, in1 = lane + kWave < ne;
-  const bool vis0 = in0 && n0 > 0, vis1 = in1 && n1 > 0;
-  const double q0 = vis0 ? __ddiv_rn(w0, (double)n0) : 0.0, q1 = vis1 ? __ddiv_rn(w1, (double)n1) : 0.0;
-  const double sp = wave_sum_d(__dadd_rn(vis0 ? (double)p0 : 0.0, vis1 ? (double)p1 : 0.0));
-  const double spq =
-      wave_sum_d(__dadd_rn(vis0 ? __dmul_rn((double)p0, q0) : 0.0, vis1 ? __dmul_rn((double)p1, q1) : 0.0));
-  const double wq = sp > 0.0 ? __ddiv_rn(spq, sp) : 0.0;
-  v_mix = __ddiv_rn(__dadd_rn(v_root, __dmul_rn((double)t, wq)), (double)(t + 1));
-  max_n = wave_max_i(max(in0 ? n0 : 0, in1 ? n1 : 0));
-  const double c0 = vis0 ? q0 : v_mix, c1 = vis1 ? q1 : v_mix;  // completed Q
-  const double mn = wave_min_d(fmin(in0 ? c0 : INFINITY, in1 ? c1 : INFINITY));
-  const double mx = wave_max_d(fmax(in0 ? c0 : -INFINITY, in1 ? c1 : -INFINITY));
-  const double den = fmax(__dsub_rn(mx, mn), 1e-8);
-  const double scale = __dmul_rn(__dadd_rn(m.g_c_visit, (double)max_n), m.g_c_scale);
-  sg0 = in0 ? __dmul_rn(scale, __ddiv_rn(__dsub_rn(c0, mn), den)) : 0.0;
-  sg1 = in1 ? __dmul_rn(scale, __ddiv_rn(__dsub_rn(c1, mn), den)) : 0.0;
-}
 // The root's choice of one simulation: among the edges whose N is the table's
 // considered-visit count (every edge if none is), the first with the largest
 // max(-1e9, (G + log P) + sigma).  Leaves (best, bi) for wave_argmax.
-__device__ __forceinline__ void gumbel_root_pick(const hz_mcts &m, int lane, int ne, int t, int n0, int n1, double w0,
+__device__ __forceinline__ void gumbel_root_pick(const hz_mcts_args &m, int lane, int ne, int t, int n0, int n1, double w0,
                                                  double w1, float p0, float p1, double v_root, double gs0, double gs1,
                                                  double &best, int &bi) {
   double sg0, sg1, v_mix;
@@ -312,7 +126,7 @@ __device__ __forceinline__ void gumbel_root_pick(const hz_mcts &m, int lane, int
 // the root's choice is gumbel_root_pick's, every other level's is PUCT's.  A
 // handle with the gate off launches the instantiations without the branch.
 template <bool Fresh = false, bool Gum = false>
-__device__ __forceinline__ int select_board(const hz_mcts &m, int b, int lane, const uint8_t *__restrict__ active,
+__device__ __forceinline__ int select_board(const hz_mcts_args &m, int b, int lane, const uint8_t *__restrict__ active,
                                             float cpuct) {
   int32_t *cnt = m.counts + (size_t)b * 4;
   size_t nb = (size_t)b * m.max_nodes, eb = (size_t)b * m.max_edges;
@@ -437,7 +251,7 @@ __device__ __forceinline__ int select_board(const hz_mcts &m, int b, int lane, c
 }
 
 template <bool Gum>
-__global__ void __launch_bounds__(kWave) k_select(hz_mcts m, const uint8_t *__restrict__ active, float cpuct) {
+__global__ void __launch_bounds__(kWave) k_select(hz_mcts_args m, const uint8_t *__restrict__ active, float cpuct) {
   select_board<false, Gum>(m, blockIdx.x, threadIdx.x, active, cpuct);
 }
 
@@ -448,7 +262,7 @@ __global__ void __launch_bounds__(kWave) k_select(hz_mcts m, const uint8_t *__re
 // One workgroup; thread t owns boards [t*per, (t+1)*per) (contiguous, so the
 // exclusive scan of the per-thread counts keeps board order).
 constexpr int kGatherThreads = 1024;
-__global__ void __launch_bounds__(kGatherThreads) k_gather(hz_mcts m, int32_t *__restrict__ rows,
+__global__ void __launch_bounds__(kGatherThreads) k_gather(hz_mcts_args m, int32_t *__restrict__ rows,
                                                            int32_t *__restrict__ count) {
   __shared__ int32_t part[kGatherThreads];
   const int t = threadIdx.x;
@@ -496,7 +310,7 @@ __global__ void __launch_bounds__(kGatherThreads) k_gather(hz_mcts m, int32_t *_
 // (profiles/r04/tree/r4p_ge*): fewer workgroups scan the flags, the encoders keep 2048 waves
 constexpr int kGEWaves = 8, kGERows = 2 * kGEWaves, kGEThreads = kGEWaves * kWave, kGELoads = 16;
 constexpr int kBoardFloats = 38 * 35, kGlobFloats = 42;  // one encoded state (hz_encode.hpp)
-__global__ void __launch_bounds__(kGEThreads) k_gather_encode(hz_mcts m, int32_t *__restrict__ rows,
+__global__ void __launch_bounds__(kGEThreads) k_gather_encode(hz_mcts_args m, int32_t *__restrict__ rows,
                                                                int32_t *__restrict__ count,
                                                                float *__restrict__ board, float *__restrict__ glob) {
   __shared__ uint64_t smask[kGEWaves][76];
@@ -588,7 +402,7 @@ constexpr int kFusedMax = 32;
 constexpr int kFusedWaves = 16;
 static_assert(kFusedMax <= 2 * kFusedWaves && kFusedMax <= kWave, "one pair per wave, one gather wave");
 template <bool Gum>
-__global__ void __launch_bounds__(kFusedWaves * kWave) k_select_gather_encode(hz_mcts m,
+__global__ void __launch_bounds__(kFusedWaves * kWave) k_select_gather_encode(hz_mcts_args m,
                                                                            const uint8_t *__restrict__ active,
                                                                            float cpuct, int32_t *__restrict__ rows,
                                                                            int32_t *__restrict__ count,
@@ -827,7 +641,7 @@ static_assert(sizeof(uint64_t) * kChildLds * 6 >= sizeof(uint32_t) * kMT, "the s
 // Gum (a handle whose Gumbel gate is on): node 0's expansion also stores the
 // network's value of the root and each root edge's G + log P.
 template <bool Gum>
-__device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts &m, uint32_t *__restrict__ mtw,
+__device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts_args &m, uint32_t *__restrict__ mtw,
                                                     int32_t *__restrict__ mtcur, int32_t *__restrict__ wtag,
                                                     const float *__restrict__ policy,
                                                     const float *__restrict__ value,
@@ -1276,7 +1090,7 @@ __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts 
 // soon as its walk is done, instead of the workgroup's one add after a
 // barrier that waits for the workgroup's slowest wave (A/B: HZ_SLOT_WAVE)
 template <int Waves, bool Sel, bool Gum, bool Gather = false, int BPW = 1, bool WaveSlot = false>  // Waves: minimum waves per SIMD the register allocation must allow (3: none forced)
-__global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_eu(Waves, 8))) k_expand_backup(hz_mcts m, uint32_t *__restrict__ mtw,
+__global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_eu(Waves, 8))) k_expand_backup(hz_mcts_args m, uint32_t *__restrict__ mtw,
                                                          int32_t *__restrict__ mtcur,
                                                          int32_t *__restrict__ wtag,
                                                          const float *__restrict__ policy,
@@ -1373,707 +1187,6 @@ __global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_e
   }
 }
 
-// ------------------------------------------------------------- root noise
-// The self-play root noise of get_best_action_and_pi (MCTS.py:314-316:
-// np.random.dirichlet([alpha] * L) over the L legal moves) and the tau = 1
-// uniform of its move choice (MCTS.py:411, np.random.choice), drawn from a
-// counter-based generator keyed by (seed, global board id, move) instead of
-// the process-global np.random: every board's draws are the same whatever
-// the batch it sits in or the number of GPUs.  One wave per
-// board; lane c draws child c's Gamma(alpha) (and c + 64's): Marsaglia-Tsang
-// for alpha + 1 with a standard normal from Box-Muller, times U^(1/alpha)
-// for alpha < 1.  The live children's sum is a fixed butterfly over the
-// wave, so the result does not depend on anything but the key.
-struct NoiseStream {
-  uint64_t key, ctr;
-  __device__ double uniform() {  // (0, 1], 53 bits
-    uint64_t z = mix64(key + 0x9E3779B97F4A7C15ULL * ++ctr);
-    return ((double)(z >> 11) + 1.0) * 0x1.0p-53;
-  }
-};
-
-__device__ double gamma_draw(NoiseStream &s, double alpha) {
-  const double a = alpha < 1.0 ? alpha + 1.0 : alpha;
-  const double d = a - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
-  double g;
-  for (;;) {
-    double x, v;
-    do {
-      double u1 = s.uniform(), u2 = s.uniform();
-      x = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-      v = 1.0 + c * x;
-    } while (v <= 0.0);
-    v = v * v * v;
-    double u = s.uniform();
-    if (u < 1.0 - 0.0331 * x * x * x * x || log(u) < 0.5 * x * x + d * (1.0 - v + log(v))) {
-      g = d * v;
-      break;
-    }
-  }
-  if (alpha < 1.0) g *= pow(s.uniform(), 1.0 / alpha);
-  return g;
-}
-
-__global__ void __launch_bounds__(kWave) k_root_noise(const int32_t *__restrict__ count, int n, uint64_t seed,
-                                                      uint64_t board_base, uint64_t move, double alpha,
-                                                      double *__restrict__ noise, double *__restrict__ u) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const uint64_t key = mix64(mix64(mix64(seed ^ 0x6A09E667F3BCC908ULL) ^ (board_base + (uint64_t)b)) ^ move);
-  const int nl = count ? min(max(count[b], 0), kMaxChildren) : 0;
-  double g[2];
-  double sum = 0.0;
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const int c = lane + kWave * k;
-    NoiseStream s{mix64(key ^ (0xD1B54A32D192ED03ULL * (uint64_t)(c + 1))), 0};
-    g[k] = c < nl ? gamma_draw(s, alpha) : 0.0;
-    sum += g[k];
-  }
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) sum += __shfl_xor(sum, off);
-  const double inv = sum > 0.0 ? 1.0 / sum : 0.0;
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const int c = lane + kWave * k;
-    if (c < kMaxChildren) noise[(size_t)b * kMaxChildren + c] = g[k] * inv;
-  }
-  if (lane == 0 && u) {
-    NoiseStream s{mix64(key ^ 0x5851F42D4C957F2DULL), 0};
-    u[b] = s.uniform() - 0x1.0p-53;  // [0, 1)
-  }
-}
-
-// One uniform in (0, 1] per board (hz_playout_coin: the coin of playout-cap
-// randomization, no reference counterpart), from k_root_noise's generator and
-// board key under a salt of its own: neither the noise nor the move-choice
-// uniform moves by a bit.
-__global__ void __launch_bounds__(256) k_playout_coin(int n, uint64_t seed, uint64_t board_base, uint64_t move,
-                                                      double *__restrict__ coin) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= n) return;
-  const uint64_t key = mix64(mix64(mix64(seed ^ 0x6A09E667F3BCC908ULL) ^ (board_base + (uint64_t)b)) ^ move);
-  NoiseStream s{mix64(key ^ 0x94D049BB133111EBULL), 0};
-  coin[b] = s.uniform();
-}
-
-// One standard Gumbel per board and legal rank (hz_root_gumbel; no reference
-// counterpart): g = -log(-log u), u = (k + 1/2) 2^-52 for a 52-bit k, so u
-// lies strictly inside (0, 1) and g is finite; from k_root_noise's generator
-// and board key under a salt of its own (the noise, the move-choice uniform
-// and the coin keep their bits).
-__global__ void __launch_bounds__(kWave) k_root_gumbel(int n, uint64_t seed, uint64_t board_base, uint64_t move,
-                                                       double *__restrict__ out) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  if (b >= n) return;
-  const uint64_t key = mix64(mix64(mix64(seed ^ 0x6A09E667F3BCC908ULL) ^ (board_base + (uint64_t)b)) ^ move);
-  for (int c = lane; c < kMaxChildren; c += kWave) {
-    const uint64_t z = mix64(mix64(key ^ (0xA0761D6478BD642FULL * (uint64_t)(c + 1))) + 0x9E3779B97F4A7C15ULL);
-    const double u = ((double)(z >> 12) + 0.5) * 0x1.0p-52;
-    out[(size_t)b * kMaxChildren + c] = -log(-log(u));
-  }
-}
-
-// root visit counts by action (MCTS.py:355-376)
-__global__ void __launch_bounds__(kWave) k_result(hz_mcts m, int32_t *__restrict__ visits) {
-  int b = blockIdx.x;
-  int lane = threadIdx.x;
-  int32_t *out = visits + (size_t)b * kActions;
-  for (int a = lane; a < kActions; a += kWave) out[a] = 0;
-  __syncthreads();
-  if (m.counts[(size_t)b * 4] == 0) return;
-  size_t nb = (size_t)b * m.max_nodes, eb = (size_t)b * m.max_edges;
-  int ne = m.node_ne[nb], e0 = m.node_e0[nb];
-  for (int i = lane; i < ne; i += kWave) out[m.edge_action[eb + e0 + i]] = m.edge_n[eb + e0 + i];
-}
-
-// ------------------------------------------------------------ search report
-// Read-only views of the tree for the caller (no reference kernel: the
-// reference keeps Python objects, MCTS.get_root_edges MCTS.py:268-269).  Both
-// kernels trust nothing they read from the tree: a node's edge range is used
-// only when it lies inside the board's edge count, a child link only when it
-// is below the board's node count; anything else reads as "no edges".
-// A node's edge range [e0, e0 + ne) when it lies within the board's n_edges
-// edges (two per lane at most), else ne = 0.
-__device__ __forceinline__ int checked_edges(const hz_mcts &m, size_t nb, int node, int n_edges, int &e0) {
-  const int ne = m.node_ne[nb + node];
-  e0 = m.node_e0[nb + node];
-  return ne > 0 && ne <= kChildSlots && e0 >= 0 && e0 <= n_edges - ne ? ne : 0;
-}
-__device__ __forceinline__ bool checked_counts(const hz_mcts &m, int n_nodes, int n_edges) {
-  return n_nodes > 0 && n_nodes <= m.max_nodes && n_edges >= 0 && n_edges <= m.max_edges;
-}
-
-// The root's edges by action id (MCTS.py:355-376 reads N from them; Edge.stats
-// MCTS.py:34-39): N, W, Q = W / N as back_fill leaves it (MCTS.py:254; 0 while
-// N == 0), P, the child node; value = sum W / sum N, both sums in edge order.
-// One wave per board: the edges' lanes note their action's slot in LDS, then
-// lanes are actions and every output row is written once, whole.
-__global__ void __launch_bounds__(kWave) k_root_edges(hz_mcts m, int32_t *__restrict__ n_out, double *__restrict__ w_out,
-                                                      double *__restrict__ q_out, float *__restrict__ p_out,
-                                                      int32_t *__restrict__ child_out,
-                                                      double *__restrict__ value_out) {
-  __shared__ int16_t slot[kActions];
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const int32_t *cnt = m.counts + (size_t)b * 4;
-  const size_t nb = (size_t)b * m.max_nodes, eb = (size_t)b * m.max_edges;
-  const int n_nodes = cnt[0], n_edges = cnt[1];
-  int e0 = 0;
-  const int ne = checked_counts(m, n_nodes, n_edges) ? checked_edges(m, nb, 0, n_edges, e0) : 0;
-  for (int a = lane; a < kActions; a += kWave) slot[a] = -1;
-  __syncthreads();
-  int n0 = 0, n1 = 0;
-  double w0 = 0.0, w1 = 0.0;
-  if (lane < ne) {
-    const size_t e = eb + e0 + lane;
-    n0 = m.edge_n[e];
-    w0 = m.edge_w[e];
-    const int a = m.edge_action[e];
-    if (a >= 0 && a < kActions) slot[a] = (int16_t)lane;
-  }
-  if (lane + kWave < ne) {
-    const size_t e = eb + e0 + lane + kWave;
-    n1 = m.edge_n[e];
-    w1 = m.edge_w[e];
-    const int a = m.edge_action[e];
-    if (a >= 0 && a < kActions) slot[a] = (int16_t)(lane + kWave);
-  }
-  __syncthreads();
-  for (int a = lane; a < kActions; a += kWave) {
-    const int i = slot[a];
-    int n = 0, child = -1;
-    double w = 0.0, q = 0.0;
-    float p = 0.f;
-    if (i >= 0) {
-      const size_t e = eb + e0 + i;
-      n = m.edge_n[e];
-      w = m.edge_w[e];
-      p = m.edge_p[e];
-      child = m.edge_child[e];
-      q = n ? __ddiv_rn(w, (double)n) : 0.0;
-    }
-    const size_t o = (size_t)b * kActions + a;
-    n_out[o] = n;
-    w_out[o] = w;
-    q_out[o] = q;
-    p_out[o] = p;
-    if (child_out) child_out[o] = child;
-  }
-  if (value_out) {
-    const int sn = wave_sum_i(n0 + n1);
-    double sw = 0.0;
-    for (int i = 0; i < ne; i++) sw = __dadd_rn(sw, __shfl(i < kWave ? w0 : w1, i & (kWave - 1)));
-    if (lane == 0) value_out[b] = sn ? __ddiv_rn(sw, (double)sn) : 0.0;
-  }
-}
-
-// The line the search expects: from the root, the first edge with the most
-// visits (the greedy choice of MCTS.py:418-423 applied at every level), until
-// a node without edges, an edge without visits or max_len moves.  One wave
-// per board, two edges per lane, one (N, index) reduction per level.
-__global__ void __launch_bounds__(kWave) k_pv(hz_mcts m, int max_len, int16_t *__restrict__ action,
-                                              int32_t *__restrict__ visits, double *__restrict__ q,
-                                              uint8_t *__restrict__ player, int32_t *__restrict__ len) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const int32_t *cnt = m.counts + (size_t)b * 4;
-  const size_t nb = (size_t)b * m.max_nodes, eb = (size_t)b * m.max_edges, ob = (size_t)b * max_len;
-  const int n_nodes = cnt[0], n_edges = cnt[1];
-  int node = 0, d = 0;
-  if (checked_counts(m, n_nodes, n_edges)) {
-    while (d < max_len && node >= 0 && node < n_nodes) {
-      int e0 = 0;
-      const int ne = checked_edges(m, nb, node, n_edges, e0);
-      if (ne == 0) break;
-      double best = -INFINITY;  // a visit count as a double (exact)
-      int bi = 0x7fffffff;
-      if (lane < ne) {
-        best = (double)m.edge_n[eb + e0 + lane];
-        bi = lane;
-      }
-      if (lane + kWave < ne) {
-        const double v = (double)m.edge_n[eb + e0 + lane + kWave];
-        if (v > best) { best = v; bi = lane + kWave; }
-      }
-      wave_argmax(best, bi);
-      const int nsel = (int)best;
-      if (nsel <= 0) break;
-      const size_t e = eb + e0 + bi;
-      if (lane == 0) {
-        action[ob + d] = m.edge_action[e];
-        visits[ob + d] = nsel;
-        q[ob + d] = __ddiv_rn(m.edge_w[e], (double)nsel);
-        player[ob + d] = m.edge_player[e];
-      }
-      node = m.edge_child[e];
-      d++;
-    }
-  }
-  for (int i = d + lane; i < max_len; i += kWave) {
-    action[ob + i] = -1;
-    visits[ob + i] = 0;
-    q[ob + i] = 0.0;
-    player[ob + i] = 0;
-  }
-  if (lane == 0) len[b] = d;
-}
-
-// The root's edges for the two Gumbel reports: at most kMaxChildren of them
-// (g_score has that many slots per board), inside the board's counts, on a
-// board the search began; else none.
-__device__ __forceinline__ int gumbel_root_edges(const hz_mcts &m, int b, int &e0) {
-  const int32_t *cnt = m.counts + (size_t)b * 4;
-  const int n_nodes = cnt[0], n_edges = cnt[1];
-  e0 = 0;
-  const int ne = checked_counts(m, n_nodes, n_edges) ? checked_edges(m, (size_t)b * m.max_nodes, 0, n_edges, e0) : 0;
-  return ne <= kMaxChildren ? ne : 0;
-}
-
-// hz_mcts_root_gumbel_scores: G + log P by root edge index (0.0 past the root's edges)
-__global__ void __launch_bounds__(kWave) k_gumbel_scores(hz_mcts m, double *__restrict__ out) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  int e0;
-  const int ne = gumbel_root_edges(m, b, e0);
-  for (int i = lane; i < kMaxChildren; i += kWave)
-    out[(size_t)b * kMaxChildren + i] = i < ne ? m.g_score[(size_t)b * kMaxChildren + i] : 0.0;
-}
-
-// hz_mcts_gumbel_result: after the search, the move (the first edge with the
-// largest score among the most visited), the improved policy softmax(log P +
-// sigma) over the root's edges by action id (the maximum subtracted first;
-// should every prior be 0, the softmax of sigma alone) and v_mix.  A root
-// without edges: action -1, a zero row, value 0.
-__global__ void __launch_bounds__(kWave) k_gumbel_result(hz_mcts m, int16_t *__restrict__ action,
-                                                         float *__restrict__ pi, double *__restrict__ value) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  float *row = pi + (size_t)b * kActions;
-  for (int a = lane; a < kActions; a += kWave) row[a] = 0.f;
-  __syncthreads();  // the zeros before the edges' entries (one wave: ordering only)
-  int e0;
-  const int ne = gumbel_root_edges(m, b, e0);
-  if (ne == 0) {
-    if (lane == 0) {
-      action[b] = -1;
-      value[b] = 0.0;
-    }
-    return;
-  }
-  const size_t eb = (size_t)b * m.max_edges + e0, gb = (size_t)b * kMaxChildren;
-  const bool in0 = lane < ne, in1 = lane + kWave < ne;
-  int n0 = 0, n1 = 0, a0 = -1, a1 = -1;
-  double w0 = 0.0, w1 = 0.0, gs0 = 0.0, gs1 = 0.0;
-  float p0 = 0.f, p1 = 0.f;
-  if (in0) {
-    n0 = m.edge_n[eb + lane];
-    w0 = m.edge_w[eb + lane];
-    p0 = m.edge_p[eb + lane];
-    a0 = m.edge_action[eb + lane];
-    gs0 = m.g_score[gb + lane];
-  }
-  if (in1) {
-    n1 = m.edge_n[eb + lane + kWave];
-    w1 = m.edge_w[eb + lane + kWave];
-    p1 = m.edge_p[eb + lane + kWave];
-    a1 = m.edge_action[eb + lane + kWave];
-    gs1 = m.g_score[gb + lane + kWave];
-  }
-  const int t = wave_sum_i(n0 + n1);
-  double sg0, sg1, v_mix;
-  int max_n;
-  gumbel_sigma(m, lane, ne, t, n0, n1, w0, w1, p0, p1, (double)m.root_value[b], sg0, sg1, v_mix, max_n);
-  double best = -INFINITY;
-  int bi = 0x7fffffff;
-  if (in0 && n0 == max_n) {
-    best = fmax(kGumbelFloor, __dadd_rn(gs0, sg0));
-    bi = lane;
-  }
-  if (in1 && n1 == max_n) {
-    const double v = fmax(kGumbelFloor, __dadd_rn(gs1, sg1));
-    if (v > best) { best = v; bi = lane + kWave; }
-  }
-  wave_argmax(best, bi);
-  const int act = __shfl(bi < kWave ? a0 : a1, bi & (kWave - 1));
-  // the improved policy
-  double l0 = in0 ? __dadd_rn(log((double)p0), sg0) : -INFINITY, l1 = in1 ? __dadd_rn(log((double)p1), sg1) : -INFINITY;
-  double mx = wave_max_d(fmax(l0, l1));
-  if (mx == -INFINITY) {
-    l0 = in0 ? sg0 : -INFINITY;
-    l1 = in1 ? sg1 : -INFINITY;
-    mx = wave_max_d(fmax(l0, l1));
-  }
-  const double x0 = in0 ? exp(__dsub_rn(l0, mx)) : 0.0, x1 = in1 ? exp(__dsub_rn(l1, mx)) : 0.0;
-  const double sum = wave_sum_d(__dadd_rn(x0, x1));
-  if (in0 && a0 >= 0 && a0 < kActions) row[a0] = (float)__ddiv_rn(x0, sum);
-  if (in1 && a1 >= 0 && a1 < kActions) row[a1] = (float)__ddiv_rn(x1, sum);
-  if (lane == 0) {
-    action[b] = (int16_t)act;
-    value[b] = v_mix;
-  }
-}
-
-// -------------------------------------------------------------- tree reuse
-// hz_mcts_advance / hz_mcts_begin_carried (no reference counterpart: MCTS.py:288
-// builds a fresh Node per call; the rule is stated in include/hz_abi.h).  Both
-// run between searches, one wave per board, and trust nothing they read from
-// the tree: edge ranges and child links are checked against the board's counts
-// before use, so every index stays inside the board's slices.
-// The wave reads words other lanes of it wrote earlier in the launch.  What
-// that rests on: (a) wave_mem_sync() between the phases is a compiler-level
-// ordering (no load or store moves across it) and a wave barrier; it is not a
-// wait for the stores to complete; (b) every such read-after-write is by the
-// same wave, whose requests to one address reach memory in issue order;
-// (c) the reads are ld_l2 loads, which go past the CU's L1, so no stale line
-// is hit.  A plain load of a word written earlier in the launch must not be
-// put behind one of these syncs.  Loads-before-stores within a chunk (a
-// lane's destination may be another lane's source) holds by data dependence:
-// the stores' values come from the chunk's load instructions, which the wave
-// waits for as a whole.
-template <class T>
-__device__ __forceinline__ T ld_l2(const T *p) {
-  return __hip_atomic_load(const_cast<T *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void wave_mem_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-__device__ __forceinline__ bool state_eq(const uint64_t *ns, const State &s) {
-  return ns[0] == s.pl[0] && ns[1] == s.pl[1] && ns[2] == s.pl[2] && ns[3] == s.pl[3] && ns[4] == s.piles &&
-         ns[5] == s.misc;
-}
-
-// After hz_step applied action[b]: the tree becomes the sub-DAG reachable
-// from the played child c (carried), or nothing (dropped).  Steps, each over
-// the board's old pools with the wave's lanes as nodes or edges:
-//   1. the carry conditions that need no traversal (wave-uniform);
-//   2. reach marks from c: the kept expanded nodes form a queue, each node's
-//      edges are the lanes; a child is claimed once (atomic exchange on its
-//      mark), kept edges are flagged in edge_hint (rebuilt in step 7);
-//   3. headroom; then new node ids: c -> 0, the others 1.. in ascending old id;
-//   4. edges packed in pool order, in place, ascending (destination <= source;
-//      a chunk's loads complete before its stores), children renumbered; the
-//      old position keeps the edge's new index (a kept node's new e0);
-//   5. nodes moved in place the same way, c first;
-//   6. the generation bumped and every kept node entered into the hash table;
-//   7. hints rebuilt from the moved nodes; counts, info and the carry flag.
-__global__ void __launch_bounds__(kWave) k_advance(hz_mcts m, const uint64_t *__restrict__ game, int n_env,
-                                                   const int16_t *__restrict__ action,
-                                                   const uint8_t *__restrict__ active, int headroom,
-                                                   int32_t *__restrict__ info) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  int32_t *cnt = m.counts + (size_t)b * 4;
-  const size_t nb = (size_t)b * m.max_nodes, eb = (size_t)b * m.max_edges;
-  const int nn = cnt[0], nE = cnt[1];
-  const int a = action[b];
-  const uint64_t below = (1ull << lane) - 1;
-  int32_t *mark = m.adv_remap + nb, *queue = m.adv_queue + nb;
-  int32_t *hint = m.edge_hint + eb;
-  bool ok = (!active || active[b]) && a >= 0 && a < kActions && checked_counts(m, nn, nE);
-  int c = -1;
-  if (ok) {  // the root's edge for the action, its child
-    int e0 = 0;
-    const int ne = checked_edges(m, nb, 0, nE, e0);
-    const bool hit0 = lane < ne && m.edge_action[eb + e0 + lane] == a;
-    const bool hit1 = lane + kWave < ne && m.edge_action[eb + e0 + lane + kWave] == a;
-    const uint64_t b0 = __ballot(hit0), b1 = __ballot(hit1);
-    const int ei = b0 ? __builtin_ctzll(b0) : b1 ? kWave + __builtin_ctzll(b1) : -1;
-    if (ei >= 0) c = m.edge_child[eb + e0 + ei];
-    ok = ei >= 0 && c > 0 && c < nn;
-  }
-  if (ok) {  // not terminal, and the state the env now holds
-    const uint64_t *cs = m.node_state + (nb + c) * 6;
-    ok = m.node_ne[nb + c] >= 0 && !game_done(cs[5]) && state_eq(cs, load_state(game, n_env, b));
-  }
-  int kn = 0, ke = 0;
-  if (ok) {
-    for (int i = lane; i < nn; i += kWave) mark[i] = 0;
-    for (int e = lane; e < nE; e += kWave) hint[e] = 0;
-    int ce0 = 0;
-    const int cne = checked_edges(m, nb, c, nE, ce0);
-    wave_mem_sync();
-    if (lane == 0) {
-      mark[c] = 1;
-      queue[0] = c;
-    }
-    wave_mem_sync();
-    kn = 1;
-    ke = cne;
-    int qh = 0, qt = cne > 0 ? 1 : 0;  // (every claimed node enters the queue at most once: qt <= nn)
-    while (qh < qt) {
-      const int batch = qt - qh < kWave ? qt - qh : kWave;
-      int ve0 = 0, vne = 0;
-      if (lane < batch) vne = checked_edges(m, nb, ld_l2(&queue[qh + lane]), nE, ve0);
-      for (int j = 0; j < batch; j++) {
-        const int e0 = __shfl(ve0, j), ne = __shfl(vne, j);
-#pragma unroll
-        for (int r = 0; r < 2; r++) {
-          const int k = lane + r * kWave;
-          bool fresh = false;
-          int ch = 0, chne = 0, che0 = 0;
-          if (k < ne) {
-            hint[e0 + k] = 1;
-            ch = m.edge_child[eb + e0 + k];
-            if (ch > 0 && ch < nn) fresh = atomicExch(&mark[ch], 1) == 0;
-          }
-          if (fresh) chne = checked_edges(m, nb, ch, nE, che0);
-          const bool grow = fresh && chne > 0;
-          const uint64_t fb = __ballot(fresh), gb = __ballot(grow);
-          if (grow) queue[qt + __popcll(gb & below)] = ch;
-          kn += __popcll(fb);
-          qt += __popcll(gb);
-          ke += wave_sum_i(grow ? chne : 0);
-        }
-      }
-      qh += batch;
-      wave_mem_sync();  // the queue's new entries, before the next batch reads them
-    }
-    ok = (long long)kn + headroom <= m.max_nodes && (long long)ke + headroom <= m.max_edges;
-  }
-  if (!ok) {  // dropped (a tree marked above is gone with its counts)
-    if (lane == 0) {
-      m.carry[b] = 0;
-      cnt[0] = 0;
-      cnt[1] = 0;
-      info[(size_t)b * 3] = 0;
-      info[(size_t)b * 3 + 1] = 0;
-      info[(size_t)b * 3 + 2] = 0;
-    }
-    return;
-  }
-  {  // 3. new ids
-    int base = 1;
-    for (int i0 = 0; i0 < nn; i0 += kWave) {
-      const int i = i0 + lane;
-      const bool kept = i < nn && i != c && ld_l2(&mark[i]) != 0;
-      const uint64_t kb = __ballot(kept);
-      if (i < nn) mark[i] = kept ? base + __popcll(kb & below) : (i == c ? 0 : -1);
-      base += __popcll(kb);
-    }
-  }
-  wave_mem_sync();
-  {  // 4. edges
-    int ebase = 0;
-    for (int c0 = 0; c0 < nE; c0 += kWave) {
-      const int e = c0 + lane;
-      const bool kept = e < nE && ld_l2(&hint[e]) == 1;
-      const uint64_t kb = __ballot(kept);
-      const int dst = ebase + __popcll(kb & below);  // <= e
-      int16_t ea = 0;
-      int ech = 0, en = 0;
-      double ew = 0.0;
-      float ep = 0.f;
-      uint8_t epl = 0;
-      if (kept) {
-        ea = m.edge_action[eb + e];
-        ech = m.edge_child[eb + e];
-        en = m.edge_n[eb + e];
-        ew = m.edge_w[eb + e];
-        ep = m.edge_p[eb + e];
-        epl = m.edge_player[eb + e];
-        ech = ech > 0 && ech < nn ? ld_l2(&mark[ech]) : 0;
-      }
-      wave_mem_sync();  // the chunk's loads before its stores (a lane's destination may be another's source)
-      if (kept) {
-        m.edge_action[eb + dst] = ea;
-        m.edge_child[eb + dst] = ech;
-        m.edge_n[eb + dst] = en;
-        m.edge_w[eb + dst] = ew;
-        m.edge_p[eb + dst] = ep;
-        m.edge_player[eb + dst] = epl;
-        hint[e] = dst;
-      }
-      ebase += __popcll(kb);
-    }
-  }
-  wave_mem_sync();
-  // a kept expanded node's new first edge: its old first edge's new index
-  auto new_e0 = [&](int ne, int e0) { return ne > 0 && e0 >= 0 && e0 < nE ? ld_l2(&hint[e0]) : 0; };
-  {  // 5. nodes: c first (slot 0 held the old root, which no kept node is)
-    uint64_t wv = 0;
-    if (lane < 6) wv = m.node_state[(nb + c) * 6 + lane];
-    else if (lane < 14) wv = m.node_key[(nb + c) * 8 + lane - 6];
-    const int cne = m.node_ne[nb + c], ce0 = new_e0(cne, m.node_e0[nb + c]);
-    wave_mem_sync();
-    if (lane < 6) m.node_state[nb * 6 + lane] = wv;
-    else if (lane < 14) m.node_key[nb * 8 + lane - 6] = wv;
-    if (lane == 0) {
-      m.node_ne[nb] = cne;
-      m.node_e0[nb] = ce0;
-    }
-    wave_mem_sync();
-    for (int i0 = 0; i0 < nn; i0 += kWave) {
-      const int i = i0 + lane;
-      const int dst = i < nn ? ld_l2(&mark[i]) : -1;  // 1 <= dst <= i for a kept node
-      uint64_t st[6], ky[8];
-      int ne = 0, e0 = 0;
-      if (dst > 0) {
-#pragma unroll
-        for (int w = 0; w < 6; w++) st[w] = ld_l2(&m.node_state[(nb + i) * 6 + w]);
-#pragma unroll
-        for (int w = 0; w < 8; w++) ky[w] = ld_l2(&m.node_key[(nb + i) * 8 + w]);
-        ne = ld_l2(&m.node_ne[nb + i]);
-        e0 = new_e0(ne, ld_l2(&m.node_e0[nb + i]));
-      }
-      wave_mem_sync();
-      if (dst > 0) {
-#pragma unroll
-        for (int w = 0; w < 6; w++) m.node_state[(nb + dst) * 6 + w] = st[w];
-#pragma unroll
-        for (int w = 0; w < 8; w++) m.node_key[(nb + dst) * 8 + w] = ky[w];
-        m.node_ne[nb + dst] = ne;
-        m.node_e0[nb + dst] = e0;
-      }
-    }
-  }
-  wave_mem_sync();
-  const int gen = cnt[2] + 1;
-  {  // 6. the hash table of the new generation (hcap >= 2 max_nodes: a free slot is always found)
-    uint64_t *ht = m.ht + (size_t)b * m.hcap;
-    const uint64_t hmask = (uint64_t)(m.hcap - 1);
-    for (int i = lane; i < kn; i += kWave) {
-      CKey k;
-#pragma unroll
-      for (int w = 0; w < 8; w++) k.w[w] = ld_l2(&m.node_key[(nb + i) * 8 + w]);
-      uint64_t slot = key_hash(k) & hmask;
-      unsigned long long old = ld_l2(&ht[slot]);
-      for (;;) {
-        while ((int)(old >> 32) == gen) {
-          slot = (slot + 1) & hmask;
-          old = ld_l2(&ht[slot]);
-        }
-        const unsigned long long prev =
-            atomicCAS((unsigned long long *)&ht[slot], old, (unsigned long long)ht_entry(gen, i));
-        if (prev == old) break;
-        old = prev;
-      }
-    }
-  }
-  // 7. hints from the moved nodes, the new root's visits
-  for (int e = lane; e < ke; e += kWave) {
-    const int ch = ld_l2(&m.edge_child[eb + e]);
-    int cne = 0, ce0 = 0;
-    if (ch >= 0 && ch < kn) {
-      cne = ld_l2(&m.node_ne[nb + ch]);
-      ce0 = ld_l2(&m.node_e0[nb + ch]);
-    }
-    hint[e] = edge_hint_of(cne > 0 ? ce0 : 0, cne > 0 ? cne : 0, cne < 0);
-  }
-  int rn = 0;
-  {
-    const int rne = ld_l2(&m.node_ne[nb]), re0 = ld_l2(&m.node_e0[nb]);
-    if (rne > 0 && rne <= kChildSlots && re0 >= 0 && re0 <= ke - rne)
-      for (int k = lane; k < rne; k += kWave) rn += ld_l2(&m.edge_n[eb + re0 + k]);
-    rn = wave_sum_i(rn);
-  }
-  if (lane == 0) {
-    cnt[0] = kn;
-    cnt[1] = ke;
-    cnt[2] = gen;
-    cnt[3] = 0;
-    m.carry[b] = 1;
-    info[(size_t)b * 3] = kn;
-    info[(size_t)b * 3 + 1] = ke;
-    info[(size_t)b * 3 + 2] = rn;
-  }
-}
-
-// hz_mcts_begin for a handle that advanced: a board whose carry flag is set
-// and whose node 0 still is the env's state keeps its tree (limit flag and
-// simulation count cleared; a noisy board's expanded root gets the root mix,
-// with the expansion's arithmetic); every other active board starts as k_begin
-// starts it.  The flag is consumed.  One wave per board; lanes are root edges.
-__global__ void __launch_bounds__(kWave) k_begin_carried(hz_mcts m, const uint64_t *__restrict__ game, int n_env,
-                                                         const uint8_t *__restrict__ active,
-                                                         const double *__restrict__ noise, double eps,
-                                                         float one_minus_eps, int testing) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  int32_t *cnt = m.counts + (size_t)b * 4;
-  const size_t nb = (size_t)b * m.max_nodes, eb = (size_t)b * m.max_edges;
-  const bool act = !active || active[b];
-  const bool flagged = m.carry[b] != 0;
-  const int nn = cnt[0], nE = cnt[1];
-  wave_mem_sync();  // every lane has read the flag
-  if (lane == 0) {
-    m.sims_done[b] = 0;
-    m.carry[b] = 0;
-  }
-  if (!act) {
-    if (lane == 0) {
-      m.leaf[b] = -1;
-      m.leaf_gidx[b] = -1;
-      cnt[0] = 0;
-      cnt[1] = 0;
-    }
-    return;
-  }
-  const State s = load_state(game, n_env, b);
-  uint64_t mk[3];
-  const int nl = legal_mask(s, mk);
-  if (m.budget && !game_done(s.misc) && nl == 0 && lane == 0) m.budget[b] = 0;  // a stuck root (k_begin)
-  const bool keep = flagged && checked_counts(m, nn, nE) && state_eq(m.node_state + nb * 6, s);
-  if (!keep) {
-    if (lane == 0) {  // k_begin's fresh tree
-      store_node(m.node_state + nb * 6, s);
-      const CKey key = canon_key(s, !m.exact_keys);
-      const uint64_t h = key_hash(key);
-#pragma unroll
-      for (int w = 0; w < 8; w++) m.node_key[nb * 8 + w] = key.w[w];
-      m.node_e0[nb] = 0;
-      m.node_ne[nb] = 0;
-      const int gen = cnt[2] + 1;
-      cnt[0] = 1;
-      cnt[1] = 0;
-      cnt[2] = gen;
-      cnt[3] = 0;
-      uint64_t *ht = m.ht + (size_t)b * m.hcap;
-      ht[h & (uint64_t)(m.hcap - 1)] = ht_entry(gen, 0);
-    }
-    return;
-  }
-  if (lane == 0) cnt[3] = 0;
-  const bool noisy = !testing && noise && (!m.noise_mask || m.noise_mask[b]);
-  int e0 = 0;
-  const int ne = checked_edges(m, nb, 0, nE, e0);
-  if (!noisy || ne == 0) return;  // (an unexpanded root is mixed where the first simulation expands it)
-  for (int k = lane; k < ne; k += kWave) {
-    const int a = m.edge_action[eb + e0 + k];
-    if (a < 0 || a >= kActions) continue;
-    // the action's rank among the root's legal moves (not the edge index: a skipped self-loop child shifts it)
-    int i = 0;
-#pragma unroll
-    for (int w = 0; w < 3; w++) {
-      const uint64_t bits = w < (a >> 6) ? mk[w] : (w == (a >> 6) ? mk[w] & ((1ull << (a & 63)) - 1) : 0ull);
-      i += __popcll(bits);
-    }
-    if (i >= kMaxChildren) continue;
-    const float p = m.edge_p[eb + e0 + k];
-    m.edge_p[eb + e0 + k] = __double2float_rn(
-        __dadd_rn((double)__fmul_rn(one_minus_eps, p), __dmul_rn(eps, noise[(size_t)b * kMaxChildren + i])));
-  }
-}
-
-template <class T>
-bool alloc(T **p, size_t count) {
-  return hipMalloc((void **)p, count * sizeof(T)) == hipSuccess;
-}
-
-}  // namespace
-
-namespace {
-// Sum of every edge's visit count over the board's tree: each simulation
-// adds one visit to every edge of its path in back_fill (MCTS.py:220-266),
-// so this is the number of edge levels the searches walked (the path-walk
-// term of the tree's algorithmic bytes).  Wave per board, one vector atomic.
-__global__ void __launch_bounds__(kWave) k_path_edges(hz_mcts m, unsigned long long *__restrict__ out) {
-  const int b = blockIdx.x;
-  const int lane = threadIdx.x;
-  const int ne = m.counts[(size_t)b * 4 + 1];
-  const int32_t *en = m.edge_n + (size_t)b * m.max_edges;
-  unsigned long long acc = 0;
-  for (int e = lane; e < ne; e += kWave) acc += (unsigned)en[e];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, kWave);
-  if (lane == 0 && acc) atomicAdd(out, acc);
-}
-
 // canon_key_child against canon_key (hz_key_check): for every legal action of
 // every given state, the child's key built from its parent's equals the key
 // built from the child's state, in both key forms.  One thread per (state,
@@ -2122,7 +1235,7 @@ hz_mcts *hz_mcts_create(int32_t n_boards, int32_t max_nodes, int32_t max_depth, 
   if (n_boards <= 0 || max_nodes < 2 || max_depth < 1) return nullptr;
   if (max_nodes >= kMaxNodesHint) return nullptr;  // edge ids (max_edges = max_nodes) must fit edge_hint_of
   if (install_comp_table()) return nullptr;  // terminal expansions score boards
-  hz_mcts *m = (hz_mcts *)calloc(1, sizeof(hz_mcts));
+  hz_mcts *m = new (std::nothrow) hz_mcts();
   if (!m) return nullptr;
   m->n = n_boards;
   m->max_nodes = max_nodes;
@@ -2134,27 +1247,7 @@ hz_mcts *hz_mcts_create(int32_t n_boards, int32_t max_nodes, int32_t max_depth, 
   m->exact_keys = exact_keys;
   m->gather_mode = -1;
   m->stream = (hipStream_t)stream;
-  size_t n = (size_t)n_boards, N = n * max_nodes, E = n * m->max_edges;
-  bool ok = alloc(&m->node_state, N * 6) && alloc(&m->node_key, N * 8) && alloc(&m->node_e0, N) &&
-            alloc(&m->node_ne, N) && alloc(&m->edge_action, E) && alloc(&m->edge_child, E) &&
-            alloc(&m->edge_n, E) && alloc(&m->edge_w, E) && alloc(&m->edge_p, E) && alloc(&m->edge_player, E) &&
-            alloc(&m->edge_hint, E) &&
-            alloc(&m->ht, n * m->hcap) && alloc(&m->counts, n * 4) && alloc(&m->path, n * max_depth) &&
-            alloc(&m->depth, n) && alloc(&m->leaf, n) && alloc(&m->leaf_gidx, n) && alloc(&m->slot, n) &&
-            alloc(&m->gidx_c, n) && alloc(&m->err, 1) && alloc(&m->sims_done, n) && alloc(&m->budget_buf, n) &&
-            alloc(&m->mask_buf, n);
-  if (ok) {
-    ok = hipMemset(m->ht, 0, n * m->hcap * sizeof(uint64_t)) == hipSuccess &&
-         hipMemset(m->counts, 0, n * 4 * sizeof(int32_t)) == hipSuccess &&
-         hipMemset(m->depth, 0, n * sizeof(int32_t)) == hipSuccess &&
-         hipMemset(m->leaf, 0xff, n * sizeof(int32_t)) == hipSuccess &&
-         hipMemset(m->leaf_gidx, 0xff, n * sizeof(int32_t)) == hipSuccess &&
-         hipMemset(m->err, 0, sizeof(int32_t)) == hipSuccess &&
-         hipMemset(m->sims_done, 0, n * sizeof(int32_t)) == hipSuccess &&
-         hipMemset(m->budget_buf, 0, n * sizeof(int32_t)) == hipSuccess &&
-         hipMemset(m->mask_buf, 0, n * sizeof(uint8_t)) == hipSuccess;
-  }
-  if (!ok) {
+  if (!request_base(m->base_bufs, *m)) {
     hz_mcts_destroy(m);
     return nullptr;
   }
@@ -2163,15 +1256,10 @@ hz_mcts *hz_mcts_create(int32_t n_boards, int32_t max_nodes, int32_t max_depth, 
 
 void hz_mcts_destroy(hz_mcts *m) {
   if (!m) return;
-  void *ptrs[] = {m->node_state, m->node_key, m->node_e0,   m->node_ne, m->edge_action, m->edge_child,
-                  m->edge_n,     m->edge_w,    m->edge_p,    m->edge_player, m->edge_hint, m->ht, m->counts,
-                  m->path,       m->depth,     m->leaf,      m->leaf_gidx, m->slot, m->gidx_c,
-                  m->err,        m->sims_done, m->budget_buf, m->mask_buf,
-                  m->carry,      m->adv_remap, m->adv_queue,
-                  m->gumbel_buf, m->g_score,   m->root_value, m->g_table};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  free(m);
+  m->gumbel_bufs.release();
+  m->carry_bufs.release();
+  m->base_bufs.release();
+  delete m;
 }
 
 int hz_mcts_set_eval_counter(hz_mcts *m, int64_t *counter) {
@@ -2219,12 +1307,6 @@ int hz_mcts_set_budget(hz_mcts *m, const int32_t *budget) {
   return 0;
 }
 
-int hz_mcts_sims_done(hz_mcts *m, int32_t *out) {
-  if (!m || !out) return -1;
-  return hipMemcpyAsync(out, m->sims_done, (size_t)m->n * sizeof(int32_t), hipMemcpyDeviceToDevice, m->stream) ? 1
-                                                                                                                : 0;
-}
-
 int hz_mcts_set_root_noise_mask(hz_mcts *m, const uint8_t *mask) {
   if (!m) return -1;
   m->noise_mask = nullptr;
@@ -2243,19 +1325,9 @@ int hz_mcts_set_gumbel(hz_mcts *m, const double *g, const int16_t *table, int32_
       !(c_visit >= 0.0) || !(c_scale >= 0.0))
     return -1;
   const size_t n = (size_t)m->n;
-  if (!m->gumbel_buf) {  // first use: every buffer at its final size and address, freed by hz_mcts_destroy only
-    const bool ok = alloc(&m->gumbel_buf, n * kMaxChildren) && alloc(&m->g_score, n * kMaxChildren) &&
-                    alloc(&m->root_value, n) && alloc(&m->g_table, (size_t)kGumbelTableMax) &&
-                    hipMemsetAsync(m->g_score, 0, n * kMaxChildren * sizeof(double), m->stream) == hipSuccess &&
-                    hipMemsetAsync(m->root_value, 0, n * sizeof(float), m->stream) == hipSuccess;
-    if (!ok) {
-      for (void *p : {(void *)m->gumbel_buf, (void *)m->g_score, (void *)m->root_value, (void *)m->g_table})
-        if (p) (void)hipFree(p);
-      m->gumbel_buf = m->g_score = nullptr;
-      m->root_value = nullptr;
-      m->g_table = nullptr;
-      return 1;
-    }
+  if (!m->gumbel_buf && !request_gumbel(m->gumbel_bufs, *m)) {  // first use; freed by hz_mcts_destroy only
+    m->gumbel_bufs.release();
+    return 1;
   }
   const int32_t entries = (max_considered + 1) * n_root;  // <= kGumbelTableMax, by the checks above
   if (hipMemcpyAsync(m->gumbel_buf, g, n * kMaxChildren * sizeof(double), hipMemcpyDeviceToDevice, m->stream) ||
@@ -2267,25 +1339,6 @@ int hz_mcts_set_gumbel(hz_mcts *m, const double *g, const int16_t *table, int32_
   m->g_c_scale = c_scale;
   m->gumbel = m->gumbel_buf;
   return 0;
-}
-
-int hz_mcts_root_gumbel_scores(hz_mcts *m, double *out) {
-  if (!m || !out || !m->gumbel) return -1;
-  hipLaunchKernelGGL(k_gumbel_scores, dim3(m->n), dim3(kWave), 0, m->stream, *m, out);
-  return launch_err();
-}
-
-int hz_mcts_gumbel_result(hz_mcts *m, int16_t *action, float *pi, double *value) {
-  if (!m || !action || !pi || !value || !m->gumbel) return -1;
-  hipLaunchKernelGGL(k_gumbel_result, dim3(m->n), dim3(kWave), 0, m->stream, *m, action, pi, value);
-  return launch_err();
-}
-
-int hz_root_gumbel(int32_t n, uint64_t seed, uint64_t board_base, uint64_t move, double *out, void *stream) {
-  if (n < 0 || !out) return -1;
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(k_root_gumbel, dim3(n), dim3(kWave), 0, (hipStream_t)stream, n, seed, board_base, move, out);
-  return launch_err();
 }
 
 int hz_mcts_set_stream(hz_mcts *m, void *stream) {
@@ -2300,35 +1353,6 @@ int hz_mcts_begin(hz_mcts *m, hz_env *env, const uint8_t *active) {
   if (m->carry && hipMemsetAsync(m->carry, 0, (size_t)m->n, m->stream) != hipSuccess) return 1;
   hipLaunchKernelGGL(k_begin, dim3((m->n + kWave - 1) / kWave), dim3(kWave), 0, m->stream, *m,
                      hz_env_state_ptr(env), m->n, active);
-  return launch_err();
-}
-
-int hz_mcts_advance(hz_mcts *m, hz_env *env, const int16_t *action, const uint8_t *active, int32_t headroom,
-                    int32_t *info) {
-  if (!m || !env || !action || !info || headroom < 0 || hz_env_size(env) != m->n) return -1;
-  if (!m->carry) {  // first use: the flags and the scratch (never a second node pool)
-    const size_t n = (size_t)m->n, N = n * m->max_nodes;
-    const bool ok = alloc(&m->carry, n) && alloc(&m->adv_remap, N) && alloc(&m->adv_queue, N) &&
-                    hipMemsetAsync(m->carry, 0, n, m->stream) == hipSuccess;
-    if (!ok) {
-      for (void *p : {(void *)m->carry, (void *)m->adv_remap, (void *)m->adv_queue})
-        if (p) (void)hipFree(p);
-      m->carry = nullptr;
-      m->adv_remap = m->adv_queue = nullptr;
-      return 1;
-    }
-  }
-  hipLaunchKernelGGL(k_advance, dim3(m->n), dim3(kWave), 0, m->stream, *m, hz_env_state_ptr(env), m->n, action,
-                     active, headroom, info);
-  return launch_err();
-}
-
-int hz_mcts_begin_carried(hz_mcts *m, hz_env *env, const uint8_t *active, const double *noise, double eps,
-                          int32_t testing) {
-  if (!m || !env || hz_env_size(env) != m->n) return -1;
-  if (!m->carry) return hz_mcts_begin(m, env, active);  // never advanced: nothing to carry
-  hipLaunchKernelGGL(k_begin_carried, dim3(m->n), dim3(kWave), 0, m->stream, *m, hz_env_state_ptr(env), m->n, active,
-                     noise, eps, (float)(1.0 - eps), testing);
   return launch_err();
 }
 
@@ -2458,81 +1482,12 @@ int hz_mcts_expand_backup_select_gather(hz_mcts *m, hz_env *env, const float *po
                        count_out, count_prev, add_prev);
 }
 
-int hz_root_noise(const int32_t *count, int32_t n, uint64_t seed, uint64_t board_base, uint64_t move, double alpha,
-                  double *noise, double *u, void *stream) {
-  if (n < 0 || !count || !noise || !(alpha > 0.0)) return -1;
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(k_root_noise, dim3(n), dim3(kWave), 0, (hipStream_t)stream, count, n, seed, board_base, move,
-                     alpha, noise, u);
-  return launch_err();
-}
-
-int hz_playout_coin(int32_t n, uint64_t seed, uint64_t board_base, uint64_t move, double *coin, void *stream) {
-  if (n < 0 || !coin) return -1;
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(k_playout_coin, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, seed, board_base,
-                     move, coin);
-  return launch_err();
-}
-
-int hz_mcts_result(hz_mcts *m, int32_t *visits) {
-  if (!m || !visits) return -1;
-  hipLaunchKernelGGL(k_result, dim3(m->n), dim3(kWave), 0, m->stream, *m, visits);
-  return launch_err();
-}
-
-int hz_mcts_stats(hz_mcts *m, int32_t *counts) {
-  if (!m || !counts) return -1;
-  return hipMemcpyAsync(counts, m->counts, (size_t)m->n * 4 * sizeof(int32_t), hipMemcpyDeviceToDevice, m->stream)
-             ? 1
-             : 0;
-}
-
-int hz_mcts_root_edges(hz_mcts *m, int32_t *n, double *w, double *q, float *p, int32_t *child, double *value) {
-  if (!m || !n || !w || !q || !p) return -1;
-  hipLaunchKernelGGL(k_root_edges, dim3(m->n), dim3(kWave), 0, m->stream, *m, n, w, q, p, child, value);
-  return launch_err();
-}
-
-int hz_mcts_pv(hz_mcts *m, int32_t max_len, int16_t *action, int32_t *visits, double *q, uint8_t *player,
-               int32_t *len) {
-  if (!m || max_len < 1 || max_len > m->max_depth || !action || !visits || !q || !player || !len) return -1;
-  hipLaunchKernelGGL(k_pv, dim3(m->n), dim3(kWave), 0, m->stream, *m, max_len, action, visits, q, player, len);
-  return launch_err();
-}
-
-int hz_mcts_export_tree(hz_mcts *m, int32_t b, uint64_t *node_state, int32_t *node_e0, int32_t *node_ne,
-                        int16_t *edge_action, int32_t *edge_child, int32_t *edge_n, double *edge_w, float *edge_p,
-                        uint8_t *edge_player) {
-  if (!m || b < 0 || b >= m->n) return -1;
-  const size_t nb = (size_t)b * m->max_nodes, eb = (size_t)b * m->max_edges, N = m->max_nodes, E = m->max_edges;
-  auto copy = [&](void *dst, const void *src, size_t bytes) {
-    return !dst || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, m->stream) == hipSuccess;
-  };
-  const bool ok = copy(node_state, m->node_state + nb * 6, N * 6 * sizeof(uint64_t)) &&
-                  copy(node_e0, m->node_e0 + nb, N * sizeof(int32_t)) &&
-                  copy(node_ne, m->node_ne + nb, N * sizeof(int32_t)) &&
-                  copy(edge_action, m->edge_action + eb, E * sizeof(int16_t)) &&
-                  copy(edge_child, m->edge_child + eb, E * sizeof(int32_t)) &&
-                  copy(edge_n, m->edge_n + eb, E * sizeof(int32_t)) &&
-                  copy(edge_w, m->edge_w + eb, E * sizeof(double)) &&
-                  copy(edge_p, m->edge_p + eb, E * sizeof(float)) &&
-                  copy(edge_player, m->edge_player + eb, E * sizeof(uint8_t));
-  return ok ? 0 : 1;
-}
-
 #ifdef HZ_DIAG
 int hz_mcts_diag_stamps(uint64_t *host) {
   if (hipDeviceSynchronize() != hipSuccess) return 1;
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_exp_stamps), sizeof(g_exp_stamps)) == hipSuccess ? 0 : 1;
 }
 #endif
-
-int hz_mcts_path_edges(hz_mcts *m, int64_t *out) {
-  if (!m || !out) return -1;
-  hipLaunchKernelGGL(k_path_edges, dim3(m->n), dim3(kWave), 0, m->stream, *m, (unsigned long long *)out);
-  return launch_err();
-}
 
 int hz_key_check(const uint64_t *states, int32_t n, int64_t *out, void *stream) {
   if (!states || !out || n < 0 || (long long)n * kActions > 0x7fffffffLL * 256) return -1;

@@ -227,13 +227,7 @@ class BatchedMCTS:
         return self.board, self.glob, self.rows, self.count
 
     def expand_backup(self, policy, value, noise=None, eps=0.25, testing=True, gathered=False):
-        if policy.numel() == 0:  # no leaf needed the network (never read, but not NULL)
-            policy, value = self._nil_pol, self._nil_val
-        policy = policy.to(dtype=torch.float32).contiguous()
-        value = value.reshape(-1).to(dtype=torch.float32).contiguous()
-        if noise is not None:
-            noise = noise.to(device=self.device, dtype=torch.float64).contiguous()
-        self._set_row_cap(policy, value)
+        policy, value, noise = self._expand_args(policy, value, noise)
         fn = nat.lib().hz_mcts_expand_backup_gathered if gathered else nat.lib().hz_mcts_expand_backup
         nat.check(fn(self._h, self.env.handle, nat.ptr(policy), nat.ptr(value), nat.ptr(noise), float(eps),
                      int(bool(testing))), "hz_mcts_expand_backup")
@@ -241,13 +235,7 @@ class BatchedMCTS:
     def expand_backup_select(self, policy, value, cpuct, active=None, noise=None, eps=0.25, testing=True):
         """expand_backup(gathered=True), then the next simulation's select in
         the same launch (hz_mcts_expand_backup_select)."""
-        if policy.numel() == 0:
-            policy, value = self._nil_pol, self._nil_val
-        policy = policy.to(dtype=torch.float32).contiguous()
-        value = value.reshape(-1).to(dtype=torch.float32).contiguous()
-        if noise is not None:
-            noise = noise.to(device=self.device, dtype=torch.float64).contiguous()
-        self._set_row_cap(policy, value)
+        policy, value, noise = self._expand_args(policy, value, noise)
         nat.check(nat.lib().hz_mcts_expand_backup_select(self._h, self.env.handle, nat.ptr(policy), nat.ptr(value),
                                                          nat.ptr(noise), float(eps), int(bool(testing)),
                                                          nat.ptr(active), float(cpuct)),
@@ -260,6 +248,16 @@ class BatchedMCTS:
         self.board / self.glob / self.rows, its count into count_out (zero on
         entry); count_prev (this batch's) is zeroed, and first added to the
         eval counter when add_prev."""
+        policy, value, noise = self._expand_args(policy, value, noise)
+        nat.check(nat.lib().hz_mcts_expand_backup_select_gather(
+            self._h, self.env.handle, nat.ptr(policy), nat.ptr(value), nat.ptr(noise), float(eps), int(bool(testing)),
+            nat.ptr(active), float(cpuct), nat.ptr(self.board), nat.ptr(self.glob), nat.ptr(self.rows),
+            nat.ptr(count_out), nat.ptr(count_prev), int(bool(add_prev))), "hz_mcts_expand_backup_select_gather")
+
+    def _expand_args(self, policy, value, noise):
+        """What every expand call passes: float32 policy rows and values (the
+        nil row when no leaf needed the network: never read, but not NULL),
+        float64 noise, all contiguous; and the row cap set from them."""
         if policy.numel() == 0:
             policy, value = self._nil_pol, self._nil_val
         policy = policy.to(dtype=torch.float32).contiguous()
@@ -267,10 +265,7 @@ class BatchedMCTS:
         if noise is not None:
             noise = noise.to(device=self.device, dtype=torch.float64).contiguous()
         self._set_row_cap(policy, value)
-        nat.check(nat.lib().hz_mcts_expand_backup_select_gather(
-            self._h, self.env.handle, nat.ptr(policy), nat.ptr(value), nat.ptr(noise), float(eps), int(bool(testing)),
-            nat.ptr(active), float(cpuct), nat.ptr(self.board), nat.ptr(self.glob), nat.ptr(self.rows),
-            nat.ptr(count_out), nat.ptr(count_prev), int(bool(add_prev))), "hz_mcts_expand_backup_select_gather")
+        return policy, value, noise
 
     def _set_row_cap(self, policy, value):
         """Before every expand call: the kernel may read rows [0, cap) of

@@ -1,12 +1,14 @@
 // Stand-alone check of libhz's host layer (csrc/hz_host.hpp, its HIP-free
-// part): built with ASan + UBSan by tests/test_host_cpu.py and run without a
+// part, and the request lists of the search handle's buffers, csrc/hz_mcts.hpp): built with ASan + UBSan by tests/test_host_cpu.py and run without a
 // GPU.  The expected values are written out from the rules the knobs had
 // before they shared a reader; nothing here is computed by the code under test.
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 #include <set>
 
 #include "../harmonies-alphazero_amd/csrc/hz_host.hpp"
+#include "../harmonies-alphazero_amd/csrc/hz_mcts.hpp"
 
 using namespace hz_host;
 
@@ -240,6 +242,111 @@ static void test_bufs() {
   delete h;
 }
 
+// ------------------------------------------- the search handle's three groups
+// hz_mcts's buffers as hz_mcts.hpp's request lists ask for them: the base
+// group has 23 requests of which 9 are filled (ht, counts, depth, err,
+// sims_done, budget_buf, mask_buf with 0; leaf, leaf_gidx with 0xff), the
+// carry group 3 and 1 (carry), the Gumbel group 4 and 2 (g_score, root_value)
+struct TreeHandle : hz_mcts_args {
+  DevBufsT<FakeDev> base_bufs, carry_bufs, gumbel_bufs;
+};
+struct TreeGroup {
+  const char *name;
+  int requests, fills;
+  DevBufsT<FakeDev> TreeHandle::*bufs;
+  bool (*request)(DevBufsT<FakeDev> &, hz_mcts_args &);
+  int (*held)(const hz_mcts_args &);  // how many of the group's pointers are not null
+};
+static int count_set(std::initializer_list<const void *> ps) {
+  int c = 0;
+  for (const void *p : ps) c += p != nullptr;
+  return c;
+}
+static int held_base(const hz_mcts_args &a) {
+  return count_set({a.node_state, a.node_key, a.node_e0, a.node_ne, a.edge_action, a.edge_child, a.edge_n, a.edge_w,
+                    a.edge_p, a.edge_player, a.edge_hint, a.ht, a.counts, a.path, a.depth, a.leaf, a.leaf_gidx, a.slot,
+                    a.gidx_c, a.err, a.sims_done, a.budget_buf, a.mask_buf});
+}
+static int held_carry(const hz_mcts_args &a) { return count_set({a.carry, a.adv_remap, a.adv_queue}); }
+static int held_gumbel(const hz_mcts_args &a) { return count_set({a.gumbel_buf, a.g_score, a.root_value, a.g_table}); }
+static const TreeGroup kTreeGroups[3] = {
+    {"base", 23, 9, &TreeHandle::base_bufs, hz_tree::request_base<DevBufsT<FakeDev>>, held_base},
+    {"carry", 3, 1, &TreeHandle::carry_bufs, hz_tree::request_carry<DevBufsT<FakeDev>>, held_carry},
+    {"gumbel", 4, 2, &TreeHandle::gumbel_bufs, hz_tree::request_gumbel<DevBufsT<FakeDev>>, held_gumbel},
+};
+
+static void test_tree_groups() {
+  TreeHandle *h = new TreeHandle();
+  h->n = 3;
+  h->max_nodes = h->max_edges = 5;
+  h->hcap = 16;
+  h->max_depth = 4;
+  CHECK(held_base(*h) + held_carry(*h) + held_gumbel(*h) == 0);
+  // no failure: every pointer of a group is set by its list, the filled ones hold their byte
+  FakeDev::reset(0, 0);
+  int want_live = 0, want_fills = 0;
+  for (const TreeGroup &g : kTreeGroups) {
+    CHECK(g.request(h->*g.bufs, *h) && (h->*g.bufs).ok);
+    want_live += g.requests;
+    want_fills += g.fills;
+    CHECK(g.held(*h) == g.requests);
+    CHECK((int)FakeDev::live.size() == want_live && FakeDev::allocs == want_live && FakeDev::fills == want_fills);
+  }
+  CHECK(want_live == 30 && want_fills == 12);
+  CHECK(h->ht[3 * 16 - 1] == 0 && h->counts[3 * 4 - 1] == 0 && h->depth[2] == 0 && h->err[0] == 0);
+  CHECK(h->sims_done[2] == 0 && h->budget_buf[2] == 0 && h->mask_buf[2] == 0);
+  CHECK(h->leaf[2] == -1 && h->leaf_gidx[2] == -1);
+  CHECK(h->carry[2] == 0 && h->g_score[3 * 69 - 1] == 0.0 && h->root_value[2] == 0.f);
+  CHECK(!h->budget && !h->noise_mask && !h->gumbel && !h->eval_ctr);  // (aliases and borrowed: no list sets them)
+  for (const TreeGroup &g : kTreeGroups) (h->*g.bufs).release();
+  CHECK(FakeDev::live.empty() && FakeDev::bad_frees == 0 && FakeDev::frees == 30);
+  CHECK(held_base(*h) + held_carry(*h) + held_gumbel(*h) == 0);
+  // group g's k-th allocation fails, then its k-th fill, while the two other groups are held
+  for (const TreeGroup &g : kTreeGroups)
+    for (int pass = 0; pass < 2; pass++)
+      for (int k = 1; k <= (pass ? g.fills : g.requests); k++) {
+        FakeDev::reset(0, 0);
+        int others = 0;
+        for (const TreeGroup &o : kTreeGroups)
+          if (&o != &g) {
+            CHECK(o.request(h->*o.bufs, *h));
+            others += o.requests;
+          }
+        const hz_mcts_args before = *h;
+        const int start = (int)FakeDev::live.size();
+        CHECK(start == others && others == 30 - g.requests);
+        FakeDev::reset(pass ? 0 : k, pass ? k : 0);
+        CHECK(!g.request(h->*g.bufs, *h));
+        CHECK(!(h->*g.bufs).ok);
+        if (!pass) CHECK((int)FakeDev::live.size() == start + k - 1 && g.held(*h) == k - 1);
+        (h->*g.bufs).release();
+        CHECK((h->*g.bufs).ok && g.held(*h) == 0);
+        CHECK((int)FakeDev::live.size() == start && FakeDev::bad_frees == 0);
+        for (const TreeGroup &o : kTreeGroups)
+          if (&o != &g) CHECK(o.held(*h) == o.requests);
+        // the other groups' pointers are the ones they were (g's are null on both sides)
+        const hz_mcts_args &a = *h;
+        CHECK(a.node_state == before.node_state && a.node_key == before.node_key && a.node_e0 == before.node_e0 &&
+              a.node_ne == before.node_ne && a.edge_action == before.edge_action && a.edge_child == before.edge_child &&
+              a.edge_n == before.edge_n && a.edge_w == before.edge_w && a.edge_p == before.edge_p &&
+              a.edge_player == before.edge_player && a.edge_hint == before.edge_hint && a.ht == before.ht &&
+              a.counts == before.counts && a.path == before.path && a.depth == before.depth && a.leaf == before.leaf &&
+              a.leaf_gidx == before.leaf_gidx && a.slot == before.slot && a.gidx_c == before.gidx_c &&
+              a.err == before.err && a.sims_done == before.sims_done && a.budget_buf == before.budget_buf &&
+              a.mask_buf == before.mask_buf);
+        CHECK(a.carry == before.carry && a.adv_remap == before.adv_remap && a.adv_queue == before.adv_queue);
+        CHECK(a.gumbel_buf == before.gumbel_buf && a.g_score == before.g_score && a.root_value == before.root_value &&
+              a.g_table == before.g_table);
+        // a later call tries again, and succeeds
+        FakeDev::reset(0, 0);
+        CHECK(g.request(h->*g.bufs, *h) && g.held(*h) == g.requests && (int)FakeDev::live.size() == 30);
+        for (const TreeGroup &o : kTreeGroups) (h->*o.bufs).release();
+        CHECK(FakeDev::live.empty() && FakeDev::bad_frees == 0);
+        CHECK(held_base(*h) + held_carry(*h) + held_gumbel(*h) == 0);
+      }
+  delete h;
+}
+
 // --------------------------------------------------------- stream windows
 struct FakeEnv {
   int32_t *pw_tag;
@@ -268,6 +375,7 @@ int main() {
   test_knobs();
   test_settings();
   test_bufs();
+  test_tree_groups();
   test_windows_voided();
   if (g_fail) {
     printf("host driver: %d checks failed\n", g_fail);
