@@ -1,5 +1,5 @@
 // hz_draws.hip — the stateless draw kernels of self-play: root noise, the
-// playout-cap coin and the root Gumbels, each keyed by (seed, global board id,
+// playout-cap coin, the root Gumbels and the leaf-symmetry keys, each keyed by (seed, global board id,
 // move).  None takes a handle.
 #include "hz_mcts.hpp"
 
@@ -111,6 +111,18 @@ __global__ void __launch_bounds__(kWave) k_root_gumbel(int n, uint64_t seed, uin
   }
 }
 
+// One 64-bit key per board (hz_leaf_sym_keys: the key leaf_sym_of mixes with a
+// leaf's node id; no reference counterpart): k_root_noise's board key under a
+// salt of its own, so the noise, the move-choice uniform, the coin and the
+// Gumbels keep their bits.
+__global__ void __launch_bounds__(256) k_leaf_sym_keys(int n, uint64_t seed, uint64_t board_base, uint64_t move,
+                                                       uint64_t *__restrict__ out) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  const uint64_t key = mix64(mix64(mix64(seed ^ 0x6A09E667F3BCC908ULL) ^ (board_base + (uint64_t)b)) ^ move);
+  out[b] = mix64(key ^ 0xC2B2AE3D27D4EB4FULL);
+}
+
 }  // namespace
 
 extern "C" {
@@ -136,6 +148,14 @@ int hz_root_gumbel(int32_t n, uint64_t seed, uint64_t board_base, uint64_t move,
   if (n < 0 || !out) return -1;
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_root_gumbel, dim3(n), dim3(kWave), 0, (hipStream_t)stream, n, seed, board_base, move, out);
+  return launch_err();
+}
+
+int hz_leaf_sym_keys(int32_t n, uint64_t seed, uint64_t board_base, uint64_t move, uint64_t *out, void *stream) {
+  if (n < 0 || !out) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_leaf_sym_keys, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, seed, board_base,
+                     move, out);
   return launch_err();
 }
 

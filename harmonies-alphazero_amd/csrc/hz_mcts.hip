@@ -261,7 +261,10 @@ __global__ void __launch_bounds__(kWave) k_select(hz_mcts_args m, const uint8_t 
 // rows[j] = board of gathered row j, slot[b] = j (or -1), count[0] = rows.
 // One workgroup; thread t owns boards [t*per, (t+1)*per) (contiguous, so the
 // exclusive scan of the per-thread counts keeps board order).
+// Sym (a handle whose leaf-symmetry gate is on): row_g[j] = the symmetry row j
+// is to be encoded under (leaf_sym_of), beside gidx_c[j].
 constexpr int kGatherThreads = 1024;
+template <bool Sym>
 __global__ void __launch_bounds__(kGatherThreads) k_gather(hz_mcts_args m, int32_t *__restrict__ rows,
                                                            int32_t *__restrict__ count) {
   __shared__ int32_t part[kGatherThreads];
@@ -284,6 +287,7 @@ __global__ void __launch_bounds__(kGatherThreads) k_gather(hz_mcts_args m, int32
     if (g >= 0) {
       m.slot[b] = j;
       m.gidx_c[j] = g;
+      if constexpr (Sym) m.row_g[j] = (uint8_t)leaf_sym_of(m.leaf_key[b], g - b * m.max_nodes);
       if (rows) rows[j] = b;
       j++;
     } else {
@@ -310,6 +314,8 @@ __global__ void __launch_bounds__(kGatherThreads) k_gather(hz_mcts_args m, int32
 // (profiles/r04/tree/r4p_ge*): fewer workgroups scan the flags, the encoders keep 2048 waves
 constexpr int kGEWaves = 8, kGERows = 2 * kGEWaves, kGEThreads = kGEWaves * kWave, kGELoads = 16;
 constexpr int kBoardFloats = 38 * 35, kGlobFloats = 42;  // one encoded state (hz_encode.hpp)
+// Sym: each row is encoded under its leaf's symmetry (leaf_sym_of), kept beside s_gidx
+template <bool Sym>
 __global__ void __launch_bounds__(kGEThreads) k_gather_encode(hz_mcts_args m, int32_t *__restrict__ rows,
                                                                int32_t *__restrict__ count,
                                                                float *__restrict__ board, float *__restrict__ glob) {
@@ -317,6 +323,7 @@ __global__ void __launch_bounds__(kGEThreads) k_gather_encode(hz_mcts_args m, in
   __shared__ float sval[kGEWaves][76];
   __shared__ int32_t wsum[kGEWaves];
   __shared__ int32_t s_gidx[kGERows];  // this workgroup's rows' leaves (gidx_c's entries), for its encoder waves
+  __shared__ uint8_t s_sym[Sym ? kGERows : 1];
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   const int per = (m.n + kGEThreads - 1) / kGEThreads;
   const int b0 = t * per < m.n ? t * per : m.n, b1 = b0 + per < m.n ? b0 + per : m.n;
@@ -363,6 +370,7 @@ __global__ void __launch_bounds__(kGEThreads) k_gather_encode(hz_mcts_args m, in
         m.slot[b] = r;
         m.gidx_c[r] = g;
         s_gidx[r - r0] = g;
+        if constexpr (Sym) s_sym[r - r0] = (uint8_t)leaf_sym_of(m.leaf_key[b], g - b * m.max_nodes);
         if (rows) rows[r] = b;
       }
       r++;
@@ -386,8 +394,12 @@ __global__ void __launch_bounds__(kGEThreads) k_gather_encode(hz_mcts_args m, in
   if (r0 >= total) return;
   __syncthreads();  // s_gidx complete
   // the workgroup's rows from 0: its leaves from LDS, its outputs from row r0
-  encode_pair<true>(m.node_state, 1, 6, s_gidx, total - r0, board + (size_t)r0 * kBoardFloats,
-                    glob + (size_t)r0 * kGlobFloats, lane, 2 * w, smask[w], sval[w]);
+  if constexpr (Sym)
+    encode_pair<true, true>(m.node_state, 1, 6, s_gidx, total - r0, board + (size_t)r0 * kBoardFloats,
+                            glob + (size_t)r0 * kGlobFloats, lane, 2 * w, smask[w], sval[w], s_sym);
+  else
+    encode_pair<true>(m.node_state, 1, 6, s_gidx, total - r0, board + (size_t)r0 * kBoardFloats,
+                      glob + (size_t)r0 * kGlobFloats, lane, 2 * w, smask[w], sval[w]);
 }
 
 // --------------------------------- select + gather + encode for small batches
@@ -401,7 +413,7 @@ __global__ void __launch_bounds__(kGEThreads) k_gather_encode(hz_mcts_args m, in
 constexpr int kFusedMax = 32;
 constexpr int kFusedWaves = 16;
 static_assert(kFusedMax <= 2 * kFusedWaves && kFusedMax <= kWave, "one pair per wave, one gather wave");
-template <bool Gum>
+template <bool Gum, bool Sym>
 __global__ void __launch_bounds__(kFusedWaves * kWave) k_select_gather_encode(hz_mcts_args m,
                                                                            const uint8_t *__restrict__ active,
                                                                            float cpuct, int32_t *__restrict__ rows,
@@ -411,6 +423,7 @@ __global__ void __launch_bounds__(kFusedWaves * kWave) k_select_gather_encode(hz
   __shared__ uint64_t smask[kFusedWaves][76];
   __shared__ float sval[kFusedWaves][76];
   __shared__ int32_t s_count;
+  __shared__ uint8_t s_sym[Sym ? kFusedMax : 1];  // Sym: the rows' symmetries (leaf_sym_of), beside gidx_c
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int b = w; b < m.n; b += kFusedWaves) select_board<false, Gum>(m, b, lane, active, cpuct);
   __syncthreads();  // every board's leaf_gidx (written by its wave) is visible to the workgroup
@@ -422,6 +435,7 @@ __global__ void __launch_bounds__(kFusedWaves * kWave) k_select_gather_encode(hz
       m.slot[lane] = g >= 0 ? j : -1;
       if (g >= 0) {
         m.gidx_c[j] = g;
+        if constexpr (Sym) s_sym[j] = (uint8_t)leaf_sym_of(m.leaf_key[lane], g - lane * m.max_nodes);
         if (rows) rows[j] = lane;
       }
     }
@@ -433,7 +447,10 @@ __global__ void __launch_bounds__(kFusedWaves * kWave) k_select_gather_encode(hz
     }
   }
   __syncthreads();
-  encode_pair<true>(m.node_state, 1, 6, m.gidx_c, s_count, board, glob, lane, 2 * w, smask[w], sval[w]);
+  if constexpr (Sym)
+    encode_pair<true, true>(m.node_state, 1, 6, m.gidx_c, s_count, board, glob, lane, 2 * w, smask[w], sval[w], s_sym);
+  else
+    encode_pair<true>(m.node_state, 1, 6, m.gidx_c, s_count, board, glob, lane, 2 * w, smask[w], sval[w]);
 }
 
 // ------------------------------------------------ turn-end chance, in parallel
@@ -640,7 +657,10 @@ static_assert(sizeof(uint64_t) * kChildLds * 6 >= sizeof(uint32_t) * kMT, "the s
 // (board b, one wave; the kernel below adds the next simulation's select)
 // Gum (a handle whose Gumbel gate is on): node 0's expansion also stores the
 // network's value of the root and each root edge's G + log P.
-template <bool Gum>
+// Sym (a handle whose leaf-symmetry gate is on): the leaf was evaluated as its
+// image under g = leaf_sym_of, so action a's prior is the row's entry at
+// sym_action(a, g) (every g is an involution); nothing else changes.
+template <bool Gum, bool Sym>
 __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts_args &m, uint32_t *__restrict__ mtw,
                                                     int32_t *__restrict__ mtcur, int32_t *__restrict__ wtag,
                                                     const float *__restrict__ policy,
@@ -707,7 +727,10 @@ __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts_
       for (int r = 0; r < 2; r++) {
         const int c = lane + r * kWave;
         cact[r] = c < nl ? kth_action(mk, c) : 0;
-        cpri[r] = c < nl ? policy[row * kActions + cact[r]] : 0.f;
+        if constexpr (Sym)
+          cpri[r] = c < nl ? policy[row * kActions + sym_action(cact[r], leaf_sym_of(m.leaf_key[b], leaf))] : 0.f;
+        else
+          cpri[r] = c < nl ? policy[row * kActions + cact[r]] : 0.f;
       }
       // the launch lasts as long as its slowest waves, the turn-end
       // expansions (chance replay + ~21 children: ~58 k cycles median against
@@ -1089,7 +1112,9 @@ __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts_
 // WaveSlot (BPW > 1): each wave takes its row with its own atomic add as
 // soon as its walk is done, instead of the workgroup's one add after a
 // barrier that waits for the workgroup's slowest wave (A/B: HZ_SLOT_WAVE)
-template <int Waves, bool Sel, bool Gum, bool Gather = false, int BPW = 1, bool WaveSlot = false>  // Waves: minimum waves per SIMD the register allocation must allow (3: none forced)
+// Sym: the leaf-symmetry gate's instantiations (the expansion's policy index; the gathering form encodes the
+// leaf's image: the four plane words permuted before encode_one_values, which works from the six state words)
+template <int Waves, bool Sel, bool Gum, bool Sym, bool Gather = false, int BPW = 1, bool WaveSlot = false>  // Waves: minimum waves per SIMD the register allocation must allow (3: none forced)
 __global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_eu(Waves, 8))) k_expand_backup(hz_mcts_args m, uint32_t *__restrict__ mtw,
                                                          int32_t *__restrict__ mtcur,
                                                          int32_t *__restrict__ wtag,
@@ -1112,7 +1137,7 @@ __global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_e
   const int b = (int)blockIdx.x * BPW + w;
   const bool live = BPW == 1 || b < m.n;
   if (live)
-    expand_backup_board<Gum>(L, m, mtw, mtcur, wtag, policy, value, noise, eps, one_minus_eps, testing, row_of, prio, b, lane,
+    expand_backup_board<Gum, Sym>(L, m, mtw, mtcur, wtag, policy, value, noise, eps, one_minus_eps, testing, row_of, prio, b, lane,
                         Sel);
   if (Sel) {
     __builtin_amdgcn_s_setprio(0);
@@ -1136,6 +1161,11 @@ __global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_e
         uint64_t lsw[6];
 #pragma unroll
         for (int k = 0; k < 6; k++) lsw[k] = m.node_state[(size_t)g * 6 + k];
+        if constexpr (Sym) {
+          const int gs = leaf_sym_of(m.leaf_key[b], g - b * m.max_nodes);
+#pragma unroll
+          for (int k = 0; k < 4; k++) lsw[k] = sym_plane(lsw[k], gs);
+        }
         encode_one_values(lsw, lane, &L.key[0][0], reinterpret_cast<float *>(&L.key[40][0]), evals, egv);
       }
     }
@@ -1185,6 +1215,50 @@ __global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_e
       HZ_XSTAMP(13)
     }
   }
+}
+
+// ------------------------------------------------------------ leaf symmetries
+// out[b] = the symmetry board b's current leaf is evaluated under (leaf_sym_of;
+// 0 for a board without a leaf to evaluate): hz_mcts_leaf_symmetry's report
+// and the per-board encoder's byte array (hz_mcts_encode_leaves).
+__global__ void __launch_bounds__(256) k_leaf_sym(hz_mcts_args m, uint8_t *__restrict__ out) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= m.n) return;
+  const int g = m.leaf_gidx[b];
+  out[b] = g >= 0 ? (uint8_t)leaf_sym_of(m.leaf_key[b], g - b * m.max_nodes) : (uint8_t)0;
+}
+
+// k_encode_board (hz_encode.hpp) with item j under symmetry sym[j]: the layered
+// encoders of a handle whose gate is on (the global vector holds no coordinate:
+// k_encode_glob serves as it is)
+template <bool Glob>
+__global__ void __launch_bounds__(256) k_encode_board_sym(const uint64_t *__restrict__ st, const int32_t *__restrict__ idx,
+                                                          int m, const int32_t *__restrict__ mcount,
+                                                          const uint8_t *__restrict__ sym, float *__restrict__ board,
+                                                          float *__restrict__ glob) {
+  __shared__ uint64_t smask[kEncWaves][76];
+  __shared__ float sval[kEncWaves][76];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (mcount) m = *mcount < m ? *mcount : m;
+  encode_pair<Glob, true>(st, 1, 6, idx, m, board, glob, lane, 2 * ((long)blockIdx.x * kEncWaves + w), smask[w],
+                          sval[w], sym);
+}
+// launch_encode's choices, over tree nodes
+void launch_encode_sym(const hz_mcts_args &m, const int32_t *idx, const uint8_t *sym, float *board, float *glob,
+                       const int32_t *mcount = nullptr) {
+  if (board) {
+    const dim3 grid((unsigned)((((long)m.n + 1) / 2 + kEncWaves - 1) / kEncWaves));
+    if (glob && m.n <= kEncFuseMax) {
+      hipLaunchKernelGGL(k_encode_board_sym<true>, grid, dim3(256), 0, m.stream, m.node_state, idx, m.n, mcount, sym,
+                         board, glob);
+      return;
+    }
+    hipLaunchKernelGGL(k_encode_board_sym<false>, grid, dim3(256), 0, m.stream, m.node_state, idx, m.n, mcount, sym,
+                       board, nullptr);
+  }
+  if (glob)
+    hipLaunchKernelGGL(k_encode_glob, dim3((unsigned)((m.n * 42 + 255) / 256)), dim3(256), 0, m.stream, m.node_state,
+                       1, 6, idx, m.n, mcount, glob);
 }
 
 // canon_key_child against canon_key (hz_key_check): for every legal action of
@@ -1256,6 +1330,7 @@ hz_mcts *hz_mcts_create(int32_t n_boards, int32_t max_nodes, int32_t max_depth, 
 
 void hz_mcts_destroy(hz_mcts *m) {
   if (!m) return;
+  m->leaf_sym_bufs.release();
   m->gumbel_bufs.release();
   m->carry_bufs.release();
   m->base_bufs.release();
@@ -1341,6 +1416,27 @@ int hz_mcts_set_gumbel(hz_mcts *m, const double *g, const int16_t *table, int32_
   return 0;
 }
 
+int hz_mcts_set_leaf_symmetry(hz_mcts *m, const uint64_t *key) {
+  if (!m) return -1;
+  m->leaf_key = nullptr;
+  if (!key) return 0;
+  if (!m->leaf_key_buf && !request_leaf_sym(m->leaf_sym_bufs, *m)) {  // first use; freed by hz_mcts_destroy only
+    m->leaf_sym_bufs.release();
+    return 1;
+  }
+  if (hipMemcpyAsync(m->leaf_key_buf, key, (size_t)m->n * sizeof(uint64_t), hipMemcpyDeviceToDevice, m->stream))
+    return 1;
+  m->leaf_key = m->leaf_key_buf;
+  return 0;
+}
+
+int hz_mcts_leaf_symmetry(hz_mcts *m, uint8_t *out) {
+  if (!m || !out) return -1;
+  if (!m->leaf_key) return hipMemsetAsync(out, 0, (size_t)m->n, m->stream) == hipSuccess ? 0 : 1;
+  hipLaunchKernelGGL(k_leaf_sym, dim3((m->n + 255) / 256), dim3(256), 0, m->stream, *m, out);
+  return launch_err();
+}
+
 int hz_mcts_set_stream(hz_mcts *m, void *stream) {
   if (!m) return -1;
   m->stream = (hipStream_t)stream;
@@ -1365,6 +1461,11 @@ int hz_mcts_select(hz_mcts *m, const uint8_t *active, float cpuct) {
 
 int hz_mcts_encode_leaves(hz_mcts *m, float *board, float *glob) {
   if (!m || (!board && !glob)) return -1;
+  if (m->leaf_key) {  // the gate: each board's byte first, then the encoders under it
+    hipLaunchKernelGGL(k_leaf_sym, dim3((m->n + 255) / 256), dim3(256), 0, m->stream, *m, m->leaf_g);
+    launch_encode_sym(*m, m->leaf_gidx, m->leaf_g, board, glob);
+    return launch_err();
+  }
   launch_encode(m->node_state, 1, 6, m->leaf_gidx, m->n, board, glob, m->stream);
   return launch_err();
 }
@@ -1376,12 +1477,16 @@ int hz_mcts_select_gather(hz_mcts *m, const uint8_t *active, float cpuct, float 
     const int rc = hz_mcts_select(m, active, cpuct);
     return rc ? rc : hz_mcts_gather_leaves(m, board, glob, rows, count);
   }
+  if (m->gumbel && m->leaf_key) return -1;  // (the symmetric instantiations exist without the Gumbel root only)
   if (m->gumbel)
-    hipLaunchKernelGGL(k_select_gather_encode<true>, dim3(1), dim3(kFusedWaves * kWave), 0, m->stream, *m, active,
-                       cpuct, rows, count, board, glob);
+    hipLaunchKernelGGL((k_select_gather_encode<true, false>), dim3(1), dim3(kFusedWaves * kWave), 0, m->stream, *m,
+                       active, cpuct, rows, count, board, glob);
+  else if (m->leaf_key)
+    hipLaunchKernelGGL((k_select_gather_encode<false, true>), dim3(1), dim3(kFusedWaves * kWave), 0, m->stream, *m,
+                       active, cpuct, rows, count, board, glob);
   else
-    hipLaunchKernelGGL(k_select_gather_encode<false>, dim3(1), dim3(kFusedWaves * kWave), 0, m->stream, *m, active,
-                       cpuct, rows, count, board, glob);
+    hipLaunchKernelGGL((k_select_gather_encode<false, false>), dim3(1), dim3(kFusedWaves * kWave), 0, m->stream, *m,
+                       active, cpuct, rows, count, board, glob);
   return launch_err();
 }
 
@@ -1391,12 +1496,22 @@ int hz_mcts_gather_leaves(hz_mcts *m, float *board, float *glob, int32_t *rows, 
   // encoder launches (same results)
   static const bool fused_default = env_pick("HZ_GATHER_ENCODE", 0, 1);
   const bool fused = m->gather_mode < 0 ? fused_default : m->gather_mode == 1;
+  // (the leaf-symmetry gate picks the instantiation: with it off the kernels carry none of its code)
   if (fused && board && glob) {
-    hipLaunchKernelGGL(k_gather_encode, dim3((m->n + kGERows - 1) / kGERows), dim3(kGEThreads), 0, m->stream, *m,
-                       rows, count, board, glob);
+    if (m->leaf_key)
+      hipLaunchKernelGGL(k_gather_encode<true>, dim3((m->n + kGERows - 1) / kGERows), dim3(kGEThreads), 0, m->stream,
+                         *m, rows, count, board, glob);
+    else
+      hipLaunchKernelGGL(k_gather_encode<false>, dim3((m->n + kGERows - 1) / kGERows), dim3(kGEThreads), 0, m->stream,
+                         *m, rows, count, board, glob);
     return launch_err();
   }
-  hipLaunchKernelGGL(k_gather, dim3(1), dim3(kGatherThreads), 0, m->stream, *m, rows, count);
+  if (m->leaf_key) {
+    hipLaunchKernelGGL(k_gather<true>, dim3(1), dim3(kGatherThreads), 0, m->stream, *m, rows, count);
+    launch_encode_sym(*m, m->gidx_c, m->row_g, board, glob, count);
+    return launch_err();
+  }
+  hipLaunchKernelGGL(k_gather<false>, dim3(1), dim3(kGatherThreads), 0, m->stream, *m, rows, count);
   launch_encode(m->node_state, 1, 6, m->gidx_c, m->n, board, glob, m->stream, count);
   return launch_err();
 }
@@ -1416,6 +1531,7 @@ static int expand_backup(hz_mcts *m, hz_env *env, const float *policy, const flo
                          float *glob = nullptr, int32_t *rows = nullptr, int32_t *count_out = nullptr,
                          int32_t *count_prev = nullptr, int add_prev = 0) {
   if (!m || !env || !policy || !value || hz_env_size(env) != m->n) return -1;
+  if (m->gumbel && m->leaf_key) return -1;  // (the symmetric instantiations exist without the Gumbel root only)
   float ome = (float)(1.0 - eps);
   // default: registers capped for four waves per SIMD (38 VGPRs spilled;
   // with the 9.8 KB LDS, 4096 boards fit the chip in one round): 44.7 vs
@@ -1429,15 +1545,16 @@ static int expand_backup(hz_mcts *m, hz_env *env, const float *policy, const flo
   uint32_t *mt = nullptr;
   int32_t *mt_pos = nullptr, *win_tag = nullptr;
   if (hz_env_stream_ptrs(env, &mt, &mt_pos, &win_tag)) return 1;
-#define HZ_EXPAND_LAUNCH_G(W, S, GUM, G, BP, ...)                                                               \
-  hipLaunchKernelGGL((k_expand_backup<W, S, GUM, G, BP, ##__VA_ARGS__>), dim3((m->n + (BP) - 1) / (BP)), dim3(kWave * (BP)), \
+#define HZ_EXPAND_LAUNCH_G(W, S, GUM, SYM, G, BP, ...)                                                          \
+  hipLaunchKernelGGL((k_expand_backup<W, S, GUM, SYM, G, BP, ##__VA_ARGS__>), dim3((m->n + (BP) - 1) / (BP)), dim3(kWave * (BP)), \
                      0, m->stream, *m, mt, mt_pos, win_tag, policy, value, noise, eps, ome, testing, slot, prio, active, cpuct, \
                      board, glob, rows, count_out, count_prev, add_prev)
-  // (the Gumbel gate picks the instantiation: with it off the kernels carry none of its code)
-#define HZ_EXPAND_LAUNCH(W, S, G, BP, ...)                                  \
-  do {                                                                      \
-    if (m->gumbel) HZ_EXPAND_LAUNCH_G(W, S, true, G, BP, ##__VA_ARGS__);     \
-    else HZ_EXPAND_LAUNCH_G(W, S, false, G, BP, ##__VA_ARGS__);              \
+  // (the Gumbel and leaf-symmetry gates pick the instantiation: with a gate off the kernels carry none of its code)
+#define HZ_EXPAND_LAUNCH(W, S, G, BP, ...)                                               \
+  do {                                                                                   \
+    if (m->gumbel) HZ_EXPAND_LAUNCH_G(W, S, true, false, G, BP, ##__VA_ARGS__);           \
+    else if (m->leaf_key) HZ_EXPAND_LAUNCH_G(W, S, false, true, G, BP, ##__VA_ARGS__);    \
+    else HZ_EXPAND_LAUNCH_G(W, S, false, false, G, BP, ##__VA_ARGS__);                    \
   } while (0)
   const bool gat = sel && count_out;
   if (waves == 4) {

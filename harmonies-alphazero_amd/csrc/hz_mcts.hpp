@@ -69,6 +69,11 @@ struct hz_mcts_args {
   int16_t *g_table;
   int32_t g_considered, g_nroot;
   double g_c_visit, g_c_scale;
+  // leaf symmetries (hz_mcts_set_leaf_symmetry; allocated by its first call): leaf_key == nullptr: gate off, else == leaf_key_buf
+  uint64_t *leaf_key;      // [n] the boards' keys (the handle's copy), or nullptr
+  uint64_t *leaf_key_buf;  // [n] owned; fixed address (a captured simulation stays valid while its contents change)
+  uint8_t *leaf_g;         // [n] by board: the g of leaf_gidx's leaves, for the per-board encoder (hz_mcts_encode_leaves)
+  uint8_t *row_g;          // [n] by gathered row, beside gidx_c: the g of k_gather's rows, for the layered encoder
 };
 
 namespace hz_tree {
@@ -79,7 +84,7 @@ constexpr int kChildSlots = 128;  // two per lane (loop bound: lanes c and c + 6
 constexpr int32_t kGumbelTableMax = (kMaxChildren + 1) * 32767;  // entries of the largest table hz_mcts_set_gumbel admits
 
 // ------------------------------------------------------ the handle's buffers
-// The three groups of a handle's device buffers, each requested whole from its
+// The four groups of a handle's device buffers, each requested whole from its
 // own owner (hz_host.hpp's DevBufsT) and freed by that owner's release(): a
 // request after a failed one does nothing, so each list ends in one check.  A
 // buffer's address is fixed while its group lives (captured simulations bake
@@ -135,6 +140,16 @@ bool request_gumbel(Bufs &o, hz_mcts_args &a) {
   o.get(a.g_table, (size_t)kGumbelTableMax * sizeof(int16_t));
   return o.ok;
 }
+// Leaf symmetries (the first hz_mcts_set_leaf_symmetry): the keys and the two
+// byte arrays the layered encoders read, cleared on the handle's stream.
+template <class Bufs>
+bool request_leaf_sym(Bufs &o, hz_mcts_args &a) {
+  const size_t n = (size_t)a.n;
+  o.get(a.leaf_key_buf, n * sizeof(uint64_t));
+  o.get(a.leaf_g, n * sizeof(uint8_t), 0, (void *)a.stream);
+  o.get(a.row_g, n * sizeof(uint8_t), 0, (void *)a.stream);
+  return o.ok;
+}
 
 }  // namespace hz_tree
 
@@ -149,7 +164,7 @@ bool request_gumbel(Bufs &o, hz_mcts_args &a) {
 // the kernel takes the hz_mcts_args part) and the owners of their buffers.
 // Made by new, never moved: the owners keep the addresses of its pointers.
 struct hz_mcts : hz_mcts_args {
-  hz_host::DevBufs base_bufs, carry_bufs, gumbel_bufs;
+  hz_host::DevBufs base_bufs, carry_bufs, gumbel_bufs, leaf_sym_bufs;
 };
 
 namespace hz_tree {

@@ -102,4 +102,12 @@ __host__ __device__ constexpr int sym_action(int a, int g) {
 }
 static_assert(sym_action(4, 3) == 4 && sym_action(5, 1) == 27 && sym_action(142, 2) == 5 + 23 * 5 + 18, "action map");
 
+// The symmetry a search evaluates a leaf under (include/hz_abi.h, "leaf
+// symmetries"): a pure function of the board's key and the leaf's node id in
+// the board's pool, so whoever encodes the leaf and whoever reads its policy
+// row compute it on their own and agree.
+__host__ __device__ __forceinline__ int leaf_sym_of(uint64_t key, int node) {
+  return (int)(mix64(key ^ (0x9FB21C651E98DF25ULL * (uint64_t)(node + 1))) >> 62);
+}
+
 }  // namespace hz

@@ -80,6 +80,9 @@ _SIGS = {
     "hz_mcts_set_gumbel": ([_vp, _vp, _vp, _c.c_int32, _c.c_int32, _c.c_double, _c.c_double], _c.c_int),
     "hz_mcts_root_gumbel_scores": ([_vp, _vp], _c.c_int),
     "hz_mcts_gumbel_result": ([_vp, _vp, _vp, _vp], _c.c_int),
+    "hz_leaf_sym_keys": ([_c.c_int32, _c.c_uint64, _c.c_uint64, _c.c_uint64, _vp, _vp], _c.c_int),
+    "hz_mcts_set_leaf_symmetry": ([_vp, _vp], _c.c_int),
+    "hz_mcts_leaf_symmetry": ([_vp, _vp], _c.c_int),
     "hz_mcts_advance": ([_vp, _vp, _vp, _vp, _c.c_int32, _vp], _c.c_int),
     "hz_mcts_begin_carried": ([_vp, _vp, _vp, _vp, _c.c_double, _c.c_int32], _c.c_int),
     "hz_mcts_stats": ([_vp, _vp], _c.c_int),

@@ -134,8 +134,10 @@ class BatchedMCTS:
         # boards: only then can a row lie past them, and _finish() reads the
         # handle's error word (hz_mcts_set_row_cap)
         self._cap_risk = False
-        # (budget gate on, root-noise mask on, the Gumbel gate's settings or None), as last set by search()
-        self._gate = (False, False, None)
+        # (budget gate on, root-noise mask on, the Gumbel gate's settings or None, leaf-symmetry gate on), as last
+        # set by search()
+        self._gate = (False, False, None, False)
+        self._leaf_sym = torch.zeros(self.n, dtype=torch.uint8, device=d)  # leaf_symmetries()' report
         self._gumbel_tables = {}  # (max_considered, n_root) -> the device table (built once per shape)
         # tree reuse (advance() / search(carry=True)): advance's info rows, and
         # the edges and walked levels the search began with (count_edges and
@@ -348,12 +350,37 @@ class BatchedMCTS:
         nat.check(nat.lib().hz_mcts_root_gumbel_scores(self._h, nat.ptr(r)), "hz_mcts_root_gumbel_scores")
         return r
 
-    def _set_gate(self, budget, root_noise, gumbel=None):
+    def _set_leaf_symmetry(self, keys):
+        """The leaf-symmetry gate of the search about to begin (keys None:
+        off), copied into the handle in stream order; returns whether it is on."""
+        L = nat.lib()
+        if keys is None:
+            if hasattr(L, "hz_mcts_set_leaf_symmetry"):  # (an older A/B build named by HZ_LIB has no gate to clear)
+                nat.check(L.hz_mcts_set_leaf_symmetry(self._h, None), "hz_mcts_set_leaf_symmetry")
+            return False
+        if not torch.is_tensor(keys) or keys.dtype not in (torch.int64, torch.uint64):
+            raise ValueError("leaf_symmetry: an int64 / uint64 tensor of one key per board (NoiseSource.leaf_symmetry)")
+        if keys.shape != (self.n,):
+            raise ValueError(f"leaf_symmetry of shape {tuple(keys.shape)}, not ({self.n},)")
+        keys = keys.to(device=self.device).contiguous()
+        nat.check(L.hz_mcts_set_leaf_symmetry(self._h, nat.ptr(keys)), "hz_mcts_set_leaf_symmetry")
+        return True
+
+    def leaf_symmetries(self):
+        """Device uint8 [n]: the symmetry g each board's current leaf is
+        evaluated under (hz_mcts_leaf_symmetry): 0 for a board without a leaf
+        to evaluate, and everywhere after a search without leaf_symmetry=.
+        The handle's own tensor, rewritten by the next call."""
+        nat.check(nat.lib().hz_mcts_leaf_symmetry(self._h, nat.ptr(self._leaf_sym)), "hz_mcts_leaf_symmetry")
+        return self._leaf_sym
+
+    def _set_gate(self, budget, root_noise, gumbel=None, leaf_sym=False):
         """The budget gate and the root-noise mask of the search about to
         begin (None: off), copied into the handle in stream order; gumbel:
-        the Gumbel gate's settings as _set_gumbel returned them."""
+        the Gumbel gate's settings as _set_gumbel returned them; leaf_sym:
+        whether the leaf-symmetry gate is on (_set_leaf_symmetry)."""
         L = nat.lib()
-        self._gate = (self._gate[0], self._gate[1], gumbel)
+        self._gate = (self._gate[0], self._gate[1], gumbel, leaf_sym)
         if budget is None and root_noise is None and not hasattr(L, "hz_mcts_set_budget"):
             return  # (an older A/B build named by HZ_LIB: it has no gate to clear)
         if budget is not None:
@@ -366,7 +393,7 @@ class BatchedMCTS:
                 raise ValueError(f"root_noise of shape {tuple(root_noise.shape)}, not ({self.n},)")
         nat.check(L.hz_mcts_set_budget(self._h, nat.ptr(budget)), "hz_mcts_set_budget")
         nat.check(L.hz_mcts_set_root_noise_mask(self._h, nat.ptr(root_noise)), "hz_mcts_set_root_noise_mask")
-        self._gate = (budget is not None, root_noise is not None, gumbel)
+        self._gate = (budget is not None, root_noise is not None, gumbel, leaf_sym)
 
     def stats(self):
         nat.check(nat.lib().hz_mcts_stats(self._h, nat.ptr(self.counts)), "hz_mcts_stats")
@@ -493,7 +520,7 @@ class BatchedMCTS:
 
     def search(self, evaluator, cpuct, active=None, noise=None, eps=0.25, testing=True, sims=None,
                gather=True, graph=False, max_rows=None, budget=None, root_noise=None, tail=None, carry=False,
-               root=None, gumbel=None, max_considered=None, c_visit=None, c_scale=None):
+               root=None, gumbel=None, max_considered=None, c_visit=None, c_scale=None, leaf_symmetry=None):
         """get_best_action_and_pi's simulation loop (MCTS.py:288-352) for every
         active board; returns root visit counts int32 [n, 143].
 
@@ -542,7 +569,19 @@ class BatchedMCTS:
         the search is PUCT as always.  gumbel_result() then has the move, the
         improved policy and v_mix; the visits returned are the search's.  In
         every search form; not with noise=, root_noise=, budget=, tail= or
-        carry=True (ValueError).  A search without root= clears the gate."""
+        carry=True (ValueError).  A search without root= clears the gate.
+
+        leaf_symmetry=keys (int64 / uint64 [n] on the device, one key per
+        board: NoiseSource.leaf_symmetry): every leaf is evaluated under one
+        of the board's four symmetries, g a function of the board's key and
+        the leaf's node id (hz_mcts_set_leaf_symmetry states the rule): the
+        network sees the leaf's image and the expansion reads the priors back
+        through g; the walk, the children, the draws and the backup are what
+        they are without it.  In every search form, with active=, budget=,
+        root_noise=, tail= and max_rows=; not with root="gumbel" or
+        carry=True (ValueError).  A search without it clears the gate."""
+        if leaf_symmetry is not None and (root == "gumbel" or carry):
+            raise ValueError("leaf_symmetry= does not combine with root='gumbel' or carry=True")
         if root not in (None, "gumbel"):
             raise ValueError(f"root {root!r}: not None or 'gumbel'")
         if root is None and (gumbel is not None or max_considered is not None or c_visit is not None or
@@ -557,7 +596,8 @@ class BatchedMCTS:
             active = active.to(device=self.device, dtype=torch.uint8).contiguous()
         self._sync()
         self._set_gate(budget, root_noise, self._set_gumbel(
-            gumbel, self.num_simulations if sims is None else int(sims), max_considered, c_visit, c_scale))
+            gumbel, self.num_simulations if sims is None else int(sims), max_considered, c_visit, c_scale),
+            self._set_leaf_symmetry(leaf_symmetry))
         self._edges_base = self._path_base = None
         if carry:
             self.begin_carried(active, noise, eps, testing)
@@ -583,7 +623,7 @@ class BatchedMCTS:
             # search with the same settings (the drop-in's one search per move);
             # only without an `active` mask, whose tensor the graph would bake in
             gk = getattr(evaluator, "graph_key", None)
-            # (a capture holds the handle by value: whether the gate and the
+            # (a capture holds the handle by value: whether each gate and the
             # mask are on, and each step's row cap, belong to the key)
             head = min(max(s0 - 1, 0), total - 1)  # replays before the tail (simulation 0 ran eagerly)
             steps = ((max_rows, head), (tail_rows, total - 1 - head))

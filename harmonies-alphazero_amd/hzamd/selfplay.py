@@ -38,6 +38,13 @@ top-m actions by Gumbel + log prior (BatchedMCTS.search(root="gumbel"), whose
 rule include/hz_abi.h states) instead of PUCT with Dirichlet noise; the move
 is the search's own at every ply, and the visit slots of the records hold the
 improved policy as rint(pi' * 65535), so pi = N / sum N rebuilds it.
+
+Leaf symmetries (no reference counterpart; config key `leaf_symmetry`:
+"random", absent by default): every leaf of every search is evaluated under
+one of the board's four symmetries, drawn per board and node from the move's
+key (NoiseSource.leaf_symmetry, BatchedMCTS.search(leaf_symmetry=), whose rule
+include/hz_abi.h states).  With playout caps; not with tree_reuse or
+root_policy "gumbel".
 """
 import torch
 
@@ -110,6 +117,17 @@ class NoiseSource:
                   "hz_root_gumbel")
         return g
 
+    def leaf_symmetry(self, step, n):
+        """One 64-bit key per board under the same key (hz_leaf_sym_keys),
+        int64 [n] on the device: move `step`'s keys for
+        BatchedMCTS.search(leaf_symmetry=); draw(), coin() and gumbel() do not
+        depend on it."""
+        keys = torch.empty(n, dtype=torch.int64, device=self.device)
+        nat.check(nat.lib().hz_leaf_sym_keys(n, self.seed & (2**64 - 1), self.board_base & (2**64 - 1),
+                                             int(step) & (2**64 - 1), nat.ptr(keys), nat.stream_ptr(self.device)),
+                  "hz_leaf_sym_keys")
+        return keys
+
 
 class SelfPlay:
     def __init__(self, n_boards, evaluator, mcts_config=None, seed_base=0, device="cuda", max_plies=200,
@@ -142,6 +160,12 @@ class SelfPlay:
                 raise ValueError("root_policy 'gumbel' does not combine with playout caps or tree_reuse")
             self.gumbel = {"max_considered": self.cfg.get("gumbel_max_considered"),
                            "c_visit": self.cfg.get("gumbel_c_visit"), "c_scale": self.cfg.get("gumbel_c_scale")}
+        # leaf symmetries: on when leaf_symmetry is "random" (absent: every leaf in the orientation it was played in)
+        self.leaf_symmetry = self.cfg.get("leaf_symmetry")
+        if self.leaf_symmetry not in (None, "random"):
+            raise ValueError(f"leaf_symmetry {self.leaf_symmetry!r}: not 'random'")
+        if self.leaf_symmetry and (self.tree_reuse or policy == "gumbel"):
+            raise ValueError("leaf_symmetry does not combine with tree_reuse or root_policy 'gumbel'")
         self.last_gumbel = None  # gumbel_result() of the last move(), with the Gumbel root
         max_nodes = int(pool * (1 + MAX_CHILDREN * self.cfg["num_simulations"])) if self.tree_reuse else None
         self.mcts = BatchedMCTS(self.env, self.cfg["num_simulations"], max_nodes=max_nodes, exact_keys=exact_keys)
@@ -228,9 +252,11 @@ class SelfPlay:
             self.last_carried = carried
             if self.tree_reuse == "topup":
                 budget = topup_budgets(carried, cfg["num_simulations"], self.reuse_min_sims)
+        keys = self.noise.leaf_symmetry(step, n) if self.leaf_symmetry else None
         v = self.mcts.search(self.evaluator, cfg["cpuct"], active=active, noise=noise,
                              eps=cfg["dirichlet_epsilon"], testing=testing, max_rows=max(1, bound),
-                             budget=budget, root_noise=full, tail=tail, carry=self.tree_reuse is not None)
+                             budget=budget, root_noise=full, tail=tail, carry=self.tree_reuse is not None,
+                             leaf_symmetry=keys)
         if self.keep_root_value:
             self.last_root_value = self.mcts.root_edges()["value"]
         self.check_steps()  # the previous move's step, done long before this search runs

@@ -485,6 +485,52 @@ int hz_mcts_set_gumbel(hz_mcts *mcts, const double *g, const int16_t *table, int
                        double c_visit, double c_scale);
 int hz_mcts_root_gumbel_scores(hz_mcts *mcts, double *out);
 int hz_mcts_gumbel_result(hz_mcts *mcts, int16_t *action, float *pi, double *value);
+/* ---- leaf symmetries: each leaf evaluated under a random board symmetry -------
+ * No reference counterpart (AlphaGo Zero's random symmetry per evaluation): the
+ * build's defined behaviour, off by default, pinned by tests/mcts_leafsym_model.py.
+ * The network sees each leaf in one of the board's four orientations ("board
+ * symmetries" above), so its asymmetries do not always push the same way.
+ *
+ * hz_leaf_sym_keys: out[n] (device u64) gets one key per board, from
+ * hz_root_noise's generator and board key (seed, board_base + b, move) under a
+ * salt of its own: key = mix64(mix64(mix64(seed ^ 0x6A09E667F3BCC908) ^
+ * (board_base + b)) ^ move), out[b] = mix64(key ^ 0xC2B2AE3D27D4EB4F), mix64 the
+ * splitmix64 finalizer.  The noise, the move-choice uniform, the coin and the
+ * Gumbels keep their bits, and a board's key does not depend on the batch or on
+ * how board_base splits it.  Enqueued on `stream`.
+ *
+ * hz_mcts_set_leaf_symmetry: key[n] (device u64) is copied in stream order into
+ * a buffer the handle owns; key == NULL turns the gate off (the default).  Call
+ * it before the hz_mcts_begin of a search.  The buffers are allocated by the
+ * first call and keep their addresses until hz_mcts_destroy, so a captured
+ * simulation stays valid while the keys change; whether the gate is on is held
+ * by value in a capture, which is to be replayed only under the gate it was
+ * captured with.
+ *   The rule.  The symmetry of board b's leaf is a pure function of the key and
+ * the leaf's node id in the board's pool:
+ *     g = mix64(key[b] ^ (0x9FB21C651E98DF25 * (node + 1))) >> 62
+ * (64-bit wrapping arithmetic).  A node is evaluated at most once per search,
+ * and a refused expansion repeats with the same g; the rule needs no simulation
+ * counter, so it is the same in every search form and under graph replay; the
+ * side that encodes a leaf and the side that expands it compute g on their own.
+ *   Under the gate the row encoded for a leaf, by every call that encodes
+ * leaves (hz_mcts_encode_leaves, hz_mcts_gather_leaves in both forms,
+ * hz_mcts_select_gather, hz_mcts_expand_backup_select_gather), is the encoding
+ * of the leaf's state under g, and the expansion reads the prior of action a at
+ * policy[row][a under g] (every g is its own inverse).  The value is read as it
+ * is.  Nothing else changes: the walk, the children (built from the leaf as
+ * stored), keys, transpositions, chance draws, root noise by legal rank, backup
+ * and limits are what they are without the gate.
+ *   The gate does not combine with the Gumbel root: with both on, the calls
+ * that select-and-gather or expand return -1 and enqueue nothing.
+ *
+ * hz_mcts_leaf_symmetry: out[n] (device u8) gets the g of each board's current
+ * leaf; 0 for a board without a leaf to evaluate (inactive, terminal leaf,
+ * budget spent) and for every board while the gate is off.  A report for
+ * callers and tests, enqueued on the handle's stream. */
+int hz_leaf_sym_keys(int32_t n, uint64_t seed, uint64_t board_base, uint64_t move, uint64_t *out, void *stream);
+int hz_mcts_set_leaf_symmetry(hz_mcts *mcts, const uint64_t *key);
+int hz_mcts_leaf_symmetry(hz_mcts *mcts, uint8_t *out);
 /* ---- tree reuse: the searched subtree carried into the next search ----------
  * No reference counterpart (MCTS.py:288 builds a fresh Node per call): this is
  * the build's defined behaviour, off unless the caller asks for it, pinned by
