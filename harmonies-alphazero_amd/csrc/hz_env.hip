@@ -39,10 +39,10 @@ struct P2Mid {    // a play stage's end state, for the next play stage
 };
 
 // pipeline 2's shape (k_play2): one seeding stage for pass 1, three for pass
-// 2, kP2Draw draw stages, kP2Play play stages.  (A/B builds: -DHZ_P2_NDRAW=4
-// and / or -DHZ_P2_NPLAY=4 leave the waves of the fifth stages idle.)
+// 2, kP2Draw draw stages, kP2Play play stages.  (A/B builds: -DHZ_P2_NDRAW=5
+// or 4 and / or -DHZ_P2_NPLAY=4 leave the waves of the last stages idle.)
 #ifndef HZ_P2_NDRAW
-#define HZ_P2_NDRAW 5
+#define HZ_P2_NDRAW 6
 #endif
 #ifndef HZ_P2_NPLAY
 #define HZ_P2_NPLAY 5
@@ -53,11 +53,11 @@ constexpr int kP2SDraw = 4;                    // the first draw stage (after P1
 constexpr int kP2SPlay = kP2SDraw + kP2Draw;   // the first play stage
 constexpr int kP2Stages = kP2SPlay + kP2Play;
 constexpr int kP2Last = kP2Stages - 1;  // stage s works on episode ep + kP2Last - s
-constexpr int kP2Ring = kP2Play + 1;    // the last draw stage's scripts and the rule hashes: read by the play stages 1..kP2Play calls later
+constexpr int kP2Ring = kP2Play + 1;    // the last draw stage's scripts: read by the play stages 1..kP2Play calls later
 // stream slots: one per stage from P2a on (P1 runs in registers), plus one:
 // the last play stage's slot stays the board's stream
 constexpr int kP2Stream = kP2Stages;
-static_assert(kP2Draw >= 2 && kP2Draw <= 5 && kP2Play >= 2 && kP2Play <= 5, "stage counts");
+static_assert(kP2Draw >= 2 && kP2Draw <= 6 && kP2Play >= 2 && kP2Play <= 5, "stage counts");
 
 // Created by value-initialising new: every field starts zero.  The device
 // buffers belong to three owners by lifetime (bufs: hz_env_create; p2_bufs:
@@ -131,8 +131,7 @@ struct hz_env {
   P2Draw p2_x[kP2Draw - 1][2];   // D1 -> D2 -> ... -> the last draw stage, by call parity
   P2Draw p2_pl[kP2Ring];         // the last draw stage -> every play stage: a ring
   P2Mid p2_m[kP2Play - 1][2];    // play stage st -> st + 1, by call parity
-  uint32_t *p2_h[kP2Ring];       // [kRulePlies][nrow] rule hashes, a ring
-  int32_t *p2_h_tag[kP2Ring];    // [nrow] their episode
+  uint32_t *p2_h[kP2Stream];     // [kRulePlies][nrow] rule hashes: entry k goes with stream slot k (and its tag)
   int32_t *p2_ep[2];         // [nrow] episode counter each board ended the call with
   // a pipeline wave that gives up waiting for its publisher (a bounded spin
   // on an LDS progress counter) ORs a bit into *wait_err (kWaitErr*), so the
@@ -680,14 +679,15 @@ static int p2_clear_tags(hz_env *e) {
   for (int k = 0; k < kP2Draw - 1; k++)
     if (c(e->p2_x[k][0].tag) || c(e->p2_x[k][1].tag)) return 1;
   for (int k = 0; k < kP2Ring; k++)
-    if (c(e->p2_pl[k].tag) || c(e->p2_h_tag[k])) return 1;
+    if (c(e->p2_pl[k].tag)) return 1;
   for (int k = 0; k < kP2Play - 1; k++)
     if (c(e->p2_m[k][0].tag) || c(e->p2_m[k][1].tag)) return 1;
   return 0;
 }
 
 // allocated on first use: kP2Stream stream slots of 2.5 KB per board plus
-// ~2.3 KB of hand-offs per board
+// ~5 KB of hand-offs per board (the rule hashes' ring, an entry per slot, is
+// most of it)
 static int alloc_p2(hz_env *e) {
   if (e->p2_s[0]) return 0;
   const size_t nr = e->nrow;
@@ -696,6 +696,7 @@ static int alloc_p2(hz_env *e) {
     o.get(e->p2_s[k], nr * kMT * 4);
     o.get(e->p2_s_tag[k], nr * 4);
     o.get(e->p2_s_cur[k], (kAheadDraws + 1) * nr * 4);
+    o.get(e->p2_h[k], kRulePlies * nr * 4);
   }
   auto md = [&](P2Draw &d) {
     o.get(d.tag, nr * 4);
@@ -707,8 +708,6 @@ static int alloc_p2(hz_env *e) {
   for (int k = 0; k < kP2Draw - 1; k++) md(e->p2_x[k][0]), md(e->p2_x[k][1]);
   for (int k = 0; k < kP2Ring; k++) {
     md(e->p2_pl[k]);
-    o.get(e->p2_h[k], kRulePlies * nr * 4);
-    o.get(e->p2_h_tag[k], nr * 4);
   }
   for (int k = 0; k < kP2Play - 1; k++)
     for (int j = 0; j < 2; j++) {
@@ -736,8 +735,11 @@ static int alloc_p2(hz_env *e) {
 // one hz_play call of pipeline 2 (k_play2).  Call c uses stream slot
 // (c - s) % kP2Stream for stage s >= 1 (P1, stage 0, has none); the draw
 // stages' hand-offs, P1 -> P2a -> P2b -> P2c and play stage st -> st + 1 by
-// call parity; the last draw stage's script and the rule hashes in rings of
-// kP2Ring (read by play stage st st + 1 calls later).  Every slot written by
+// call parity; the last draw stage's script in a ring of kP2Ring (read by
+// play stage st st + 1 calls later); the rule hashes in a ring as long as the
+// slots', indexed like them (entry (c - s) % kP2Stream for stage s: written by
+// the seeding stages, P1 included, each its rows, read by the play stages),
+// valid whenever the slot's tag says seeded.  Every slot written by
 // call c is read by call c + 1 or later, so launch order on the stream is the
 // only synchronisation.
 static int launch_play2(hz_env *e, int32_t max_plies, int32_t *games_done, int32_t *steps_done) {
@@ -773,6 +775,7 @@ static int launch_play2(hz_env *e, int32_t max_plies, int32_t *games_done, int32
     a.s_mt[s] = e->p2_s[sl(s)];
     a.s_tag[s] = e->p2_s_tag[sl(s)];
   }
+  for (int s = 0; s < kP2SDraw; s++) a.s_h[s] = e->p2_h[sl(s)];
   a.s_idx_last = sl(kP2Last);
   a.p1h_w = e->p2_p1h[r];
   a.p1t_w = e->p2_p1t[r];
@@ -800,13 +803,11 @@ static int launch_play2(hz_env *e, int32_t max_plies, int32_t *games_done, int32
     d.d0 = e->p2_dcut[k];
     d.d1 = k == kP2Draw - 1 ? draws : std::min(draws, e->p2_dcut[k + 1]);
   }
-  a.h_w = e->p2_h[c % kP2Ring];
-  a.ht_w = e->p2_h_tag[c % kP2Ring];
   for (int st = 0; st < kP2Play; st++) {
     P2PlayArgs &p = a.pp[st];
     const bool last = st == kP2Play - 1;
     const int s = kP2SPlay + st;
-    const int k = (c + kP2Ring - 1 - st) % kP2Ring;  // the script and the hashes written by call c - 1 - st
+    const int k = (c + kP2Ring - 1 - st) % kP2Ring;  // the script written by call c - 1 - st
     p.ep = last ? e->episode : e->p2_ep[w];
     p.ep_off = last ? 0 : kP2Play - 1 - st;
     p.g0 = st > 0 ? e->p2_cut[st - 1] : 0;
@@ -815,8 +816,7 @@ static int launch_play2(hz_env *e, int32_t max_plies, int32_t *games_done, int32
     p.ptag = e->p2_pl[k].tag;
     p.pk = e->p2_pl[k].k;
     p.q = st > 0 ? e->p2_m[st - 1][w].q : e->p2_pl[k].q;
-    p.h = e->p2_h[k];
-    p.ht = e->p2_h_tag[k];
+    p.h = e->p2_h[sl(s)];
     p.slot = e->p2_s[sl(s)];
     p.cur = e->p2_s_cur[sl(s)];
     p.in = e->p2_m[st > 0 ? st - 1 : 0][w];  // play stage st - 1 -> st, by call parity
@@ -887,18 +887,14 @@ hz_env *hz_env_create(int32_t n_boards, uint64_t seed_base, void *stream) {
   for (int k = 0; k < kP2Play - 1; k++) e->p2_cut[k] = kP2PCut[k];
   if constexpr (kP2Play == 4) env_cuts("HZ_P2_CUTS", e->p2_cut);
   else if constexpr (kP2Play == 5) env_cuts_n("HZ_P2_CUTS5", e->p2_cut, kP2Play - 1, 4, 1 << 20);
-  // HZ_P2_DCUTS="a,b,c,d": the first draws of draw stages 2..5 (increasing,
-  // 1..23; stage 1 starts at draw 0; no stage more than kP2StageDraws draws,
-  // else the setting is ignored)
+  // HZ_P2_DCUTS="a,b,c,d[,e]": the first draws of draw stages 2..5, or 2..6
+  // (increasing, 1..23, the sixth's may be 24: an empty stage; stage 1 starts
+  // at draw 0; with four values the sixth stage keeps its default, raised to
+  // the fifth's; no stage more than kP2StageDraws draws, else the setting is
+  // ignored: env_p2_dcuts)
   for (int k = 0; k < kP2Draw; k++) e->p2_dcut[k] = kP2DCut[k];
   e->p2_dcut[kP2Draw] = kAheadDraws;
-  if constexpr (kP2Draw == 5) {
-    int dc[kP2Draw + 1];
-    for (int k = 0; k <= kP2Draw; k++) dc[k] = e->p2_dcut[k];
-    if (env_cuts_n("HZ_P2_DCUTS", dc + 1, kP2Draw - 1, 1, kAheadDraws - 1) &&
-        cuts_gaps_within(dc, kP2Draw + 1, kP2StageDraws))
-      for (int k = 0; k <= kP2Draw; k++) e->p2_dcut[k] = dc[k];
-  }
+  if constexpr (kP2Draw >= 5) env_p2_dcuts("HZ_P2_DCUTS", e->p2_dcut, kP2Draw, kAheadDraws, kP2StageDraws);
   // HZ_P2_FELL_LIMIT: the slot rows a play stage may draw from once its
   // script has run out (a slot holds kP2Twist; a game that needs more is
   // played again from scratch by the last play stage).  Lower values only

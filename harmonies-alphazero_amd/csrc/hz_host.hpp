@@ -1,7 +1,8 @@
 // hz_host.hpp — the host layer every .hip unit of libhz shares (csrc/units.mk
 // names them): no device code.
 //
-//   env_int / env_pick / env_clamped / env_cuts(_n), Setting : the environment knobs
+//   env_int / env_pick / env_clamped / env_cuts(_n) /
+//   env_p2_dcuts, Setting                                : the environment knobs
 //   DevBufsT<Dev>                                        : owner of device buffers
 //   streams_touched<Dev>(e)                              : voids the saved draw windows
 //   launch_err(), lds_opt_in<Kernel>(bytes)              : launch helpers (HIP only)
@@ -76,6 +77,30 @@ inline bool env_cuts_n(const char *name, int *cut, int n, int step, int hi) {
 inline bool cuts_gaps_within(const int *cut, int n, int max_gap) {
   for (int k = 0; k + 1 < n; k++)
     if (cut[k + 1] - cut[k] > max_gap) return false;
+  return true;
+}
+
+// Pipeline 2's draw cuts (HZ_P2_DCUTS).  dcut[0 .. ndraw] holds the defaults
+// on entry: dcut[0] = 0, the first draws of stages 2 .. ndraw, and
+// dcut[ndraw] = draws, one past the last draw.  The setting lists the first
+// draws of stages 2 .. ndraw (ndraw - 1 increasing values in 1 .. draws; only
+// the last stage's may be `draws`, an empty stage) or, with six stages, those
+// of stages 2 .. 5 alone (four values in 1 .. draws - 1): the sixth stage's
+// then stays the default's, raised to the fifth's if that is later.  No stage
+// may take more than max_gap draws.  True and dcut[] replaced if the setting
+// is valid, else false and dcut[] as it was.
+inline bool env_p2_dcuts(const char *name, int *dcut, int ndraw, int draws, int max_gap) {
+  if (ndraw < 2 || ndraw > 8) return false;
+  int dc[9];
+  for (int k = 0; k <= ndraw; k++) dc[k] = dcut[k];
+  bool got = ndraw == 6 && env_cuts_n(name, dc + 1, 5, 1, draws);
+  if (!got) {
+    const int n = ndraw == 6 ? 4 : ndraw - 1;
+    got = env_cuts_n(name, dc + 1, n, 1, draws - 1);
+    if (got && ndraw == 6 && dc[5] < dc[4]) dc[5] = dc[4];
+  }
+  if (!got || !cuts_gaps_within(dc, ndraw + 1, max_gap)) return false;
+  for (int k = 0; k <= ndraw; k++) dcut[k] = dc[k];
   return true;
 }
 

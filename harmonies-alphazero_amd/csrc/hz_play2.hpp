@@ -11,11 +11,11 @@ namespace {
 // hz_play's second pipeline (hz_env_set_pipeline(e, 2)).  Each of
 // k_rollout's roles runs one serial per-board chain of ~60 k cycles (a whole
 // game, a whole seeding, 16 pile draws), and a launch lasts as long as its
-// longest chain.  Here every board's episode is cut into fourteen stages of
+// longest chain.  Here every board's episode is cut into fifteen stages of
 // about 20 k cycles, one per consecutive hz_play call, and one launch runs
-// all fourteen at once, each on a different episode of the board (ep = the
+// all fifteen at once, each on a different episode of the board (ep = the
 // episode counter the previous call left, p2_ep; stage s works on episode
-// ep + 13 - s).  The wave of each stage outside the seed and play blocks is
+// ep + 14 - s).  The wave of each stage outside the seed and play blocks is
 // kP2Wave's (HZ_P2_WAVES); by default:
 //   s = 0  P1    seeding pass 1, all 624 steps, in     draw-Y blocks, wave 2
 //                registers: only its last word leaves
@@ -26,19 +26,22 @@ namespace {
 //   s = 3  P2c   pass 2, steps 433-624, rows 433-560  seed blocks, wave 2
 //                kept in LDS; rows 0-159 of the next  (twist: wave 3)
 //                generation twisted
+//          (each of s = 0..3 then computes its rows of the episode's 80 rule
+//          hashes, kP2HashCut, from the seed it holds, behind its chain)
 //   s = 4  D1    pile draws [dcut0 = 0, dcut1), from  draw-X blocks, wave 0
 //                slot rows [L, L + 96), L = 3 dcut & ~3
 //   s = 5  D2    draws [dcut1, dcut2)                 draw-X blocks, wave 1
 //   s = 6  D3    draws [dcut2, dcut3)                 draw-Y blocks, wave 0
 //   s = 7  D4    draws [dcut3, dcut4)                 draw-Y blocks, wave 1
-//   s = 8  D5    draws [dcut4, 24)                    draw-X blocks, wave 2
-//          (the episode's rule hashes meanwhile:      draw-X blocks, wave 3)
-//   s = 9  playA plies [0, cut0)                      draw-Y blocks, wave 3
-//   s = 10 playB plies [cut0, cut1)                   play blocks, wave 3
-//   s = 11 playC plies [cut1, cut2)                   play blocks, wave 2
-//   s = 12 playD plies [cut2, cut3)                   play blocks, wave 1
-//   s = 13 playE the rest, final scoring, the board's play blocks, wave 0
+//   s = 8  D5    draws [dcut4, dcut5)                 draw-X blocks, wave 2
+//   s = 9  D6    draws [dcut5, 24)                    draw-X blocks, wave 3
+//   s = 10 playA plies [0, cut0)                      draw-Y blocks, wave 3
+//   s = 11 playB plies [cut0, cut1)                   play blocks, wave 3
+//   s = 12 playC plies [cut1, cut2)                   play blocks, wave 2
+//   s = 13 playD plies [cut2, cut3)                   play blocks, wave 1
+//   s = 14 playE the rest, final scoring, the board's play blocks, wave 0
 //                state, cursor and counters
+// (-DHZ_P2_NDRAW=5: fourteen stages, draw-X wave 3 idle.)
 // Pass 1 never reaches memory: a pass-1 word is a function of the board's key
 // and the constant kInitGen table, so P1 hands on only what pass 2's last
 // step needs (row 1's word after the 624th step), and each pass-2 stage
@@ -58,7 +61,15 @@ namespace {
 // stage uses an input only when its tag names the stage's episode, so a wrong
 // prediction costs time, never results: the stages skip the board and playE
 // plays its whole game from scratch (seeding and drawing in LDS, like
-// k_rollout's unprepared boards).  The results are k_rollout's: the board ends
+// k_rollout's unprepared boards).  The episode's rule hashes live in a ring
+// entry that goes with the slot (same index; P1, which has no slot, writes
+// the entry P2a adopts in the next call) and have no tag of their own: every
+// seeding stage stores its hash rows before its tag, and each tests the
+// previous stage's tag (P2a P1's, P2b P2a's, P2c P2b's), so a slot tagged
+// "seeded for e" has all of e's rows, and the last draw stage's script tag,
+// the one a play stage tests, is given only on such a slot.  An entry is next
+// written by P1 one call after the last play stage read it.
+// The results are k_rollout's: the board ends
 // the call with episode ep's final state, cursor and counters, and
 // games_done / steps_done count that game (its first plies ran in the four
 // calls before, in playA to playD).  In steady state a call does every stage
@@ -91,8 +102,11 @@ constexpr int kP2WinRows = kP2Win + 24;  // LDS rows per window (a scan reads up
 // ran 13.8 us against D1's 10.5, and the cuts became 0, 7, 13, 18
 // (profiles/r05/p2_dcut); five stages: profiles/r07, and profiles/r09 since
 // the first stage loads its window in its first round trip and takes a sixth
-// draw from the last.
-#if HZ_P2_NDRAW == 5
+// draw from the last.  Six stages: profiles/r22 (every scanned set passes
+// tests/test_p2_windows6_cpu.py first).
+#if HZ_P2_NDRAW == 6
+#define HZ_P2_DCUT 0, 5, 9, 13, 17, 20
+#elif HZ_P2_NDRAW == 5
 #define HZ_P2_DCUT 0, 6, 11, 15, 19
 #elif HZ_P2_NDRAW == 4
 #define HZ_P2_DCUT 0, 7, 13, 18
@@ -120,19 +134,25 @@ constexpr int kP2StageDraws = 7;
 #endif
 constexpr int kP2PCut[kP2Play - 1] = {HZ_P2_PCUT};
 // what each wave of a draw-X (first four) and a draw-Y block runs: a draw
-// stage (0 .. kP2Draw - 1), P1, the rule hashes, play stage 0, or nothing.
+// stage (0 .. kP2Draw - 1), P1, play stage 0, or nothing.  (The rule hashes
+// had a wave of their own, draw-X wave 3, until the seeding stages took them:
+// kP2HashCut.)
 // (A play wave brings the ply loop's ~50 KB of code into its CU pair's
 // instruction cache next to the draw code.)
-enum { kWvP1 = 8, kWvHash = 9, kWvPlay = 10, kWvIdle = 15 };
+enum { kWvP1 = 8, kWvPlay = 10, kWvIdle = 15 };
 #ifndef HZ_P2_WAVES
-#if HZ_P2_NDRAW == 5 && HZ_P2_NPLAY == 5
-#define HZ_P2_WAVES 0, 1, 4, 9, 2, 3, 8, 10
+#if HZ_P2_NDRAW == 6 && HZ_P2_NPLAY == 5
+#define HZ_P2_WAVES 0, 1, 4, 5, 2, 3, 8, 10
+#elif HZ_P2_NDRAW == 6
+#define HZ_P2_WAVES 0, 1, 4, 5, 2, 3, 8, 15
+#elif HZ_P2_NDRAW == 5 && HZ_P2_NPLAY == 5
+#define HZ_P2_WAVES 0, 1, 4, 15, 2, 3, 8, 10
 #elif HZ_P2_NDRAW == 5
-#define HZ_P2_WAVES 0, 1, 4, 9, 2, 3, 8, 15
+#define HZ_P2_WAVES 0, 1, 4, 15, 2, 3, 8, 15
 #elif HZ_P2_NPLAY == 5
-#define HZ_P2_WAVES 0, 1, 8, 9, 2, 3, 10, 15
+#define HZ_P2_WAVES 0, 1, 8, 15, 2, 3, 10, 15
 #else
-#define HZ_P2_WAVES 0, 1, 8, 9, 2, 3, 15, 15
+#define HZ_P2_WAVES 0, 1, 8, 15, 2, 3, 15, 15
 #endif
 #endif
 constexpr int kP2Wave[8] = {HZ_P2_WAVES};
@@ -142,10 +162,26 @@ constexpr int p2_wave_count(int code) {
   return c;
 }
 constexpr bool p2_waves_ok() {
-  for (int d = 0; d < 5; d++)
+  for (int d = 0; d < 6; d++)
     if (p2_wave_count(d) != (d < kP2Draw ? 1 : 0)) return false;
-  return p2_wave_count(kWvP1) == 1 && p2_wave_count(kWvHash) == 1 && p2_wave_count(kWvPlay) == (kP2Play == 5 ? 1 : 0);
+  return p2_wave_count(kWvP1) == 1 && p2_wave_count(kWvPlay) == (kP2Play == 5 ? 1 : 0);
 }
+#ifndef HZ_P2_HSPLIT
+// The rule hashes' split over the seeding stages: the first rows of P2a's,
+// P2b's and P2c's ranges (A/B builds).  P1 computes rows [0, first), P2a
+// [first, second), P2b [second, third), P2c the rest, each behind its chain's
+// last step; a range may be empty.  A hash is ~137 cycles.  By the stamps of
+// profiles/r19 P1, P2b and P2c end 7.2-7.5 k cycles before the launch and P2a
+// 4.6 k, with the twist (which follows P2c and is left alone) between, so P1,
+// P2b and P2c share the rows and P2a takes none (profiles/r22).
+#define HZ_P2_HSPLIT 24, 24, 52
+#endif
+constexpr int kP2HashSplit[3] = {HZ_P2_HSPLIT};
+// seeding stage s (0 P1 .. 3 P2c) computes hash rows [kP2HashCut[s], kP2HashCut[s + 1])
+constexpr int kP2HashCut[5] = {0, kP2HashSplit[0], kP2HashSplit[1], kP2HashSplit[2], kRulePlies};
+static_assert(0 <= kP2HashCut[1] && kP2HashCut[1] <= kP2HashCut[2] && kP2HashCut[2] <= kP2HashCut[3] &&
+                  kP2HashCut[3] <= kRulePlies,
+              "HZ_P2_HSPLIT: non-decreasing rows within the table");
 static_assert(p2_waves_ok(), "HZ_P2_WAVES: every stage outside the seed and play blocks on exactly one wave");
 constexpr int kP2MinPlies = 96;   // hz_play max_plies from which pipeline 2 applies (rule games end by ply 80)
 #ifdef HZ_DIAG
@@ -194,8 +230,7 @@ struct P2PlayArgs {          // play stage st
   int fell_lim;              // slot rows it may draw from (HZ_P2_FELL_LIMIT; at most kP2Twist)
   const int32_t *ptag, *pk;  // the last draw stage's script: tag and draws done (written st + 1 calls before)
   const uint64_t *q;         // [4][nrow] the script: the draw stage's (st = 0), else what the previous play stage left of it
-  const uint32_t *h;         // [kRulePlies][nrow] the episode's rule hashes
-  const int32_t *ht;         // [nrow] their episode
+  const uint32_t *h;         // [kRulePlies][nrow] the slot's rule hashes (the episode's whenever ptag names it)
   uint32_t *slot;            // the stream slot and its cursor table
   const int32_t *cur;
   P2Mid in, out;             // the previous play stage's state (st = 0: any valid one, read and discarded) and this one's
@@ -226,8 +261,7 @@ struct P2Args {
   int32_t *p1t_w;
   uint32_t *p2h_w;            // [4][nrow] P2a's
   uint32_t *p3h_w;            // [4][nrow] P2b's
-  uint32_t *h_w;                  // [kRulePlies][nrow] rule hashes (read by play stage st st + 1 calls later)
-  int32_t *ht_w;                  // [nrow] their episode
+  uint32_t *s_h[kP2SDraw];        // [kRulePlies][nrow] the rule hashes' entry of seeding stage s (P1's: the one P2a uses next call)
   int32_t *err;                   // the env's wait-error word
   int spin;                       // spin bound of the twist wave's waits
 };
@@ -402,6 +436,27 @@ __device__ __forceinline__ void p2_keys(uint64_t seed, uint32_t &kA, uint32_t &k
   kB = key1 ? key1 + 1u : key0;
 }
 
+// Seeding stage S's rows of the episode's rule hashes (kP2HashCut), from the
+// seed the stage holds, into the entry that goes with its slot.  Called
+// behind the stage's chain (its last step and last progress publish, so no
+// wave waits for it) and before the stage stores its tag: a slot tagged
+// seeded then has all 80 rows.  The fence keeps the compiler from spreading
+// the multiplies into the chain's last steps.  Plain stores (p2_st): written
+// through (sc1) like the slot stores they measured 0.9 % slower (profiles/r22).
+template <int S>
+__device__ __forceinline__ void p2_hash_rows(const P2Args &a, int b, uint64_t seed) {
+  constexpr int J0 = kP2HashCut[S], J1 = kP2HashCut[S + 1];
+  if constexpr (J0 < J1) {
+    __builtin_amdgcn_sched_barrier(0);
+    const size_t nr = (size_t)a.nrow;
+    const uint64_t rk = rule_key(seed);
+    uint32_t *h = a.s_h[S] + (size_t)J0 * nr + b;
+#pragma unroll 1
+    for (int j = J0; j < J1; j++, h += nr) p2_st(h, rule_h32(rk, j));
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 // P1: all of init_by_array's pass 1 in registers (624 steps of four
 // dependent VALU operations).  No stream slot and no LDS: what leaves is row
 // 1's word after the 624th step (the only pass-1 word pass 2 cannot recompute
@@ -435,8 +490,9 @@ __device__ __forceinline__ uint32_t p1_steps8(const u32x8 &t, uint32_t prev, uin
 }
 __device__ __forceinline__ void p2_p1(const P2Args &a, int b) {
   const int e = a.ep_in[b] + kP2Last;
+  const uint64_t seed = episode_seed(a.seed_base, b, e);
   uint32_t kA, kB;
-  p2_keys(episode_seed(a.seed_base, b, e), kA, kB);
+  p2_keys(seed, kA, kB);
   uint32_t prev = 19650218u;
   const uint32_t *tab = kInitGen.v + 1;
   static_assert(38 * 16 + 1 == 609 && 617 + 8 <= kMT + kInitGenPad, "the last group's read (rows 617-624) within the table's padding");
@@ -462,6 +518,7 @@ __device__ __forceinline__ void p2_p1(const P2Args &a, int b) {
   for (int u = 0; u < 7; u++) prev = p1_step(tb[u], prev, !(u & 1), kA, kB);  // steps 617..623
   // mt[0] = mt[623]; the 624th step at i = 1 (key j = 623 % keylen -> kB)
   a.p1h_w[b] = p1_step(p1_row1(kA, kB), prev, false, kA, kB);
+  p2_hash_rows<0>(a, b, seed);  // (before the tag: P2a, which tests it, vouches for these rows)
   a.p1t_w[b] = e * 8 + 2;
 }
 
@@ -675,8 +732,9 @@ __device__ __forceinline__ void p2_third(const P2Args &a, int b0, int lane, int 
     return;
   }
   uint32_t *slot = a.s_mt[1 + K];
+  const uint64_t seed = episode_seed(a.seed_base, b, e);
   uint32_t kA, kB;
-  p2_keys(episode_seed(a.seed_base, b, e), kA, kB);
+  p2_keys(seed, kA, kB);
   uint32_t prev, first1, row2, q;
   if (K == 0) {
     first1 = act ? hw[0] : 0u;
@@ -736,10 +794,12 @@ __device__ __forceinline__ void p2_third(const P2Args &a, int b0, int lane, int 
       ho[nr + b] = first1;
       ho[2 * nr + b] = row2;
       ho[3 * nr + b] = h.last;
+      p2_hash_rows<1 + K>(a, b, seed);
       a.s_tag[1 + K][b] = e * 8 + 3 + K;
     }
   } else if (ok) {
-    a.s_tag[3][b] = e * 8 + 5;
+    p2_hash_rows<3>(a, b, seed);
+    a.s_tag[3][b] = e * 8 + 5;  // seeded: the earlier stages' tags named e, so all of e's hash rows are in
   }
 }
 
@@ -889,7 +949,7 @@ __device__ __forceinline__ P2PlayArgs p2_play_args(const P2Args &a, int st, int 
   nr = (size_t)a.nrow;
   seed_base = a.seed_base;
   asm volatile("" ::"s"(r.ep), "s"(r.ep_off), "s"(r.g0), "s"(r.g_end), "s"(r.ptag), "s"(r.pk), "s"(r.q), "s"(r.h),
-               "s"(r.ht), "s"(r.slot), "s"(r.cur), "s"(r.in.tag), "s"(r.in.st), "s"(r.in.q), "s"(r.in.i),
+               "s"(r.slot), "s"(r.cur), "s"(r.in.tag), "s"(r.in.st), "s"(r.in.q), "s"(r.in.i),
                "s"(r.out.tag), "s"(r.out.st), "s"(r.out.q), "s"(r.out.i), "s"(n), "s"(nr), "s"(seed_base),
                "s"(r.fell_lim));
   __builtin_amdgcn_sched_barrier(0);
@@ -996,7 +1056,7 @@ __device__ __forceinline__ void p2_draw_stage(const P2Args &a, int b0, int lane,
       win_store();
     }
   }
-  P2_PHASE(28 + stage, t0);  // window staged
+  P2_PHASE(stage < 5 ? 28 + stage : 43, t0);  // window staged (slot 33 is D2's arguments)
   if (!act) return;
   if (!ok) {
     out.tag[b] = -1;
@@ -1035,20 +1095,9 @@ __device__ __forceinline__ void p2_draw_stage(const P2Args &a, int b0, int lane,
   p2_st(&out.tag[b], e * 8 + stage + 1);
 }
 
-// the rule hashes of the last draw stage's episode (read by the play stages
-// in the next kP2Play calls)
-__device__ __forceinline__ void p2_hashes(const P2Args &a, int b) {
-  const size_t nr = (size_t)a.nrow;
-  const int e = a.ep_in[b] + kP2Last - (kP2SPlay - 1);
-  const uint64_t rk = rule_key(episode_seed(a.seed_base, b, e));
-#pragma unroll 1
-  for (int j = 0; j < kRulePlies; j++) p2_st(&a.h_w[(size_t)j * nr + b], rule_h32(rk, j));
-  a.ht_w[b] = e;
-}
-
 // a wave of a draw-X or draw-Y block that runs no play stage (kP2Wave):
 // a draw stage, which stages its own window (the wave's) and reads only it,
-// P1, or the rule hashes
+// or P1
 __device__ __forceinline__ void p2_draw(const P2Args &a, int blk, int code) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int b0 = blk * kBlock;
@@ -1056,8 +1105,6 @@ __device__ __forceinline__ void p2_draw(const P2Args &a, int blk, int code) {
     p2_draw_stage(a, b0, lane, code, w * kP2WinRows * kWinStride);
   } else if (code == kWvP1 && b0 + lane < a.n) {
     p2_p1(a, b0 + lane);
-  } else if (code == kWvHash && b0 + lane < a.n) {
-    p2_hashes(a, b0 + lane);
   }
 }
 
@@ -1097,7 +1144,7 @@ __device__ __forceinline__ void p2_play(const P2Args &a, int blk, int st, bool i
   // The opening is one scalar batch and one vector batch.  Scalar: the
   // stage's record and n, nrow (p2_play_args).  Vector, all issued before the
   // first wait and used only after it: the episode counter, the script's tag
-  // and length, the previous stage's tag, the hashes' episode, the script,
+  // and length, the previous stage's tag, the script,
   // the previous stage's state, and the eight hash rows of the turn pair the
   // stage expects to start with, [g0, g0 + 8) (g0 = the cut before it, an
   // argument; p2_plies takes them as its first pair read ahead, and uses
@@ -1134,7 +1181,7 @@ __device__ __forceinline__ void p2_play(const P2Args &a, int blk, int st, bool i
   for (int j = 0; j < 8; j++) hr[j] = p2_row(r.h, (h0_row + j) * nr);
   p2_fence();
   int ep = p2_at(r.ep, c4);
-  const int ptag = p2_at(r.ptag, c4), nd = p2_at(r.pk, c4), itag = p2_at(r.in.tag, i4), htg = p2_at(r.ht, c4);
+  const int ptag = p2_at(r.ptag, c4), nd = p2_at(r.pk, c4), itag = p2_at(r.in.tag, i4);
   const int id = p2_at(ir[0], i4), ig = p2_at(ir[1], i4), ifc = p2_at(ir[2], i4);
   uint64_t sq[4], ist[6];
 #pragma unroll
@@ -1158,7 +1205,6 @@ __device__ __forceinline__ void p2_play(const P2Args &a, int blk, int st, bool i
     const int g_end = r.g_end;
     const uint64_t sd = episode_seed(seed_base, b, e), rk = rule_key(sd);
     const int mtag = st > 0 ? itag : e;
-    const uint32_t *hs = htg == e ? r.h + b : nullptr;
     State s;
     int g = 0;
     PlayDraw2 draw{{sq[0], sq[1], sq[2], sq[3], 0, nd}, false, MTR(slot, (int)nr, 0, fell_lim), cur + (size_t)nd * nr};
@@ -1173,6 +1219,8 @@ __device__ __forceinline__ void p2_play(const P2Args &a, int blk, int st, bool i
       draw.gm = MTR(slot, (int)nr, ifc >= 0 ? ifc : 0, fell_lim);
     }
     bool prep = ptag == e * 8 + kP2Draw && mtag == e;
+    // (the script's tag vouches for the hash rows too: it is given only on a slot seeded for e)
+    const uint32_t *hs = r.h + b;
     if (last) {
       P2_USE_V((int)prep);
       P2_PHASE(42, t0);

@@ -84,7 +84,7 @@ class BatchedEnv:
         nat.check(nat.lib().hz_env_set_auto_ahead(self._h, int(bool(enable))), "hz_env_set_auto_ahead")
 
     def set_pipeline(self, pipeline):
-        """hz_play's pipeline: 2 (the default) = every game spread over fourteen
+        """hz_play's pipeline: 2 (the default) = every game spread over fifteen
         consecutive calls (k_play2), 1 = chance-ahead (k_rollout); results
         are identical either way (hz_env_set_pipeline)."""
         L = nat.lib()

@@ -214,9 +214,12 @@ int hz_play(hz_env *env, int32_t max_plies, int32_t auto_reset, uint64_t *traj_s
 int hz_env_set_seed_ahead(hz_env *env, int32_t draws);
 /* hz_play's pipeline: 2 (the default; HZ_PIPELINE=1 in the environment at
  * hz_env_create makes 1 the default) = every board's game spread over
- * fourteen consecutive calls, one stage per call (seeding pass 1 in one
- * stage, pass 2 in three, five draw stages, five play stages), all fourteen
- * running in each launch on different episodes; 1 = the chance-ahead
+ * fifteen consecutive calls, one stage per call (seeding pass 1 in one
+ * stage, pass 2 in three, each with its share of the episode's rule hashes,
+ * six draw stages, five play stages), all fifteen running in each launch on
+ * different episodes, so the pipeline's depth is fifteen calls: the
+ * fifteenth call after a (re)start is the first to replay a fully prepared
+ * episode; 1 = the chance-ahead
  * pipeline above.  Same results either way; pipeline 2 applies to calls with
  * auto_reset = 0, no trajectory outputs and max_plies >= 96 (others take
  * pipeline 1).  Returns -1 for a value other than 1 or 2. */

@@ -19,12 +19,12 @@ for pipe in (1, 2):
     env = BatchedEnv(n, device="cuda")
     env.set_pipeline(pipe)
     # (the draw blocks' waves as hz_play2.hpp's default HZ_P2_WAVES places them)
-    names = ({0: "playE", 1: "playD", 2: "playC", 3: "playB", 4: "D1", 5: "D2", 6: "D5", 7: "hashes", 8: "D3",
+    names = ({0: "playE", 1: "playD", 2: "playC", 3: "playB", 4: "D1", 5: "D2", 6: "D5", 7: "D6", 8: "D3",
               9: "D4", 10: "P1", 11: "playA", 12: "P2a", 13: "P2b", 14: "P2c", 15: "twist",
               16: "playA_loaded", 17: "playA_plies", 18: "playB_loaded", 19: "playB_plies",
               20: "playC_loaded", 21: "playC_plies", 22: "playD_loaded", 23: "playD_plies",
               24: "playE_loaded", 25: "playE_plies", 27: "playE_scored",
-              28: "D1_staged", 29: "D2_staged", 30: "D3_staged", 31: "D4_staged", 32: "D5_staged",
+              28: "D1_staged", 29: "D2_staged", 30: "D3_staged", 31: "D4_staged", 32: "D5_staged", 43: "D6_staged",
               35: "twist_go", 36: "twist_it1", 37: "twist_looped",
               # an opening taken apart, on D2 and playE (tools/p2_span.py)
               33: "D2_args", 34: "D2_ep", 26: "D2_tags", 38: "playE_args", 39: "playE_ep", 42: "playE_tags"} if pipe == 2 else

@@ -39,7 +39,7 @@ if ROLE >= 0:
     L.hz_diag_set_role_only(-1)
 s = stamps[:, 40].cpu().numpy().astype(np.int64).reshape(-1, 64)  # [block][16 role + 4 w + k]
 # (the draw blocks' waves as hz_play2.hpp's default HZ_P2_WAVES places them)
-names = {0: ["playE", "playD", "playC", "playB"], 1: ["D1", "D2", "D5", "hashes"], 2: ["D3", "D4", "P1", "playA"],
+names = {0: ["playE", "playD", "playC", "playB"], 1: ["D1", "D2", "D5", "D6"], 2: ["D3", "D4", "P1", "playA"],
          3: ["P2a", "P2b", "P2c", "twist"]}
 rs, re_, ts, te = (s[:, k::4] for k in range(4))  # [block][role * 4 + w]
 valid = rs > 0
@@ -89,7 +89,7 @@ out["cus_used"] = len(per_cu)
 # tools/p2_roles.py's slot names)
 ph = stamps.cpu().numpy().astype(np.int64)
 pnames = {16: "playA_loaded", 17: "playA_plies", 24: "playE_loaded", 25: "playE_plies", 27: "playE_scored",
-          28: "D1_staged", 29: "D2_staged", 30: "D3_staged", 31: "D4_staged", 32: "D5_staged",
+          28: "D1_staged", 29: "D2_staged", 30: "D3_staged", 31: "D4_staged", 32: "D5_staged", 43: "D6_staged",
           35: "twist_go", 36: "twist_it1", 37: "twist_looped",
           # an opening taken apart, on D2 and playE: the stage's arguments in scalar registers, the
           # episode counter's load back, the tags compared (then D2_staged / playE_loaded: every input in hand)
