@@ -122,12 +122,17 @@ __device__ __forceinline__ void gumbel_root_pick(const hz_mcts_args &m, int lane
 // loads), for a walk in the launch whose backup just added to them at L2
 // Returns the leaf's encoder index (b * max_nodes + leaf, wave-uniform), -1
 // when the board is inactive or its leaf is terminal (no network row)
-// Gum: the launch of a handle whose Gumbel gate is on (hz_mcts_set_gumbel):
-// the root's choice is gumbel_root_pick's, every other level's is PUCT's.  A
-// handle with the gate off launches the instantiations without the branch.
-template <bool Fresh = false, bool Gum = false>
+// Root (the root form, chosen by the host from the handle's gates): kRootPuct;
+// kRootGumbel, a handle whose Gumbel gate is on (hz_mcts_set_gumbel): the
+// root's choice is gumbel_root_pick's; kRootForced, a handle whose forced-
+// playout gate is on (hz_mcts_set_forced): at the root of a board whose bit is
+// set the first forced edge wins, ahead of PUCT.  Every other level's choice is
+// PUCT's.  A handle with both gates off launches the instantiations without
+// either branch.
+template <bool Fresh = false, int Root = kRootPuct>
 __device__ __forceinline__ int select_board(const hz_mcts_args &m, int b, int lane, const uint8_t *__restrict__ active,
                                             float cpuct) {
+  constexpr bool Gum = Root == kRootGumbel;
   int32_t *cnt = m.counts + (size_t)b * 4;
   size_t nb = (size_t)b * m.max_nodes, eb = (size_t)b * m.max_edges;
   // the board's flags and its root's edges in one memory round trip (the
@@ -143,6 +148,9 @@ __device__ __forceinline__ int select_board(const hz_mcts_args &m, int b, int la
     sims = m.sims_done[b];  // (written by this board's wave alone, in an earlier launch)
     budget = m.budget[b];
   }
+  // the forced-playout gate's bit of this board (same round trip)
+  bool forced_on = false;
+  if constexpr (Root == kRootForced) forced_on = !m.forced_mask || m.forced_mask[b];
   if (!act || n_nodes == 0 || sims >= budget) {
     if (lane == 0) {
       m.leaf[b] = -1;
@@ -194,8 +202,26 @@ __device__ __forceinline__ int select_board(const hz_mcts_args &m, int b, int la
     const int ns = wave_sum_i(n0 + n1);
     double best = -INFINITY;
     int bi = 0x7fffffff;
+    bool forced = false;  // the forced rule decided this level (wave-uniform)
+    if constexpr (Root == kRootForced) {
+      // the forced-playout rule (include/hz_abi.h): the first root edge that
+      // is owed visits, in ascending edge index (edges 64.. after edges ..63)
+      if (forced_on && d == 0 && ne <= kMaxChildren) {
+        const uint64_t f0 = __ballot(lane < ne && forced_edge(m.forced_k, n0, p0, ns));
+        const uint64_t f1 = __ballot(lane + kWave < ne && forced_edge(m.forced_k, n1, p1, ns));
+        forced = (f0 | f1) != 0ull;
+        if (forced) bi = f0 ? __builtin_ctzll(f0) : kWave + __builtin_ctzll(f1);
+        if (lane == 0) {  // (written by this board's wave alone; cleared by hz_mcts_set_forced)
+          int32_t *fc = m.forced_cnt + (size_t)b * 2;
+          fc[0] += 1;
+          if (forced) fc[1] += 1;
+        }
+      }
+    }
     // (a root has at most kMaxChildren edges: the expansion refuses more)
-    if (Gum && d == 0 && ne <= kMaxChildren) {  // (Gum: the host launches this form only while m.gumbel is set)
+    if (forced) {
+      // bi is the forced edge's index
+    } else if (Gum && d == 0 && ne <= kMaxChildren) {  // (Gum: the host launches this form only while m.gumbel is set)
       // the scores and the root's value were stored by the expansion of node
       // 0, in this launch (Fresh) or an earlier one
       const double *gs = m.g_score + (size_t)b * kMaxChildren;
@@ -224,7 +250,7 @@ __device__ __forceinline__ int select_board(const hz_mcts_args &m, int b, int la
         if (v > best) { best = v; bi = lane + kWave; }
       }
     }
-    wave_argmax(best, bi);
+    if (!forced) wave_argmax(best, bi);
     int sel = e0 + bi;
     if (d >= m.max_depth) {
       if (lane == 0) cnt[3] = 1;
@@ -250,9 +276,9 @@ __device__ __forceinline__ int select_board(const hz_mcts_args &m, int b, int la
   return gidx;
 }
 
-template <bool Gum>
+template <int Root>
 __global__ void __launch_bounds__(kWave) k_select(hz_mcts_args m, const uint8_t *__restrict__ active, float cpuct) {
-  select_board<false, Gum>(m, blockIdx.x, threadIdx.x, active, cpuct);
+  select_board<false, Root>(m, blockIdx.x, threadIdx.x, active, cpuct);
 }
 
 // ------------------------------------------------------------ gather leaves
@@ -413,7 +439,7 @@ __global__ void __launch_bounds__(kGEThreads) k_gather_encode(hz_mcts_args m, in
 constexpr int kFusedMax = 32;
 constexpr int kFusedWaves = 16;
 static_assert(kFusedMax <= 2 * kFusedWaves && kFusedMax <= kWave, "one pair per wave, one gather wave");
-template <bool Gum, bool Sym>
+template <int Root, bool Sym>
 __global__ void __launch_bounds__(kFusedWaves * kWave) k_select_gather_encode(hz_mcts_args m,
                                                                            const uint8_t *__restrict__ active,
                                                                            float cpuct, int32_t *__restrict__ rows,
@@ -425,7 +451,7 @@ __global__ void __launch_bounds__(kFusedWaves * kWave) k_select_gather_encode(hz
   __shared__ int32_t s_count;
   __shared__ uint8_t s_sym[Sym ? kFusedMax : 1];  // Sym: the rows' symmetries (leaf_sym_of), beside gidx_c
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int b = w; b < m.n; b += kFusedWaves) select_board<false, Gum>(m, b, lane, active, cpuct);
+  for (int b = w; b < m.n; b += kFusedWaves) select_board<false, Root>(m, b, lane, active, cpuct);
   __syncthreads();  // every board's leaf_gidx (written by its wave) is visible to the workgroup
   if (w == 0) {
     const int g = lane < m.n ? m.leaf_gidx[lane] : -1;
@@ -1114,7 +1140,8 @@ __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts_
 // barrier that waits for the workgroup's slowest wave (A/B: HZ_SLOT_WAVE)
 // Sym: the leaf-symmetry gate's instantiations (the expansion's policy index; the gathering form encodes the
 // leaf's image: the four plane words permuted before encode_one_values, which works from the six state words)
-template <int Waves, bool Sel, bool Gum, bool Sym, bool Gather = false, int BPW = 1, bool WaveSlot = false>  // Waves: minimum waves per SIMD the register allocation must allow (3: none forced)
+// Root: the root form of the Sel walk (select_board); the expansion itself knows the Gumbel root only
+template <int Waves, bool Sel, int Root, bool Sym, bool Gather = false, int BPW = 1, bool WaveSlot = false>  // Waves: minimum waves per SIMD the register allocation must allow (3: none forced)
 __global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_eu(Waves, 8))) k_expand_backup(hz_mcts_args m, uint32_t *__restrict__ mtw,
                                                          int32_t *__restrict__ mtcur,
                                                          int32_t *__restrict__ wtag,
@@ -1137,7 +1164,7 @@ __global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_e
   const int b = (int)blockIdx.x * BPW + w;
   const bool live = BPW == 1 || b < m.n;
   if (live)
-    expand_backup_board<Gum, Sym>(L, m, mtw, mtcur, wtag, policy, value, noise, eps, one_minus_eps, testing, row_of, prio, b, lane,
+    expand_backup_board<Root == kRootGumbel, Sym>(L, m, mtw, mtcur, wtag, policy, value, noise, eps, one_minus_eps, testing, row_of, prio, b, lane,
                         Sel);
   if (Sel) {
     __builtin_amdgcn_s_setprio(0);
@@ -1149,7 +1176,7 @@ __global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_e
     // cache maintenance) before the walk's loads issue, so the walk does not
     // rest on same-address requests reaching L2 in issue order
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    const int g = live ? select_board<true, Gum>(m, b, lane, active, cpuct) : -1;
+    const int g = live ? select_board<true, Root>(m, b, lane, active, cpuct) : -1;
     // Gather: the leaf's six state words loaded and its row built in the
     // lane's registers (encode_one_values) before the row-slot barriers,
     // under the wait for the workgroup's slowest wave; after them only the
@@ -1330,6 +1357,7 @@ hz_mcts *hz_mcts_create(int32_t n_boards, int32_t max_nodes, int32_t max_depth, 
 
 void hz_mcts_destroy(hz_mcts *m) {
   if (!m) return;
+  m->forced_bufs.release();
   m->leaf_sym_bufs.release();
   m->gumbel_bufs.release();
   m->carry_bufs.release();
@@ -1430,6 +1458,25 @@ int hz_mcts_set_leaf_symmetry(hz_mcts *m, const uint64_t *key) {
   return 0;
 }
 
+int hz_mcts_set_forced(hz_mcts *m, const uint8_t *mask, double k) {
+  if (!m || !(k >= 0.0)) return -1;  // (a NaN fails the comparison)
+  m->forced_k = 0.0;
+  m->forced_mask = nullptr;
+  if (k == 0.0) return 0;
+  if (!m->forced_buf && !request_forced(m->forced_bufs, *m)) {  // first use; freed by hz_mcts_destroy only
+    m->forced_bufs.release();
+    return 1;
+  }
+  if (hipMemsetAsync(m->forced_cnt, 0, (size_t)m->n * 2 * sizeof(int32_t), m->stream)) return 1;
+  if (mask) {
+    if (hipMemcpyAsync(m->forced_buf, mask, (size_t)m->n * sizeof(uint8_t), hipMemcpyDeviceToDevice, m->stream))
+      return 1;
+    m->forced_mask = m->forced_buf;
+  }
+  m->forced_k = k;
+  return 0;
+}
+
 int hz_mcts_leaf_symmetry(hz_mcts *m, uint8_t *out) {
   if (!m || !out) return -1;
   if (!m->leaf_key) return hipMemsetAsync(out, 0, (size_t)m->n, m->stream) == hipSuccess ? 0 : 1;
@@ -1454,8 +1501,11 @@ int hz_mcts_begin(hz_mcts *m, hz_env *env, const uint8_t *active) {
 
 int hz_mcts_select(hz_mcts *m, const uint8_t *active, float cpuct) {
   if (!m) return -1;
-  if (m->gumbel) hipLaunchKernelGGL(k_select<true>, dim3(m->n), dim3(kWave), 0, m->stream, *m, active, cpuct);
-  else hipLaunchKernelGGL(k_select<false>, dim3(m->n), dim3(kWave), 0, m->stream, *m, active, cpuct);
+  const bool forced = m->forced_k > 0.0;
+  if (m->gumbel && forced) return -1;  // (one root form per search)
+  if (m->gumbel) hipLaunchKernelGGL(k_select<kRootGumbel>, dim3(m->n), dim3(kWave), 0, m->stream, *m, active, cpuct);
+  else if (forced) hipLaunchKernelGGL(k_select<kRootForced>, dim3(m->n), dim3(kWave), 0, m->stream, *m, active, cpuct);
+  else hipLaunchKernelGGL(k_select<kRootPuct>, dim3(m->n), dim3(kWave), 0, m->stream, *m, active, cpuct);
   return launch_err();
 }
 
@@ -1478,15 +1528,17 @@ int hz_mcts_select_gather(hz_mcts *m, const uint8_t *active, float cpuct, float 
     return rc ? rc : hz_mcts_gather_leaves(m, board, glob, rows, count);
   }
   if (m->gumbel && m->leaf_key) return -1;  // (the symmetric instantiations exist without the Gumbel root only)
-  if (m->gumbel)
-    hipLaunchKernelGGL((k_select_gather_encode<true, false>), dim3(1), dim3(kFusedWaves * kWave), 0, m->stream, *m,
-                       active, cpuct, rows, count, board, glob);
-  else if (m->leaf_key)
-    hipLaunchKernelGGL((k_select_gather_encode<false, true>), dim3(1), dim3(kFusedWaves * kWave), 0, m->stream, *m,
-                       active, cpuct, rows, count, board, glob);
-  else
-    hipLaunchKernelGGL((k_select_gather_encode<false, false>), dim3(1), dim3(kFusedWaves * kWave), 0, m->stream, *m,
-                       active, cpuct, rows, count, board, glob);
+  const bool forced = m->forced_k > 0.0;
+  if (m->gumbel && forced) return -1;  // (one root form per search)
+#define HZ_SGE_LAUNCH(ROOT, SYM)                                                                                     \
+  hipLaunchKernelGGL((k_select_gather_encode<ROOT, SYM>), dim3(1), dim3(kFusedWaves * kWave), 0, m->stream, *m, active, \
+                     cpuct, rows, count, board, glob)
+  if (m->gumbel) HZ_SGE_LAUNCH(kRootGumbel, false);
+  else if (forced && m->leaf_key) HZ_SGE_LAUNCH(kRootForced, true);
+  else if (forced) HZ_SGE_LAUNCH(kRootForced, false);
+  else if (m->leaf_key) HZ_SGE_LAUNCH(kRootPuct, true);
+  else HZ_SGE_LAUNCH(kRootPuct, false);
+#undef HZ_SGE_LAUNCH
   return launch_err();
 }
 
@@ -1532,6 +1584,8 @@ static int expand_backup(hz_mcts *m, hz_env *env, const float *policy, const flo
                          int32_t *count_prev = nullptr, int add_prev = 0) {
   if (!m || !env || !policy || !value || hz_env_size(env) != m->n) return -1;
   if (m->gumbel && m->leaf_key) return -1;  // (the symmetric instantiations exist without the Gumbel root only)
+  const bool forced = m->forced_k > 0.0;
+  if (m->gumbel && forced) return -1;  // (one root form per search)
   float ome = (float)(1.0 - eps);
   // default: registers capped for four waves per SIMD (38 VGPRs spilled;
   // with the 9.8 KB LDS, 4096 boards fit the chip in one round): 44.7 vs
@@ -1545,31 +1599,41 @@ static int expand_backup(hz_mcts *m, hz_env *env, const float *policy, const flo
   uint32_t *mt = nullptr;
   int32_t *mt_pos = nullptr, *win_tag = nullptr;
   if (hz_env_stream_ptrs(env, &mt, &mt_pos, &win_tag)) return 1;
-#define HZ_EXPAND_LAUNCH_G(W, S, GUM, SYM, G, BP, ...)                                                          \
-  hipLaunchKernelGGL((k_expand_backup<W, S, GUM, SYM, G, BP, ##__VA_ARGS__>), dim3((m->n + (BP) - 1) / (BP)), dim3(kWave * (BP)), \
+#define HZ_EXPAND_LAUNCH_G(W, S, ROOT, SYM, G, BP, ...)                                                         \
+  hipLaunchKernelGGL((k_expand_backup<W, S, ROOT, SYM, G, BP, ##__VA_ARGS__>), dim3((m->n + (BP) - 1) / (BP)), dim3(kWave * (BP)), \
                      0, m->stream, *m, mt, mt_pos, win_tag, policy, value, noise, eps, ome, testing, slot, prio, active, cpuct, \
                      board, glob, rows, count_out, count_prev, add_prev)
-  // (the Gumbel and leaf-symmetry gates pick the instantiation: with a gate off the kernels carry none of its code)
-#define HZ_EXPAND_LAUNCH(W, S, G, BP, ...)                                               \
-  do {                                                                                   \
-    if (m->gumbel) HZ_EXPAND_LAUNCH_G(W, S, true, false, G, BP, ##__VA_ARGS__);           \
-    else if (m->leaf_key) HZ_EXPAND_LAUNCH_G(W, S, false, true, G, BP, ##__VA_ARGS__);    \
-    else HZ_EXPAND_LAUNCH_G(W, S, false, false, G, BP, ##__VA_ARGS__);                    \
+  // (the Gumbel, forced-playout and leaf-symmetry gates pick the instantiation: with a gate off the kernels carry
+  // none of its code; the forced rule lives in the walk, so the forms without a select have no forced instantiation)
+#define HZ_EXPAND_LAUNCH_NOSEL(W)                                                             \
+  do {                                                                                        \
+    if (m->gumbel) HZ_EXPAND_LAUNCH_G(W, false, kRootGumbel, false, false, 1);                 \
+    else if (m->leaf_key) HZ_EXPAND_LAUNCH_G(W, false, kRootPuct, true, false, 1);             \
+    else HZ_EXPAND_LAUNCH_G(W, false, kRootPuct, false, false, 1);                             \
+  } while (0)
+#define HZ_EXPAND_LAUNCH(W, G, BP, ...)                                                            \
+  do {                                                                                             \
+    if (m->gumbel) HZ_EXPAND_LAUNCH_G(W, true, kRootGumbel, false, G, BP, ##__VA_ARGS__);           \
+    else if (forced && m->leaf_key) HZ_EXPAND_LAUNCH_G(W, true, kRootForced, true, G, BP, ##__VA_ARGS__); \
+    else if (forced) HZ_EXPAND_LAUNCH_G(W, true, kRootForced, false, G, BP, ##__VA_ARGS__);         \
+    else if (m->leaf_key) HZ_EXPAND_LAUNCH_G(W, true, kRootPuct, true, G, BP, ##__VA_ARGS__);       \
+    else HZ_EXPAND_LAUNCH_G(W, true, kRootPuct, false, G, BP, ##__VA_ARGS__);                       \
   } while (0)
   const bool gat = sel && count_out;
   if (waves == 4) {
-    if (gat && gather_bpw() == 8) HZ_EXPAND_LAUNCH(4, true, true, 8);
-    else if (gat && wave_slot) HZ_EXPAND_LAUNCH(4, true, true, kGatherBPW, true);
-    else if (gat) HZ_EXPAND_LAUNCH(4, true, true, kGatherBPW);
-    else if (sel) HZ_EXPAND_LAUNCH(4, true, false, 1);
-    else HZ_EXPAND_LAUNCH(4, false, false, 1);
+    if (gat && gather_bpw() == 8) HZ_EXPAND_LAUNCH(4, true, 8);
+    else if (gat && wave_slot) HZ_EXPAND_LAUNCH(4, true, kGatherBPW, true);
+    else if (gat) HZ_EXPAND_LAUNCH(4, true, kGatherBPW);
+    else if (sel) HZ_EXPAND_LAUNCH(4, false, 1);
+    else HZ_EXPAND_LAUNCH_NOSEL(4);
   } else {
-    if (gat && gather_bpw() == 8) HZ_EXPAND_LAUNCH(3, true, true, 8);
-    else if (gat) HZ_EXPAND_LAUNCH(3, true, true, kGatherBPW);
-    else if (sel) HZ_EXPAND_LAUNCH(3, true, false, 1);
-    else HZ_EXPAND_LAUNCH(3, false, false, 1);
+    if (gat && gather_bpw() == 8) HZ_EXPAND_LAUNCH(3, true, 8);
+    else if (gat) HZ_EXPAND_LAUNCH(3, true, kGatherBPW);
+    else if (sel) HZ_EXPAND_LAUNCH(3, false, 1);
+    else HZ_EXPAND_LAUNCH_NOSEL(3);
   }
 #undef HZ_EXPAND_LAUNCH
+#undef HZ_EXPAND_LAUNCH_NOSEL
 #undef HZ_EXPAND_LAUNCH_G
   return launch_err();
 }

@@ -74,6 +74,11 @@ struct hz_mcts_args {
   uint64_t *leaf_key_buf;  // [n] owned; fixed address (a captured simulation stays valid while its contents change)
   uint8_t *leaf_g;         // [n] by board: the g of leaf_gidx's leaves, for the per-board encoder (hz_mcts_encode_leaves)
   uint8_t *row_g;          // [n] by gathered row, beside gidx_c: the g of k_gather's rows, for the layered encoder
+  // forced playouts at the root (hz_mcts_set_forced; allocated by its first call): forced_k == 0: gate off
+  double forced_k;         // KataGo's k; a captured simulation holds it by value
+  uint8_t *forced_mask;    // nullptr: every board, else == forced_buf
+  uint8_t *forced_buf;     // [n] owned; fixed address (a captured simulation stays valid while its contents change)
+  int32_t *forced_cnt;     // [n][2] this search's root selections under the gate, and those the forced rule decided
 };
 
 namespace hz_tree {
@@ -84,7 +89,7 @@ constexpr int kChildSlots = 128;  // two per lane (loop bound: lanes c and c + 6
 constexpr int32_t kGumbelTableMax = (kMaxChildren + 1) * 32767;  // entries of the largest table hz_mcts_set_gumbel admits
 
 // ------------------------------------------------------ the handle's buffers
-// The four groups of a handle's device buffers, each requested whole from its
+// The five groups of a handle's device buffers, each requested whole from its
 // own owner (hz_host.hpp's DevBufsT) and freed by that owner's release(): a
 // request after a failed one does nothing, so each list ends in one check.  A
 // buffer's address is fixed while its group lives (captured simulations bake
@@ -151,6 +156,16 @@ bool request_leaf_sym(Bufs &o, hz_mcts_args &a) {
   return o.ok;
 }
 
+// Forced playouts (the first hz_mcts_set_forced): the mask and the per-board
+// counters, cleared on the handle's stream.
+template <class Bufs>
+bool request_forced(Bufs &o, hz_mcts_args &a) {
+  const size_t n = (size_t)a.n;
+  o.get(a.forced_buf, n * sizeof(uint8_t), 0, (void *)a.stream);
+  o.get(a.forced_cnt, n * 2 * sizeof(int32_t), 0, (void *)a.stream);
+  return o.ok;
+}
+
 }  // namespace hz_tree
 
 // ---------------------------------------------------------------- HIP only
@@ -164,7 +179,7 @@ bool request_leaf_sym(Bufs &o, hz_mcts_args &a) {
 // the kernel takes the hz_mcts_args part) and the owners of their buffers.
 // Made by new, never moved: the owners keep the addresses of its pointers.
 struct hz_mcts : hz_mcts_args {
-  hz_host::DevBufs base_bufs, carry_bufs, gumbel_bufs, leaf_sym_bufs;
+  hz_host::DevBufs base_bufs, carry_bufs, gumbel_bufs, leaf_sym_bufs, forced_bufs;
 };
 
 namespace hz_tree {
@@ -294,6 +309,16 @@ __device__ __forceinline__ void gumbel_sigma(const hz_mcts_args &m, int lane, in
   const double scale = __dmul_rn(__dadd_rn(m.g_c_visit, (double)max_n), m.g_c_scale);
   sg0 = in0 ? __dmul_rn(scale, __ddiv_rn(__dsub_rn(c0, mn), den)) : 0.0;
   sg1 = in1 ? __dmul_rn(scale, __ddiv_rn(__dsub_rn(c1, mn), den)) : 0.0;
+}
+
+// ------------------------------------------------------------ forced playouts
+// The root forms of the walk (select_board's template argument): PUCT, the
+// Gumbel root, or PUCT behind the forced-playout rule of hz_mcts_set_forced.
+constexpr int kRootPuct = 0, kRootGumbel = 1, kRootForced = 2;
+// Root edge e is forced iff N_e > 0 and (double)(N_e N_e) < (k (double)P_e)
+// (double)t: an exact integer product against two fp64 products in that order.
+__device__ __forceinline__ bool forced_edge(double k, int n, float p, int t) {
+  return n > 0 && (double)((long long)n * (long long)n) < __dmul_rn(__dmul_rn(k, (double)p), (double)t);
 }
 
 // A node's edge range [e0, e0 + ne) when it lies within the board's n_edges

@@ -373,6 +373,7 @@ int hz_mcts_advance(hz_mcts *m, hz_env *env, const int16_t *action, const uint8_
 int hz_mcts_begin_carried(hz_mcts *m, hz_env *env, const uint8_t *active, const double *noise, double eps,
                           int32_t testing) {
   if (!m || !env || hz_env_size(env) != m->n) return -1;
+  if (m->forced_k > 0.0) return -1;  // (forced playouts start from an empty tree: hz_mcts_set_forced)
   if (!m->carry) return hz_mcts_begin(m, env, active);  // never advanced: nothing to carry
   hipLaunchKernelGGL(k_begin_carried, dim3(m->n), dim3(kWave), 0, m->stream, *m, hz_env_state_ptr(env), m->n, active,
                      noise, eps, (float)(1.0 - eps), testing);

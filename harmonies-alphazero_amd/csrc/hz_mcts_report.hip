@@ -237,6 +237,87 @@ __global__ void __launch_bounds__(kWave) k_gumbel_result(hz_mcts_args m, int16_t
   }
 }
 
+// hz_mcts_pruned_visits: policy target pruning (include/hz_abi.h states the
+// rule; KataGo's, with the select's own arithmetic).  One wave per board, two
+// root edges per lane as in the walk.  The best edge e* (the first with the
+// largest N) sets bound = q + U at its own count; every other visited edge
+// gives back up to nf = floor(sqrt((k P) t)) visits, one at a time, while
+// its q + U at the reduced count stays below the bound, and goes to 0 when
+// a reduction leaves it at most one visit.  The lane's loop runs at most
+// min(nf, N) <= sqrt(k t) steps.  A board whose bit is clear, or without a
+// visit, gets k_result's row; a board without a tree zeros.
+__global__ void __launch_bounds__(kWave) k_pruned_visits(hz_mcts_args m, float cpuct, int32_t *__restrict__ visits) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int32_t *out = visits + (size_t)b * kActions;
+  for (int a = lane; a < kActions; a += kWave) out[a] = 0;
+  __syncthreads();  // the zeros before the edges' entries (one wave: ordering only)
+  const int32_t *cnt = m.counts + (size_t)b * 4;
+  const int n_nodes = cnt[0], n_edges = cnt[1];
+  int e0 = 0;
+  const int ne = checked_counts(m, n_nodes, n_edges) ? checked_edges(m, (size_t)b * m.max_nodes, 0, n_edges, e0) : 0;
+  if (ne == 0) return;
+  const size_t eb = (size_t)b * m.max_edges + e0;
+  const bool in0 = lane < ne, in1 = lane + kWave < ne;
+  int n0 = 0, n1 = 0, a0 = -1, a1 = -1;
+  double w0 = 0.0, w1 = 0.0;
+  float p0 = 0.f, p1 = 0.f;
+  if (in0) {
+    n0 = m.edge_n[eb + lane];
+    w0 = m.edge_w[eb + lane];
+    p0 = m.edge_p[eb + lane];
+    a0 = m.edge_action[eb + lane];
+  }
+  if (in1) {
+    n1 = m.edge_n[eb + lane + kWave];
+    w1 = m.edge_w[eb + lane + kWave];
+    p1 = m.edge_p[eb + lane + kWave];
+    a1 = m.edge_action[eb + lane + kWave];
+  }
+  const int t = wave_sum_i(n0 + n1);
+  const bool on = (!m.forced_mask || m.forced_mask[b]) && t > 0;
+  if (on) {
+    const double s = __dsqrt_rn(t > 1 ? (double)t : 1.0);
+    auto u_of = [&](float p, int x) {
+      return __ddiv_rn(__dmul_rn((double)__fmul_rn(cpuct, p), s), (double)(1 + x));
+    };
+    double best = -INFINITY;  // a visit count as a double (exact)
+    int bi = 0x7fffffff;
+    if (in0) {
+      best = (double)n0;
+      bi = lane;
+    }
+    if (in1 && (double)n1 > best) {
+      best = (double)n1;
+      bi = lane + kWave;
+    }
+    wave_argmax(best, bi);
+    const int src = bi & (kWave - 1);
+    const bool hi = bi >= kWave;
+    const int nb = __shfl(hi ? n1 : n0, src);
+    const double wb = __shfl(hi ? w1 : w0, src);
+    const float pb = __shfl(hi ? p1 : p0, src);
+    const double bound = __dadd_rn(nb ? __ddiv_rn(wb, (double)nb) : 0.0, u_of(pb, nb));
+    auto prune = [&](int e, int n, double w, float p) {
+      if (e == bi || n <= 0) return n;
+      const double q = __ddiv_rn(w, (double)n);
+      // nf as an int, at most n (a NaN or a negative root gives 0)
+      const double rt = floor(__dsqrt_rn(__dmul_rn(__dmul_rn(m.forced_k, (double)p), (double)t)));
+      const int lim = rt >= (double)n ? n : (rt > 0.0 ? (int)rt : 0);
+      int r = 0;
+      for (int j = 1; j <= lim; j++) {
+        if (!(__dadd_rn(q, u_of(p, n - j)) < bound)) break;
+        r = j;
+      }
+      const int left = n - r;
+      return r > 0 && left <= 1 ? 0 : left;
+    };
+    n0 = prune(lane, n0, w0, p0);
+    n1 = prune(lane + kWave, n1, w1, p1);
+  }
+  if (in0 && a0 >= 0 && a0 < kActions) out[a0] = n0;
+  if (in1 && a1 >= 0 && a1 < kActions) out[a1] = n1;
+}
+
 // Sum of every edge's visit count over the board's tree: each simulation
 // adds one visit to every edge of its path in back_fill (MCTS.py:220-266),
 // so this is the number of edge levels the searches walked (the path-walk
@@ -318,6 +399,19 @@ int hz_mcts_gumbel_result(hz_mcts *m, int16_t *action, float *pi, double *value)
   if (!m || !action || !pi || !value || !m->gumbel) return -1;
   hipLaunchKernelGGL(k_gumbel_result, dim3(m->n), dim3(kWave), 0, m->stream, *m, action, pi, value);
   return launch_err();
+}
+
+int hz_mcts_pruned_visits(hz_mcts *m, float cpuct, int32_t *visits) {
+  if (!m || !visits || !(m->forced_k > 0.0)) return -1;
+  hipLaunchKernelGGL(k_pruned_visits, dim3(m->n), dim3(kWave), 0, m->stream, *m, cpuct, visits);
+  return launch_err();
+}
+
+int hz_mcts_forced_counts(hz_mcts *m, int32_t *out) {
+  if (!m || !out || !(m->forced_k > 0.0)) return -1;
+  return hipMemcpyAsync(out, m->forced_cnt, (size_t)m->n * 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, m->stream)
+             ? 1
+             : 0;
 }
 
 int hz_mcts_path_edges(hz_mcts *m, int64_t *out) {

@@ -83,6 +83,9 @@ _SIGS = {
     "hz_leaf_sym_keys": ([_c.c_int32, _c.c_uint64, _c.c_uint64, _c.c_uint64, _vp, _vp], _c.c_int),
     "hz_mcts_set_leaf_symmetry": ([_vp, _vp], _c.c_int),
     "hz_mcts_leaf_symmetry": ([_vp, _vp], _c.c_int),
+    "hz_mcts_set_forced": ([_vp, _vp, _c.c_double], _c.c_int),
+    "hz_mcts_pruned_visits": ([_vp, _c.c_float, _vp], _c.c_int),
+    "hz_mcts_forced_counts": ([_vp, _vp], _c.c_int),
     "hz_mcts_advance": ([_vp, _vp, _vp, _vp, _c.c_int32, _vp], _c.c_int),
     "hz_mcts_begin_carried": ([_vp, _vp, _vp, _vp, _c.c_double, _c.c_int32], _c.c_int),
     "hz_mcts_stats": ([_vp, _vp], _c.c_int),

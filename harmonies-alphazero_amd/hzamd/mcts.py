@@ -34,6 +34,7 @@ from .env import ACTION_SIZE
 MAX_CHILDREN = 69
 MAX_NODES_END = 1 << 24  # hz_mcts_create refuses max_nodes from here on (an edge id must fit 24 bits)
 DEFAULT_MAX_DEPTH = 192
+FORCED_K_DEFAULT = 2.0  # KataGo's k (forced playouts), not tuned here
 GUMBEL_DEFAULT = {"max_considered": 16, "c_visit": 50.0, "c_scale": 1.0}  # the paper's setting, not tuned here
 
 
@@ -134,9 +135,9 @@ class BatchedMCTS:
         # boards: only then can a row lie past them, and _finish() reads the
         # handle's error word (hz_mcts_set_row_cap)
         self._cap_risk = False
-        # (budget gate on, root-noise mask on, the Gumbel gate's settings or None, leaf-symmetry gate on), as last
-        # set by search()
-        self._gate = (False, False, None, False)
+        # (budget gate on, root-noise mask on, the Gumbel gate's settings or None, leaf-symmetry gate on, the forced
+        # gate's (k, mask given) or None), as last set by search()
+        self._gate = (False, False, None, False, None)
         self._leaf_sym = torch.zeros(self.n, dtype=torch.uint8, device=d)  # leaf_symmetries()' report
         self._gumbel_tables = {}  # (max_considered, n_root) -> the device table (built once per shape)
         # tree reuse (advance() / search(carry=True)): advance's info rows, and
@@ -374,13 +375,64 @@ class BatchedMCTS:
         nat.check(nat.lib().hz_mcts_leaf_symmetry(self._h, nat.ptr(self._leaf_sym)), "hz_mcts_leaf_symmetry")
         return self._leaf_sym
 
-    def _set_gate(self, budget, root_noise, gumbel=None, leaf_sym=False):
+    def _set_forced(self, forced, forced_k):
+        """The forced-playout gate of the search about to begin (forced None
+        or False: off), the mask copied into the handle in stream order;
+        returns (the gate's k, whether a mask was given), which is what a
+        captured simulation holds of it by value, or None."""
+        L = nat.lib()
+        if forced is None or forced is False:
+            if hasattr(L, "hz_mcts_set_forced"):  # (an older A/B build named by HZ_LIB has no gate to clear)
+                nat.check(L.hz_mcts_set_forced(self._h, None, 0.0), "hz_mcts_set_forced")
+            return None
+        k = FORCED_K_DEFAULT if forced_k is None else float(forced_k)
+        if not k > 0.0:
+            raise ValueError(f"forced_k {forced_k!r}: not above 0")
+        mask = None
+        if forced is not True:
+            if not torch.is_tensor(forced) or forced.dtype not in (torch.bool, torch.uint8):
+                raise ValueError("forced: True, or a bool / uint8 tensor of one flag per board")
+            if forced.shape != (self.n,):
+                raise ValueError(f"forced of shape {tuple(forced.shape)}, not ({self.n},)")
+            mask = forced.to(device=self.device, dtype=torch.uint8).contiguous()
+        nat.check(L.hz_mcts_set_forced(self._h, nat.ptr(mask), k), "hz_mcts_set_forced")
+        return k, mask is not None
+
+    def pruned_visits(self, cpuct):
+        """After search(forced=) (hz_mcts_pruned_visits): device int32 [n, 143],
+        the root's visits with the visits that were only forced taken back
+        (policy target pruning, whose rule include/hz_abi.h states; cpuct: the
+        search's).  A board whose forced bit was clear has its result() row, a
+        board without a tree zeros.  The handle's own tensor, rewritten by the
+        next call."""
+        if self._gate[4] is None:
+            raise ValueError("pruned_visits() after a search without forced=")
+        r = self._report.get("pruned")
+        if r is None:
+            r = self._report["pruned"] = self._zeros(torch.int32, self.n, ACTION_SIZE)
+        nat.check(nat.lib().hz_mcts_pruned_visits(self._h, float(cpuct), nat.ptr(r)), "hz_mcts_pruned_visits")
+        return r
+
+    def forced_counts(self):
+        """After search(forced=) (hz_mcts_forced_counts): device int32 [n, 2],
+        per board the root selections of the search under the gate and those
+        the forced rule decided.  The handle's own tensor."""
+        if self._gate[4] is None:
+            raise ValueError("forced_counts() after a search without forced=")
+        r = self._report.get("forced_counts")
+        if r is None:
+            r = self._report["forced_counts"] = self._zeros(torch.int32, self.n, 2)
+        nat.check(nat.lib().hz_mcts_forced_counts(self._h, nat.ptr(r)), "hz_mcts_forced_counts")
+        return r
+
+    def _set_gate(self, budget, root_noise, gumbel=None, leaf_sym=False, forced=None):
         """The budget gate and the root-noise mask of the search about to
         begin (None: off), copied into the handle in stream order; gumbel:
         the Gumbel gate's settings as _set_gumbel returned them; leaf_sym:
-        whether the leaf-symmetry gate is on (_set_leaf_symmetry)."""
+        whether the leaf-symmetry gate is on (_set_leaf_symmetry); forced: the
+        forced gate's (k, mask given) as _set_forced returned it."""
         L = nat.lib()
-        self._gate = (self._gate[0], self._gate[1], gumbel, leaf_sym)
+        self._gate = (self._gate[0], self._gate[1], gumbel, leaf_sym, forced)
         if budget is None and root_noise is None and not hasattr(L, "hz_mcts_set_budget"):
             return  # (an older A/B build named by HZ_LIB: it has no gate to clear)
         if budget is not None:
@@ -393,7 +445,7 @@ class BatchedMCTS:
                 raise ValueError(f"root_noise of shape {tuple(root_noise.shape)}, not ({self.n},)")
         nat.check(L.hz_mcts_set_budget(self._h, nat.ptr(budget)), "hz_mcts_set_budget")
         nat.check(L.hz_mcts_set_root_noise_mask(self._h, nat.ptr(root_noise)), "hz_mcts_set_root_noise_mask")
-        self._gate = (budget is not None, root_noise is not None, gumbel, leaf_sym)
+        self._gate = (budget is not None, root_noise is not None, gumbel, leaf_sym, forced)
 
     def stats(self):
         nat.check(nat.lib().hz_mcts_stats(self._h, nat.ptr(self.counts)), "hz_mcts_stats")
@@ -520,7 +572,8 @@ class BatchedMCTS:
 
     def search(self, evaluator, cpuct, active=None, noise=None, eps=0.25, testing=True, sims=None,
                gather=True, graph=False, max_rows=None, budget=None, root_noise=None, tail=None, carry=False,
-               root=None, gumbel=None, max_considered=None, c_visit=None, c_scale=None, leaf_symmetry=None):
+               root=None, gumbel=None, max_considered=None, c_visit=None, c_scale=None, leaf_symmetry=None,
+               forced=None, forced_k=None):
         """get_best_action_and_pi's simulation loop (MCTS.py:288-352) for every
         active board; returns root visit counts int32 [n, 143].
 
@@ -579,7 +632,24 @@ class BatchedMCTS:
         through g; the walk, the children, the draws and the backup are what
         they are without it.  In every search form, with active=, budget=,
         root_noise=, tail= and max_rows=; not with root="gumbel" or
-        carry=True (ValueError).  A search without it clears the gate."""
+        carry=True (ValueError).  A search without it clears the gate.
+
+        forced=True, or a bool / uint8 [n] mask, with forced_k=k (default 2,
+        KataGo's): forced playouts at the root of the boards whose flag is
+        set (hz_mcts_set_forced states the rule): a root child that has been
+        visited is owed sqrt(k P sum N) visits and is chosen ahead of PUCT
+        until it has them; everything else is the search it is without it.
+        pruned_visits(cpuct) then has the visits with the merely forced ones
+        taken back; the visits returned are the raw ones.  In every search
+        form, with active=, budget=, root_noise=, tail=, max_rows= and
+        leaf_symmetry=; not with root="gumbel" or carry=True (ValueError).  A
+        search without it clears the gate."""
+        if forced is False:
+            forced = None
+        if forced is not None and (root == "gumbel" or carry):
+            raise ValueError("forced= does not combine with root='gumbel' or carry=True")
+        if forced is None and forced_k is not None:
+            raise ValueError("forced_k= goes with forced=")
         if leaf_symmetry is not None and (root == "gumbel" or carry):
             raise ValueError("leaf_symmetry= does not combine with root='gumbel' or carry=True")
         if root not in (None, "gumbel"):
@@ -597,7 +667,7 @@ class BatchedMCTS:
         self._sync()
         self._set_gate(budget, root_noise, self._set_gumbel(
             gumbel, self.num_simulations if sims is None else int(sims), max_considered, c_visit, c_scale),
-            self._set_leaf_symmetry(leaf_symmetry))
+            self._set_leaf_symmetry(leaf_symmetry), self._set_forced(forced, forced_k))
         self._edges_base = self._path_base = None
         if carry:
             self.begin_carried(active, noise, eps, testing)
@@ -623,8 +693,9 @@ class BatchedMCTS:
             # search with the same settings (the drop-in's one search per move);
             # only without an `active` mask, whose tensor the graph would bake in
             gk = getattr(evaluator, "graph_key", None)
-            # (a capture holds the handle by value: whether each gate and the
-            # mask are on, and each step's row cap, belong to the key)
+            # (a capture holds the handle by value: whether each gate and each
+            # mask, the forced gate's too, are on, and each step's row cap,
+            # belong to the key)
             head = min(max(s0 - 1, 0), total - 1)  # replays before the tail (simulation 0 ran eagerly)
             steps = ((max_rows, head), (tail_rows, total - 1 - head))
             key = None if gk is None or active is not None else (

@@ -45,6 +45,16 @@ one of the board's four symmetries, drawn per board and node from the move's
 key (NoiseSource.leaf_symmetry, BatchedMCTS.search(leaf_symmetry=), whose rule
 include/hz_abi.h states).  With playout caps; not with tree_reuse or
 root_policy "gumbel".
+
+Forced playouts and policy target pruning (no reference counterpart; config
+key `forced_playouts`: KataGo's k, absent by default, with `prune_targets`,
+default True): on the boards searched in full (every active board without
+playout caps) a visited root child is owed sqrt(k P sum N) visits
+(BatchedMCTS.search(forced=), whose rule include/hz_abi.h states); the move
+is chosen from the raw visits (kept in `last_visits`), and the visits move()
+returns and the records hold are the pruned ones
+(BatchedMCTS.pruned_visits).  Off while `testing`; with playout caps and
+leaf symmetries; not with tree_reuse or root_policy "gumbel".
 """
 import torch
 
@@ -166,6 +176,22 @@ class SelfPlay:
             raise ValueError(f"leaf_symmetry {self.leaf_symmetry!r}: not 'random'")
         if self.leaf_symmetry and (self.tree_reuse or policy == "gumbel"):
             raise ValueError("leaf_symmetry does not combine with tree_reuse or root_policy 'gumbel'")
+        # forced playouts: on when forced_playouts (k) is given; the records then hold the pruned visits
+        fk = self.cfg.get("forced_playouts")
+        self.forced_k = None
+        if fk is not None:
+            if isinstance(fk, bool) or not isinstance(fk, (int, float)) or not float(fk) > 0.0:
+                raise ValueError(f"forced_playouts {fk!r}: not a number above 0 (KataGo's k)")
+            if self.tree_reuse or policy == "gumbel":
+                raise ValueError("forced_playouts does not combine with tree_reuse or root_policy 'gumbel'")
+            self.forced_k = float(fk)
+        prune = self.cfg.get("prune_targets")
+        if prune is not None and not isinstance(prune, bool):
+            raise ValueError(f"prune_targets {prune!r}: not True or False")
+        if prune and self.forced_k is None:
+            raise ValueError("prune_targets goes with forced_playouts")
+        self.prune_targets = self.forced_k is not None and prune is not False
+        self.last_visits = None  # int32 [n, 143] of the last move(): the raw visits the move was chosen from
         self.last_gumbel = None  # gumbel_result() of the last move(), with the Gumbel root
         max_nodes = int(pool * (1 + MAX_CHILDREN * self.cfg["num_simulations"])) if self.tree_reuse else None
         self.mcts = BatchedMCTS(self.env, self.cfg["num_simulations"], max_nodes=max_nodes, exact_keys=exact_keys)
@@ -253,10 +279,15 @@ class SelfPlay:
             if self.tree_reuse == "topup":
                 budget = topup_budgets(carried, cfg["num_simulations"], self.reuse_min_sims)
         keys = self.noise.leaf_symmetry(step, n) if self.leaf_symmetry else None
+        # forced playouts: the boards searched in full (every searched board without caps); off while testing
+        forced = None
+        if self.forced_k is not None and not testing:
+            forced = full if full is not None else True
         v = self.mcts.search(self.evaluator, cfg["cpuct"], active=active, noise=noise,
                              eps=cfg["dirichlet_epsilon"], testing=testing, max_rows=max(1, bound),
                              budget=budget, root_noise=full, tail=tail, carry=self.tree_reuse is not None,
-                             leaf_symmetry=keys)
+                             leaf_symmetry=keys, forced=forced, forced_k=self.forced_k if forced is not None else None)
+        self.last_visits = v
         if self.keep_root_value:
             self.last_root_value = self.mcts.root_edges()["value"]
         self.check_steps()  # the previous move's step, done long before this search runs
@@ -268,6 +299,8 @@ class SelfPlay:
         if self.keep_noise:
             self.noise_log.append((noise.clone(), u.clone(), act.clone()))
         self._step(act, active, step)
+        if forced is not None and self.prune_targets:  # the move came from the raw visits; the records get the pruned
+            v = self.mcts.pruned_visits(cfg["cpuct"])
         return st, v, active
 
     def _gumbel_move(self, st, active, bound):

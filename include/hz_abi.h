@@ -534,6 +534,58 @@ int hz_mcts_gumbel_result(hz_mcts *mcts, int16_t *action, float *pi, double *val
 int hz_leaf_sym_keys(int32_t n, uint64_t seed, uint64_t board_base, uint64_t move, uint64_t *out, void *stream);
 int hz_mcts_set_leaf_symmetry(hz_mcts *mcts, const uint64_t *key);
 int hz_mcts_leaf_symmetry(hz_mcts *mcts, uint8_t *out);
+/* ---- forced playouts at the root, policy target pruning ------------------------
+ * No reference counterpart ("Accelerating Self-Play Learning in Go", Wu, 2019:
+ * KataGo's companions of playout-cap randomization): the build's defined
+ * behaviour, off by default, pinned by tests/mcts_forced_model.py.  A root child
+ * that has been visited at all is owed sqrt(k P sum N) visits and is chosen ahead
+ * of PUCT until it has them, so a move the Dirichlet noise pushed up is confirmed
+ * or refuted; after the search the visits that were only forced are taken back.
+ * Both rules are root-only and use IEEE fp64 multiply, divide, add and sqrt, one
+ * operation at a time, none fused, on numbers the walk already holds.
+ *
+ * hz_mcts_set_forced: k > 0 turns the gate on; mask[n] (device uint8) is copied in
+ * stream order into a buffer the handle owns (allocated by the first call, its
+ * address fixed until hz_mcts_destroy); mask == NULL: every board.  k == 0 turns
+ * the gate off (the default); a negative or NaN k returns -1.  Call it before the
+ * hz_mcts_begin of a search.  k, whether the gate is on and whether the mask is
+ * NULL are held by value in a captured simulation (a capture made with a mask
+ * reads the handle's buffer, one made without reads none), which is to be
+ * replayed only under the settings it was captured with; the mask's contents may
+ * change between replays.  The gate does not combine with the Gumbel root (with both on,
+ * every call that selects or expands returns -1 and enqueues nothing) or with a
+ * carried tree (hz_mcts_begin_carried returns -1); it combines with budgets, the
+ * root-noise mask, the row cap and leaf symmetries.
+ *   Forced select: level 0 of the walk, a board whose bit is set and whose root
+ * has 1 <= ne <= 69 edges; t = sum N over the root's edges.  Edge e is forced iff
+ * N_e > 0 and (double)(N_e * N_e) < (k * (double)P_e) * (double)t: an exact integer
+ * product on the left, two fp64 multiplications in that order on the right, P_e
+ * the stored prior (after the root mix).  If any edge is forced, the first forced
+ * edge in ascending edge index wins; otherwise the choice is PUCT's, unchanged.
+ * Every other level, the expansion, the draws, the backup, the budgets and the
+ * limits are what they are without the gate, and a board whose bit is clear
+ * searches exactly as it does without it.
+ *   hz_mcts_pruned_visits (enqueued on the handle's stream; -1 while the gate is
+ * off): visits[n][143] (device int32) by action id.  For a board whose bit is set,
+ * whose root has edges and t > 0: s = sqrt(max(1, t)); U_e(x) = ((double)(cpuct
+ * *f32 P_e) * s) / (double)(1 + x) and q_e = N_e ? W_e / N_e : 0, the select's own
+ * arithmetic; e* = the first edge with the largest N, bound = q_e* + U_e*(N_e*).
+ * Every other edge with N_e > 0: nf = (int)floor(sqrt((k * (double)P_e) *
+ * (double)t)); r = the largest value in 0 .. min(nf, N_e) such that q_e +
+ * U_e(N_e - j) < bound for every j = 1 .. r (the first j that fails ends it; q_e
+ * stays fixed); N'_e = N_e - r, and 0 if r > 0 and N'_e <= 1.  e* and unvisited
+ * edges keep their counts.  A board whose bit is clear gets hz_mcts_result's row;
+ * a board without a tree zeros.
+ *   hz_mcts_forced_counts (a report for callers and tools; -1 while the gate is
+ * off): out[n][2] (device int32) = per board, the root selections this gate saw
+ * since the last hz_mcts_set_forced (a board whose bit is set, a root with edges)
+ * and those of them the forced rule decided.  The counters are instrumentation
+ * that stays in the forced kernels: lane 0 of the board's wave adds to them at
+ * every root selection under the gate (kernels of a handle with the gate off hold
+ * no such code).  A separate instantiation without them is a possible follow-up. */
+int hz_mcts_set_forced(hz_mcts *mcts, const uint8_t *mask, double k);
+int hz_mcts_pruned_visits(hz_mcts *mcts, float cpuct, int32_t *visits);
+int hz_mcts_forced_counts(hz_mcts *mcts, int32_t *out);
 /* ---- tree reuse: the searched subtree carried into the next search ----------
  * No reference counterpart (MCTS.py:288 builds a fresh Node per call): this is
  * the build's defined behaviour, off unless the caller asks for it, pinned by
