@@ -52,11 +52,14 @@ __device__ double gamma_draw(NoiseStream &s, double alpha) {
   return g;
 }
 
-__global__ void __launch_bounds__(kWave) k_root_noise(const int32_t *__restrict__ count, int n, uint64_t seed,
-                                                      uint64_t board_base, uint64_t move, double alpha,
-                                                      double *__restrict__ noise, double *__restrict__ u) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const uint64_t key = mix64(mix64(mix64(seed ^ 0x6A09E667F3BCC908ULL) ^ (board_base + (uint64_t)b)) ^ move);
+// The key of board b's draws at `move`: every draw kernel's, the per-board-move forms' too.
+__device__ __forceinline__ uint64_t draw_key(uint64_t seed, uint64_t board_base, int b, uint64_t move) {
+  return mix64(mix64(mix64(seed ^ 0x6A09E667F3BCC908ULL) ^ (board_base + (uint64_t)b)) ^ move);
+}
+
+// Board b's noise row and uniform under `key` (one wave): k_root_noise's and k_root_noise_at's body.
+__device__ __forceinline__ void root_noise_row(const int32_t *__restrict__ count, int b, int lane, uint64_t key,
+                                               double alpha, double *__restrict__ noise, double *__restrict__ u) {
   const int nl = count ? min(max(count[b], 0), kMaxChildren) : 0;
   double g[2];
   double sum = 0.0;
@@ -81,17 +84,47 @@ __global__ void __launch_bounds__(kWave) k_root_noise(const int32_t *__restrict_
   }
 }
 
+__global__ void __launch_bounds__(kWave) k_root_noise(const int32_t *__restrict__ count, int n, uint64_t seed,
+                                                      uint64_t board_base, uint64_t move, double alpha,
+                                                      double *__restrict__ noise, double *__restrict__ u) {
+  const int b = blockIdx.x;
+  root_noise_row(count, b, threadIdx.x, draw_key(seed, board_base, b, move), alpha, noise, u);
+}
+
+// The per-board-move form (hz_root_noise_at): board b's row at move[b], where
+// mask[b] == 1; every other row of noise and u keeps what it holds.
+__global__ void __launch_bounds__(kWave) k_root_noise_at(const int32_t *__restrict__ count, int n, uint64_t seed,
+                                                         uint64_t board_base, const uint64_t *__restrict__ move,
+                                                         const uint8_t *__restrict__ mask, double alpha,
+                                                         double *__restrict__ noise, double *__restrict__ u) {
+  const int b = blockIdx.x;
+  if (mask[b] != 1) return;  // (wave-uniform)
+  root_noise_row(count, b, threadIdx.x, draw_key(seed, board_base, b, move[b]), alpha, noise, u);
+}
+
 // One uniform in (0, 1] per board (hz_playout_coin: the coin of playout-cap
 // randomization, no reference counterpart), from k_root_noise's generator and
 // board key under a salt of its own: neither the noise nor the move-choice
 // uniform moves by a bit.
+__device__ __forceinline__ double coin_of(uint64_t key) {
+  NoiseStream s{mix64(key ^ 0x94D049BB133111EBULL), 0};
+  return s.uniform();
+}
 __global__ void __launch_bounds__(256) k_playout_coin(int n, uint64_t seed, uint64_t board_base, uint64_t move,
                                                       double *__restrict__ coin) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= n) return;
-  const uint64_t key = mix64(mix64(mix64(seed ^ 0x6A09E667F3BCC908ULL) ^ (board_base + (uint64_t)b)) ^ move);
-  NoiseStream s{mix64(key ^ 0x94D049BB133111EBULL), 0};
-  coin[b] = s.uniform();
+  coin[b] = coin_of(draw_key(seed, board_base, b, move));
+}
+
+// The per-board-move form (hz_playout_coin_at): board b's coin at move[b],
+// where mask[b] == 1; every other entry keeps what it holds.
+__global__ void __launch_bounds__(256) k_playout_coin_at(int n, uint64_t seed, uint64_t board_base,
+                                                         const uint64_t *__restrict__ move,
+                                                         const uint8_t *__restrict__ mask, double *__restrict__ coin) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n || mask[b] != 1) return;
+  coin[b] = coin_of(draw_key(seed, board_base, b, move[b]));
 }
 
 // One standard Gumbel per board and legal rank (hz_root_gumbel; no reference
@@ -141,6 +174,24 @@ int hz_playout_coin(int32_t n, uint64_t seed, uint64_t board_base, uint64_t move
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_playout_coin, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, seed, board_base,
                      move, coin);
+  return launch_err();
+}
+
+int hz_root_noise_at(const int32_t *count, int32_t n, uint64_t seed, uint64_t board_base, const uint64_t *move,
+                     const uint8_t *mask, double alpha, double *noise, double *u, void *stream) {
+  if (n < 0 || !count || !move || !mask || !noise || !(alpha > 0.0)) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_root_noise_at, dim3(n), dim3(kWave), 0, (hipStream_t)stream, count, n, seed, board_base, move,
+                     mask, alpha, noise, u);
+  return launch_err();
+}
+
+int hz_playout_coin_at(int32_t n, uint64_t seed, uint64_t board_base, const uint64_t *move, const uint8_t *mask,
+                       double *coin, void *stream) {
+  if (n < 0 || !move || !mask || !coin) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_playout_coin_at, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, seed, board_base,
+                     move, mask, coin);
   return launch_err();
 }
 

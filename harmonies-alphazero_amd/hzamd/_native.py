@@ -76,6 +76,13 @@ _SIGS = {
     "hz_mcts_set_budget": ([_vp, _vp], _c.c_int),
     "hz_mcts_sims_done": ([_vp, _vp], _c.c_int),
     "hz_mcts_set_root_noise_mask": ([_vp, _vp], _c.c_int),
+    "hz_mcts_begin_some": ([_vp, _vp, _vp], _c.c_int),
+    "hz_mcts_set_gate_some": ([_vp, _vp, _vp, _vp], _c.c_int),
+    "hz_root_noise_at": ([_vp, _c.c_int32, _c.c_uint64, _c.c_uint64, _vp, _vp, _c.c_double, _vp, _vp, _vp], _c.c_int),
+    "hz_playout_coin_at": ([_c.c_int32, _c.c_uint64, _c.c_uint64, _vp, _vp, _vp, _vp], _c.c_int),
+    "hz_choose_actions": ([_vp, _c.c_int32, _vp, _vp, _vp, _vp], _c.c_int),
+    "hz_turn_choose": ([_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int64, _c.c_int32, _c.c_int32] + [_vp] * 6, _c.c_int),
+    "hz_turn_after": ([_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int64, _c.c_uint64] + [_vp] * 9, _c.c_int),
     "hz_root_gumbel": ([_c.c_int32, _c.c_uint64, _c.c_uint64, _c.c_uint64, _vp, _vp], _c.c_int),
     "hz_mcts_set_gumbel": ([_vp, _vp, _vp, _c.c_int32, _c.c_int32, _c.c_double, _c.c_double], _c.c_int),
     "hz_mcts_root_gumbel_scores": ([_vp, _vp], _c.c_int),

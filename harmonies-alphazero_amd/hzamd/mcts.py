@@ -168,6 +168,40 @@ class BatchedMCTS:
         self._sync()
         nat.check(nat.lib().hz_mcts_begin(self._h, self.env.handle, nat.ptr(active)), "hz_mcts_begin")
 
+    def _mask(self, mask, name="mask"):
+        """A per-board mask of the masked entry points: uint8 [n] on the device."""
+        if not torch.is_tensor(mask) or mask.shape != (self.n,):
+            raise ValueError(f"{name}: a tensor of one flag per board, shape ({self.n},)")
+        return mask.to(device=self.device, dtype=torch.uint8).contiguous()
+
+    def begin_some(self, mask):
+        """begin() for the boards whose mask is 1 (hz_mcts_begin_some), with
+        nothing written on the boards whose mask is 0: their trees, counts
+        and sims_done stay what they are (begin() clears inactive boards and
+        zeroes every board's sims_done).  A board whose mask is 2 is stopped:
+        no tree, and budget 0 under the gate."""
+        self._sync()
+        nat.check(nat.lib().hz_mcts_begin_some(self._h, self.env.handle, nat.ptr(self._mask(mask))),
+                  "hz_mcts_begin_some")
+
+    def set_gate_some(self, mask, budget=None, root_noise=None):
+        """The budget and the root-noise bit of the boards whose mask is 1
+        (hz_mcts_set_gate_some), written into the handle's copies in stream
+        order; every other board keeps its own.  The gate (the mask) must be
+        on: set by the last search(budget=, root_noise=) or _set_gate()."""
+        if budget is not None:
+            if not self._gate[0]:
+                raise ValueError("set_gate_some(budget=) while the budget gate is off")
+            budget = budget.to(device=self.device, dtype=torch.int32).contiguous()
+            if budget.shape != (self.n,):
+                raise ValueError(f"budget of shape {tuple(budget.shape)}, not ({self.n},)")
+        if root_noise is not None:
+            if not self._gate[1]:
+                raise ValueError("set_gate_some(root_noise=) while the root-noise mask is off")
+            root_noise = self._mask(root_noise, "root_noise")
+        nat.check(nat.lib().hz_mcts_set_gate_some(self._h, nat.ptr(budget), nat.ptr(root_noise),
+                                                  nat.ptr(self._mask(mask))), "hz_mcts_set_gate_some")
+
     def begin_carried(self, active=None, noise=None, eps=0.25, testing=True):
         """begin() that keeps the trees advance() carried (hz_mcts_begin_carried):
         a carried board whose node 0 still is the env's state starts from its
@@ -818,6 +852,24 @@ def choose_actions(visits, explore, u):
     sampled = torch.argmax((target.unsqueeze(1) < cum.to(torch.float64)).to(torch.int32), dim=1)
     act = torch.where(explore.to(torch.bool), sampled, greedy)
     return torch.where(total > 0, act, torch.full_like(act, -1))
+
+
+def choose_actions_native(visits, explore, u):
+    """choose_actions in one launch (hz_choose_actions: the rule the turn of
+    SelfPlay.play_async applies to its trees): int16 [n] on the device."""
+    n = visits.shape[0]
+    d = visits.device
+    if visits.shape != (n, ACTION_SIZE):
+        raise ValueError(f"visits of shape {tuple(visits.shape)}, not (n, {ACTION_SIZE})")
+    visits = visits.to(torch.int32).contiguous()
+    explore = explore.to(device=d, dtype=torch.uint8).contiguous()
+    u = u.to(device=d, dtype=torch.float64).contiguous()
+    if explore.shape != (n,) or u.shape != (n,):
+        raise ValueError("explore and u: one entry per board")
+    act = torch.empty(n, dtype=torch.int16, device=d)
+    nat.check(nat.lib().hz_choose_actions(nat.ptr(visits), n, nat.ptr(explore), nat.ptr(u), nat.ptr(act),
+                                          nat.stream_ptr(d)), "hz_choose_actions")
+    return act
 
 
 def pi_from_visits(visits):

@@ -55,6 +55,16 @@ is chosen from the raw visits (kept in `last_visits`), and the visits move()
 returns and the records hold are the pruned ones
 (BatchedMCTS.pruned_visits).  Off while `testing`; with playout caps and
 leaf symmetries; not with tree_reuse or root_policy "gumbel".
+
+The asynchronous schedule (no reference counterpart; SelfPlay.play_async,
+and `schedule="async"` with `moves_per_board` in iteration() and the
+trainer's self-play config, absent by default): play_steady without the
+barrier between moves.  Every board keeps a move counter of its own, and a
+board whose search is spent records, moves and begins its next search inside
+the sim step (the turn: include/hz_abi.h), so boards with different budgets
+never leave a sim step with idle rows; the records are play_steady's bit for
+bit.  With playout caps on or off and `testing`; not with tree_reuse,
+root_policy "gumbel", leaf_symmetry, forced_playouts or keep_root_value.
 """
 import torch
 
@@ -83,6 +93,22 @@ def playout_budgets(coin, p, full_sims, fast_sims):
     full = coin < float(p) if float(p) < 1.0 else torch.ones_like(coin, dtype=torch.bool)
     budget = torch.where(full, int(full_sims), int(fast_sims)).to(torch.int32)
     return budget, full
+
+
+def check_schedule(schedule, moves_per_board):
+    """The self-play schedule keys (SelfPlay.iteration, Trainer's
+    self_play_config): schedule None (a game per board, the barrier schedule)
+    takes no moves_per_board; "async" (SelfPlay.play_async) needs a positive
+    integer.  Returns moves_per_board as an int, or None."""
+    if schedule not in (None, "async"):
+        raise ValueError(f"schedule {schedule!r}: not None or 'async'")
+    if schedule is None:
+        if moves_per_board is not None:
+            raise ValueError("moves_per_board goes with schedule 'async'")
+        return None
+    if isinstance(moves_per_board, bool) or not isinstance(moves_per_board, int) or moves_per_board < 1:
+        raise ValueError(f"schedule 'async' needs moves_per_board, a positive integer, not {moves_per_board!r}")
+    return moves_per_board
 
 
 class NoiseSource:
@@ -116,6 +142,44 @@ class NoiseSource:
                                             int(step) & (2**64 - 1), nat.ptr(coin), nat.stream_ptr(self.device)),
                   "hz_playout_coin")
         return coin
+
+    def _at_args(self, moves, mask, n):
+        if not torch.is_tensor(moves) or moves.dtype not in (torch.int64, torch.uint64) or moves.shape != (n,):
+            raise ValueError("moves: an int64 / uint64 tensor of one move counter per board")
+        if not torch.is_tensor(mask) or mask.shape != (n,):
+            raise ValueError("mask: one flag per board")
+        return (moves.to(device=self.device).contiguous(),
+                mask.to(device=self.device, dtype=torch.uint8).contiguous())
+
+    def draw_at(self, moves, counts, alpha, mask, noise_out, u_out):
+        """The per-board-counter form of draw() (hz_root_noise_at): where
+        mask[b] == 1, row b of noise_out (f64 [n, 69]) and u_out[b] (f64 [n])
+        get the bits draw(moves[b], ...) gives board b; every other row keeps
+        what it holds.  moves: int64 / uint64 [n] on the device."""
+        n = counts.numel()
+        moves, mask = self._at_args(moves, mask, n)
+        counts = counts.to(device=self.device, dtype=torch.int32).contiguous()
+        for t, shape, name in ((noise_out, (n, MAX_CHILDREN), "noise_out"), (u_out, (n,), "u_out")):
+            if (not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != shape or
+                    not t.is_contiguous() or t.device.type != self.device.type):
+                raise ValueError(f"{name}: a contiguous float64 tensor of shape {shape} on {self.device}")
+        nat.check(nat.lib().hz_root_noise_at(nat.ptr(counts), n, self.seed & (2**64 - 1),
+                                             self.board_base & (2**64 - 1), nat.ptr(moves), nat.ptr(mask),
+                                             float(alpha), nat.ptr(noise_out), nat.ptr(u_out),
+                                             nat.stream_ptr(self.device)), "hz_root_noise_at")
+
+    def coin_at(self, moves, mask, coin_out):
+        """The per-board-counter form of coin() (hz_playout_coin_at): where
+        mask[b] == 1, coin_out[b] (f64 [n]) gets board b's coin of move
+        moves[b]; every other entry keeps what it holds."""
+        n = coin_out.numel()
+        moves, mask = self._at_args(moves, mask, n)
+        if coin_out.dtype != torch.float64 or coin_out.dim() != 1 or not coin_out.is_contiguous() or \
+                coin_out.device.type != self.device.type:
+            raise ValueError(f"coin_out: a contiguous float64 tensor of shape ({n},) on {self.device}")
+        nat.check(nat.lib().hz_playout_coin_at(n, self.seed & (2**64 - 1), self.board_base & (2**64 - 1),
+                                               nat.ptr(moves), nat.ptr(mask), nat.ptr(coin_out),
+                                               nat.stream_ptr(self.device)), "hz_playout_coin_at")
 
     def gumbel(self, step, n):
         """One standard Gumbel per board and legal rank under the same key
@@ -482,6 +546,169 @@ class SelfPlay:
             rec["carried"] = carried  # int32 [M, n]: the root visits the search started with (tree reuse)
         return rec
 
+    ASYNC_LAG = 2  # sim steps queued past the one whose running-board count the host waits for
+
+    def _async_unsupported(self):
+        """The configuration keys play_async does not take yet (each needs one
+        more masked per-board draw, or the carried begin)."""
+        off = []
+        if self.tree_reuse:
+            off.append("tree_reuse")
+        if self.gumbel is not None:
+            off.append("root_policy 'gumbel'")
+        if self.leaf_symmetry:
+            off.append("leaf_symmetry")
+        if self.forced_k is not None:
+            off.append("forced_playouts")
+        if self.keep_root_value:
+            off.append("keep_root_value")
+        return off
+
+    def play_async(self, moves, reset=True, sim_steps=None):
+        """play_steady(moves) without the barrier between moves: every board
+        keeps a move counter of its own, and a board whose search is spent
+        records its result, plays its move and begins its next search inside
+        the sim step, while the other boards carry on with theirs; every sim
+        step then has one live row per board, whatever the boards' budgets
+        (playout caps).  Board b's k-th move is searched, chosen, recorded and
+        played exactly as play_steady does at its move k (the draws' keys, the
+        budget rule, the tau rule by the board's own ply, the game seeds), so
+        the records are play_steady's bit for bit, for a row_independent
+        evaluator.
+
+        One sim step is select + gather + encode, the evaluator, expand +
+        backup, then the turn (hz_turn_choose, hz_step, hz_turn_after,
+        hz_reset on the ended games, the turned boards' draws and gate
+        updates, hz_mcts_begin_some): the layered form, in which a turned
+        board's new root is evaluated in the very next step.  The host reads
+        nothing per sim step: the count of running boards comes back through
+        a pinned ring ASYNC_LAG steps late, so up to ASYNC_LAG empty steps are
+        queued after the last board has stopped.
+
+        The run ends when every board has made `moves` moves, or after
+        sim_steps sim steps if given; the boards have then made different
+        numbers of moves.  Returns play_steady's dict plus `moves_done` int32
+        [n] (records past moves_done[b] are zero and invalid) and `sim_steps`
+        (the steps up to the last turn); compact_steady() takes it as it is.
+        A failed env step on a searched board raises RuntimeError at the end
+        of the run, as check_steps() does.  The draws' move counter
+        (step_counter) advances by `moves`, as play_steady's does, cut or not.
+
+        PUCT root with Dirichlet noise, `testing`, playout caps on or off;
+        tree_reuse, root_policy "gumbel", leaf_symmetry, forced_playouts and
+        keep_root_value raise ValueError."""
+        off = self._async_unsupported()
+        if off:
+            raise ValueError(f"play_async does not take {', '.join(off)}")
+        M = int(moves)
+        limit = None if sim_steps is None else int(sim_steps)
+        if M < 0 or (limit is not None and limit < 0):
+            raise ValueError("play_async: negative moves or sim_steps")
+        env, n, d, cfg, mcts, L = self.env, self.n, self.device, self.cfg, self.mcts, nat.lib()
+        testing = bool(cfg.get("testing", False))
+        nsims, cpuct, eps = int(cfg["num_simulations"]), cfg["cpuct"], cfg["dirichlet_epsilon"]
+        alpha, tau0 = cfg["dirichlet_alpha"], int(cfg["turns_until_tau0"])
+        base = int(env.seed_base)
+        self.check_steps()  # (an earlier move()'s step)
+        if reset:
+            env.reset(seeds=base + torch.arange(n, device=d, dtype=torch.int64))
+
+        def z(dtype, *shape, fill=0):
+            return torch.full(shape, fill, dtype=dtype, device=d)
+
+        rec = {"states": z(torch.int64, M, 6, n), "visits": z(torch.int32, M, n, 143), "game": z(torch.int32, M, n),
+               "ended": z(torch.bool, M, n), "outcome": z(torch.float32, M, n), "plies": z(torch.int16, M, n)}
+        full = z(torch.bool, M, n) if self.playout_cap else None
+        mc, ply, game = z(torch.int64, n), z(torch.int32, n), z(torch.int64, n)
+        running = z(torch.int32, 1, fill=n if M else 0)
+        act, turned, bad = z(torch.int16, n, fill=-1), z(torch.uint8, n), z(torch.uint8, n)
+        sel, seeds = z(torch.uint8, n), z(torch.int64, n)
+        begin = z(torch.uint8, n, fill=1 if M else 2)  # the first searches: every board's
+        noise, u, coin = z(torch.float64, n, MAX_CHILDREN), z(torch.float64, n), z(torch.float64, n, fill=1.0)
+        budget_all = z(torch.int32, n, fill=nsims)
+        step0 = self.step_counter
+        # the budget gate and the root-noise mask on, every other gate off
+        mcts._sync()
+        mcts._set_gate(budget_all, z(torch.uint8, n, fill=1), mcts._set_gumbel(None, nsims, None, None, None),
+                       mcts._set_leaf_symmetry(None), mcts._set_forced(None, None))
+        mcts.eval_rows.zero_()
+        mcts._cap_risk = False
+        device_rows = bool(getattr(self.evaluator, "device_rows", False))
+
+        def begin_turned():
+            """Step (d): the searches of the boards `begin` names, at their own move counters."""
+            _, count = env.legal_mask()
+            mv = mc + step0 if step0 else mc
+            if self.playout_cap:
+                p, fast = self.playout_cap
+                self.noise.coin_at(mv, begin, coin)
+                budget, is_full = playout_budgets(coin, p, nsims, fast)
+                mcts.set_gate_some(begin, budget=budget, root_noise=is_full)
+            else:  # (the stuck-root rule may have zeroed the board's last budget)
+                mcts.set_gate_some(begin, budget=budget_all)
+            self.noise.draw_at(mv, count, alpha, begin, noise, u)
+            mcts.begin_some(begin)
+
+        def sim_step():
+            board, glob, rows, count = mcts.select_gather(cpuct)
+            if device_rows:
+                policy, value = self.evaluator(board, glob, rows, count)
+            else:  # every row, the stale ones past count included (unused): no host read of count
+                policy, value = self.evaluator(board, glob)
+            mcts.expand_backup(policy, value, noise, eps, testing, gathered=True)
+            nat.check(L.hz_turn_choose(mcts._h, env.handle, nat.ptr(u), nat.ptr(ply), nat.ptr(mc), nat.ptr(game), M,
+                                       tau0, int(testing), nat.ptr(act), nat.ptr(turned), nat.ptr(rec["states"]),
+                                       nat.ptr(rec["visits"]), nat.ptr(rec["game"]), nat.ptr(full)), "hz_turn_choose")
+            status = env.step(act)
+            nat.check(L.hz_turn_after(env.handle, nat.ptr(turned), nat.ptr(status), nat.ptr(mc), nat.ptr(ply),
+                                      nat.ptr(game), M, base & (2**64 - 1), nat.ptr(rec["ended"]),
+                                      nat.ptr(rec["outcome"]), nat.ptr(rec["plies"]), nat.ptr(sel), nat.ptr(seeds),
+                                      nat.ptr(begin), nat.ptr(bad), nat.ptr(running), nat.stream_ptr(d)),
+                      "hz_turn_after")
+            env.reset(sel=sel, seeds=seeds)
+            begin_turned()
+
+        begin_turned()
+        ring = torch.zeros(self.ASYNC_LAG + 2, dtype=torch.int32, pin_memory=True)
+        pending = []  # (sim steps run, ring slot, event), oldest first
+        done_at = 0 if M == 0 else None
+
+        def landed(keep):
+            """Wait for the counts queued more than `keep` steps ago; the step count at which no board ran."""
+            while len(pending) > keep:
+                at, slot, ev = pending.pop(0)
+                ev.synchronize()
+                if int(ring[slot]) == 0:
+                    return at
+            return None
+
+        steps = 0
+        while done_at is None and (limit is None or steps < limit):
+            sim_step()
+            steps += 1
+            slot = steps % ring.numel()
+            ring[slot:slot + 1].copy_(running, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            pending.append((steps, slot, ev))
+            done_at = landed(self.ASYNC_LAG)
+        if done_at is None:
+            done_at = landed(0)
+        mcts.eval_rows_total += mcts.eval_rows
+        self.step_counter = step0 + M
+        from .infer import check_split_timeouts
+        check_split_timeouts(d)
+        nbad = torch.nonzero(bad).flatten().tolist()  # (the run's one wait for the device)
+        if nbad:
+            raise RuntimeError(f"self-play step failed on boards {nbad[:8]}")
+        rec["players"] = ((rec["states"][:, 5] >> 41) & 1).to(torch.int8)
+        rec["moves"] = M
+        if full is not None:
+            rec["full"] = full
+        rec["moves_done"] = mc.to(torch.int32)
+        rec["sim_steps"] = steps if done_at is None else done_at
+        return rec
+
     def _full_only(self, rec, full_only):
         """The records' full-search mask when only those become training
         records (the default with playout caps on), else None."""
@@ -506,6 +733,8 @@ class SelfPlay:
         res[key[em]] = rec["outcome"][em]
         has[key[em]] = True
         mask = has[key]                                            # records of ended games
+        if "moves_done" in rec:  # play_async cut short by sim_steps: the slots a board did not reach are no records
+            mask = mask & (torch.arange(M, device=d).unsqueeze(1) < rec["moves_done"].unsqueeze(0))
         full = self._full_only(rec, full_only)
         if full is not None:
             mask = mask & full
@@ -554,18 +783,25 @@ class SelfPlay:
             comp["q"] = rec["root_value"][mask].to(torch.float32)
         return comp
 
-    def iteration(self, buffer=None, group=None, timings=None):
+    def iteration(self, buffer=None, group=None, timings=None, schedule=None, moves_per_board=None):
         """One self-play phase: every board plays a game; with torch.distributed
         initialised the packed records of all ranks are all-gathered (RCCL)
         into `buffer` (a distributed.ReplayBuffer) on every rank, in rank
         order.  timings (a dict, optional) gets "play_s" and "exchange_s"
-        (device-synchronised; the exchange starts after a barrier)."""
+        (device-synchronised; the exchange starts after a barrier).
+        schedule="async" with moves_per_board=K: the phase is play_async(K) and
+        compact_steady() instead (the games that ended inside the run)."""
         from . import distributed as hd
         import time
         import torch.distributed as dist
+        moves_per_board = check_schedule(schedule, moves_per_board)
         t0 = time.perf_counter()
-        rec = self.play()
-        comp = self.compact(rec)
+        if schedule == "async":
+            rec = self.play_async(moves_per_board)
+            comp = self.compact_steady(rec)
+        else:
+            rec = self.play()
+            comp = self.compact(rec)
         packed = hd.pack_records(comp["states"], comp["visits"], comp["z"], comp["player"])
         distributed = dist.is_available() and dist.is_initialized()
         if timings is not None:

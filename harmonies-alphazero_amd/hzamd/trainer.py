@@ -31,7 +31,7 @@ from . import buffer_io
 from . import distributed as hd
 from .manager import ModelManager
 from .mcts import BatchedPredictor
-from .selfplay import SelfPlay
+from .selfplay import SelfPlay, check_schedule
 from .train import SYMMETRY_MODES, SymRecordSource, featurize, training_phase
 
 
@@ -52,6 +52,10 @@ class Trainer:
         if sym is not None and sym != "none" and sym not in SYMMETRY_MODES:
             raise ValueError(f"training_config['symmetry'] = {sym!r}: expected 'none', 'random' or 'all'")
         self.symmetry = None if sym in (None, "none") else sym
+        # "schedule": absent plays a game per board (SelfPlay.play); "async" with
+        # "moves_per_board" runs SelfPlay.play_async and keeps the games that ended inside it
+        self.schedule = self_play_config.get("schedule")
+        self.moves_per_board = check_schedule(self.schedule, self_play_config.get("moves_per_board"))
         self.eval_mcts_config = dict(arena.MCTS_EVAL, **(eval_mcts_config or {}))
         self.seed_base = int(seed_base)
         self.log = log
@@ -99,9 +103,15 @@ class Trainer:
         base = self.seed_base + (self.iteration * self.world + self.rank) * n
         pred = BatchedPredictor(data_generating_manager.model, tower=data_generating_manager.inference_tower)
         sp = SelfPlay(n, pred, self.mcts_config, seed_base=base, device=self.device)
-        packed, rec = sp.iteration(self.replay_buffer)
-        self.last_self_play = {"examples": int(packed.shape[0]), "games": n * self.world,
-                               "plies": rec["plies"], "seconds": time.time() - t0}
+        if self.schedule is None:
+            packed, rec = sp.iteration(self.replay_buffer)
+            games, plies = n * self.world, rec["plies"]
+        else:  # the games that ended inside this rank's run; every board made moves_per_board moves
+            packed, rec = sp.iteration(self.replay_buffer, schedule=self.schedule,
+                                       moves_per_board=self.moves_per_board)
+            games, plies = int(rec["ended"].sum()), self.moves_per_board
+        self.last_self_play = {"examples": int(packed.shape[0]), "games": games,
+                               "plies": plies, "seconds": time.time() - t0}
         self.log(f"self-play: {self.last_self_play['games']} games, {self.last_self_play['examples']} examples, "
                  f"buffer {len(self.replay_buffer)}/{self.replay_buffer.capacity}, "
                  f"{self.last_self_play['seconds']:.2f}s")

@@ -423,6 +423,66 @@ int hz_mcts_take_error(hz_mcts *mcts, int32_t *out);
 int hz_mcts_set_budget(hz_mcts *mcts, const int32_t *budget);
 int hz_mcts_sims_done(hz_mcts *mcts, int32_t *out);
 int hz_mcts_set_root_noise_mask(hz_mcts *mcts, const uint8_t *mask);
+/* ---- the turn of asynchronous self-play (no reference counterpart) -----------
+ * SelfPlay.play_async: a board whose search is spent records its result, plays
+ * its move and begins its next search inside a sim step, while every other
+ * board's tree, counters, budget and noise row stay untouched, so every sim
+ * step has one live row per board.  All of it is defined under the budget gate
+ * (hz_mcts_set_budget) and, where a full flag is recorded, the root-noise mask.
+ * A mask here is device uint8 [n]: 1 selects the board, 0 leaves it alone;
+ * hz_mcts_begin_some also knows 2.
+ *
+ * hz_mcts_begin_some: for mask[b] == 1 exactly what hz_mcts_begin does for an
+ * active board (node 0 = the env's state, its key, its hash entry under a new
+ * generation, counts[b] = {1, 0, generation + 1, 0}, sims_done[b] = 0, budget 0
+ * in the handle's copy for a stuck root, the board's carry dropped); for
+ * mask[b] == 0 NOTHING is written (hz_mcts_begin clears inactive boards and
+ * zeroes every board's sims_done; this does not); for mask[b] == 2 the board is
+ * stopped: counts[b][0] = counts[b][1] = 0, leaf -1, sims_done 0 and, under the
+ * gate, budget 0, so no select walks it again.
+ * hz_mcts_set_gate_some: budget_buf[b] = budget[b] and the root-noise bit of b
+ * = (noise_bit[b] != 0) where mask[b] == 1, in stream order, the handle's
+ * buffers keeping their addresses; either array may be NULL (not updated).
+ * -1 when the gate (the mask) it would update is off.  Call it before the
+ * hz_mcts_begin_some of the boards' searches.
+ * hz_root_noise_at / hz_playout_coin_at: hz_root_noise and hz_playout_coin with
+ * one move counter per board, move[n] (device uint64 / int64): where
+ * mask[b] == 1, row b of noise, u[b] and coin[b] get the bits of the scalar
+ * call with move = move[b]; every other row keeps what it holds.
+ * hz_choose_actions: the move choice of get_best_action_and_pi (MCTS.py:394-423)
+ * as hzamd.mcts.choose_actions computes it, from visits[n][143] by action id:
+ * total and cumulative counts in int64; where explore[b] != 0 the first action
+ * a with u[b] * total < cum[a], the product and both sides in fp64 (action 0 if
+ * none is); else the first action with the most visits; -1 when total == 0.
+ * hz_turn_choose (step 4a of a turn): board b turns iff 0 <= mc[b] < moves and
+ * sims_done[b] >= the handle's budget[b].  For a turning board: its root visits
+ * by action id as hz_mcts_result gives them, action[b] by hz_choose_actions'
+ * rule with explore = !testing && ply[b] < turns_until_tau0, turned[b] = 1, and
+ * the record row at slot k = mc[b]: rec_states[k][0..5][b] = the env's six state
+ * words, rec_visits[k][b][0..142], rec_game[k][b] = game[b], and rec_full[k][b]
+ * (may be NULL) = the board's root-noise bit.  Otherwise action[b] = -1,
+ * turned[b] = 0 and no record is written.  -1 when the budget gate is off.
+ * hz_turn_after (step 4c), after hz_step(action): for turned[b] != 0, from the
+ * env's state now: rec_ended[k][b], rec_outcome[k][b] (+1 / -1 / 0 for player
+ * 0 / player 1 / a draw or a game not over), rec_plies[k][b] = ply[b] + 1; then
+ * game[b] += ended, ply[b] = ended ? 0 : ply[b] + 1, mc[b] = k + 1; sel[b] =
+ * ended and seeds[b] = seed_base + b + (game[b] << 32) for hz_reset(sel, seeds);
+ * begin[b] = 1 if mc[b] < moves, else 2 and *running -= 1; bad[b] = 1 if
+ * status[b] != 0 (never cleared).  For turned[b] == 0: sel[b] = begin[b] = 0. */
+int hz_mcts_begin_some(hz_mcts *mcts, hz_env *env, const uint8_t *mask);
+int hz_mcts_set_gate_some(hz_mcts *mcts, const int32_t *budget, const uint8_t *noise_bit, const uint8_t *mask);
+int hz_root_noise_at(const int32_t *count, int32_t n, uint64_t seed, uint64_t board_base, const uint64_t *move,
+                     const uint8_t *mask, double alpha, double *noise, double *u, void *stream);
+int hz_playout_coin_at(int32_t n, uint64_t seed, uint64_t board_base, const uint64_t *move, const uint8_t *mask,
+                       double *coin, void *stream);
+int hz_choose_actions(const int32_t *visits, int32_t n, const uint8_t *explore, const double *u, int16_t *action,
+                      void *stream);
+int hz_turn_choose(hz_mcts *mcts, hz_env *env, const double *u, const int32_t *ply, const int64_t *mc,
+                   const int64_t *game, int64_t moves, int32_t turns_until_tau0, int32_t testing, int16_t *action,
+                   uint8_t *turned, int64_t *rec_states, int32_t *rec_visits, int32_t *rec_game, uint8_t *rec_full);
+int hz_turn_after(hz_env *env, const uint8_t *turned, const int32_t *status, int64_t *mc, int32_t *ply, int64_t *game,
+                  int64_t moves, uint64_t seed_base, uint8_t *rec_ended, float *rec_outcome, int16_t *rec_plies,
+                  uint8_t *sel, uint64_t *seeds, uint8_t *begin, uint8_t *bad, int32_t *running, void *stream);
 /* ---- the Gumbel root: sequential halving, improved-policy targets ------------
  * No reference counterpart ("Policy improvement by planning with Gumbel",
  * Danihelka et al., ICLR 2022): the build's defined behaviour, off by default,
