@@ -21,6 +21,8 @@
 // the handle's create, destroy and setters; hz_mcts.hpp says where the rest is.
 #include "hz_mcts.hpp"
 
+#include <type_traits>
+
 #include "../../include/hz_abi.h"
 #include "hz_encode.hpp"
 
@@ -640,12 +642,6 @@ __device__ __forceinline__ uint64_t xstamp() {
 #define HZ_XSTAMP(k)
 #define HZ_XFLAG(k, v)
 #endif
-#ifdef HZ_KEYCHECK
-// diagnostic build only (tools/Makefile libhz_kc.so): children whose key
-// differs from canon_key of their state, leaves whose stored key differs from
-// canon_key of their stored state, children checked
-__device__ unsigned long long g_kc[3];
-#endif
 static_assert(kChildLds >= kMaxChildren, "child arrays hold every legal move");
 // 9.8 KB (was 12.3 KB, 19.5 KB before that): 16 waves fit a CU.  The turn-end
 // stream copy and the children's states share their bytes (the stream is
@@ -826,14 +822,6 @@ __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts_
           ScriptDraw sd{turn_end ? L.script[c] : ~0ull};
           step_state(ch, a, sd);
           CKey k = canon_key_child(lk, ls, ch, a, !m.exact_keys);
-#ifdef HZ_KEYCHECK
-          {
-            const CKey want = canon_key(ch, !m.exact_keys), lw = canon_key(ls, !m.exact_keys);
-            if (!key_eq(want, k)) atomicAdd(&g_kc[0], 1ull);
-            if (!key_eq(lw, lk)) atomicAdd(&g_kc[1], 1ull);
-            atomicAdd(&g_kc[2], 1ull);
-          }
-#endif
 #pragma unroll
           for (int w = 0; w < 8; w++) L.key[c][w] = k.w[w];
 #pragma unroll
@@ -1130,19 +1118,23 @@ __device__ __forceinline__ void expand_backup_board(ExpandLds &L, const hz_mcts_
 // count_out must be zero at launch; count_prev (the count of the batch this
 // launch consumed) is zeroed here for the launch after next, and added to
 // the eval counter first when add_prev (a count no gather kernel added).
-// BPW boards per workgroup (one wave each, each with its own LDS record; the
-// expansion synchronises its own wave only): with Gather, the workgroup's
-// boards take their rows with one atomic add (16 boards: 256 adds per
+// A gathering workgroup holds kGatherBPW boards (one wave each, each with its
+// own LDS record; the expansion synchronises its own wave only), which take
+// their rows with one atomic add after a barrier (16 boards: 256 adds per
 // simulation at 4096 boards instead of 4096 to one address, which cost ~20
-// us of same-address serialisation at L2).
-// WaveSlot (BPW > 1): each wave takes its row with its own atomic add as
-// soon as its walk is done, instead of the workgroup's one add after a
-// barrier that waits for the workgroup's slowest wave (A/B: HZ_SLOT_WAVE)
+// us of same-address serialisation at L2; an add per wave as soon as its walk
+// is done, without the barrier, cost more than it saved: 77 against 46 us,
+// DESIGN.md section 10 item 4); every other form has one board per workgroup.
 // Sym: the leaf-symmetry gate's instantiations (the expansion's policy index; the gathering form encodes the
 // leaf's image: the four plane words permuted before encode_one_values, which works from the six state words)
 // Root: the root form of the Sel walk (select_board); the expansion itself knows the Gumbel root only
-template <int Waves, bool Sel, int Root, bool Sym, bool Gather = false, int BPW = 1, bool WaveSlot = false>  // Waves: minimum waves per SIMD the register allocation must allow (3: none forced)
-__global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_eu(Waves, 8))) k_expand_backup(hz_mcts_args m, uint32_t *__restrict__ mtw,
+// Registers are capped for four waves per SIMD (with the 9.8 KB LDS record,
+// 4096 boards fit the chip in one round): 44.7 against 47.3 us per sim step
+// for three, profiles/r03.
+constexpr int kGatherBPW = 16;
+static_assert(kGatherBPW * sizeof(ExpandLds) <= 160 * 1024, "the workgroup's records fit the LDS");
+template <bool Sel, int Root, bool Sym, bool Gather = false>
+__global__ void __launch_bounds__(kWave * (Gather ? kGatherBPW : 1)) __attribute__((amdgpu_waves_per_eu(4, 8))) k_expand_backup(hz_mcts_args m, uint32_t *__restrict__ mtw,
                                                          int32_t *__restrict__ mtcur,
                                                          int32_t *__restrict__ wtag,
                                                          const float *__restrict__ policy,
@@ -1154,6 +1146,7 @@ __global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_e
                                                          float *__restrict__ board, float *__restrict__ glob,
                                                          int32_t *__restrict__ rows, int32_t *__restrict__ count_out,
                                                          int32_t *__restrict__ count_prev, int add_prev) {
+  constexpr int BPW = Gather ? kGatherBPW : 1;  // boards (waves) per workgroup
   __shared__ ExpandLds Ls[BPW];
   __shared__ int32_t s_need[BPW > 1 ? BPW : 1];
   __shared__ int32_t s_base;
@@ -1206,7 +1199,7 @@ __global__ void __launch_bounds__(kWave * BPW) __attribute__((amdgpu_waves_per_e
         *count_prev = 0;
       }
       int slot = -1;
-      if constexpr (BPW > 1 && !WaveSlot) {
+      if constexpr (BPW > 1) {
         if (lane == 0) s_need[w] = g >= 0;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -1501,11 +1494,12 @@ int hz_mcts_begin(hz_mcts *m, hz_env *env, const uint8_t *active) {
 
 int hz_mcts_select(hz_mcts *m, const uint8_t *active, float cpuct) {
   if (!m) return -1;
-  const bool forced = m->forced_k > 0.0;
-  if (m->gumbel && forced) return -1;  // (one root form per search)
-  if (m->gumbel) hipLaunchKernelGGL(k_select<kRootGumbel>, dim3(m->n), dim3(kWave), 0, m->stream, *m, active, cpuct);
-  else if (forced) hipLaunchKernelGGL(k_select<kRootForced>, dim3(m->n), dim3(kWave), 0, m->stream, *m, active, cpuct);
-  else hipLaunchKernelGGL(k_select<kRootPuct>, dim3(m->n), dim3(kWave), 0, m->stream, *m, active, cpuct);
+  // (k_select encodes no leaf: the leaf-symmetry gate is not its concern)
+  const LaunchForm form = pick_form(m->gumbel != nullptr, m->forced_k > 0.0, false, true);
+  if (form.root < 0) return -1;
+  with_form<true>(form, [&](auto f) {
+    hipLaunchKernelGGL(k_select<decltype(f)::root>, dim3(m->n), dim3(kWave), 0, m->stream, *m, active, cpuct);
+  });
   return launch_err();
 }
 
@@ -1527,27 +1521,21 @@ int hz_mcts_select_gather(hz_mcts *m, const uint8_t *active, float cpuct, float 
     const int rc = hz_mcts_select(m, active, cpuct);
     return rc ? rc : hz_mcts_gather_leaves(m, board, glob, rows, count);
   }
-  if (m->gumbel && m->leaf_key) return -1;  // (the symmetric instantiations exist without the Gumbel root only)
-  const bool forced = m->forced_k > 0.0;
-  if (m->gumbel && forced) return -1;  // (one root form per search)
-#define HZ_SGE_LAUNCH(ROOT, SYM)                                                                                     \
-  hipLaunchKernelGGL((k_select_gather_encode<ROOT, SYM>), dim3(1), dim3(kFusedWaves * kWave), 0, m->stream, *m, active, \
-                     cpuct, rows, count, board, glob)
-  if (m->gumbel) HZ_SGE_LAUNCH(kRootGumbel, false);
-  else if (forced && m->leaf_key) HZ_SGE_LAUNCH(kRootForced, true);
-  else if (forced) HZ_SGE_LAUNCH(kRootForced, false);
-  else if (m->leaf_key) HZ_SGE_LAUNCH(kRootPuct, true);
-  else HZ_SGE_LAUNCH(kRootPuct, false);
-#undef HZ_SGE_LAUNCH
+  const LaunchForm form = pick_form(*m, true);
+  if (form.root < 0) return -1;
+  with_form<true>(form, [&](auto f) {
+    using F = decltype(f);
+    hipLaunchKernelGGL((k_select_gather_encode<F::root, F::sym>), dim3(1), dim3(kFusedWaves * kWave), 0, m->stream, *m,
+                       active, cpuct, rows, count, board, glob);
+  });
   return launch_err();
 }
 
 int hz_mcts_gather_leaves(hz_mcts *m, float *board, float *glob, int32_t *rows, int32_t *count) {
   if (!m || !count || (!board && !glob)) return -1;
-  // default: k_gather_encode (one launch); HZ_GATHER_ENCODE=0: k_gather + the
-  // encoder launches (same results)
-  static const bool fused_default = env_pick("HZ_GATHER_ENCODE", 0, 1);
-  const bool fused = m->gather_mode < 0 ? fused_default : m->gather_mode == 1;
+  // default: k_gather_encode (one launch); mode 0: k_gather + the encoder
+  // launches (same results)
+  const bool fused = m->gather_mode != 0;
   // (the leaf-symmetry gate picks the instantiation: with it off the kernels carry none of its code)
   if (fused && board && glob) {
     if (m->leaf_key)
@@ -1568,73 +1556,34 @@ int hz_mcts_gather_leaves(hz_mcts *m, float *board, float *glob, int32_t *rows, 
   return launch_err();
 }
 
-// boards per workgroup of the gathering expand launch (one atomic add per
-// workgroup): 16 by default, HZ_GATHER_BPW=8 (A/B: two workgroups per CU)
-constexpr int kGatherBPW = 16;
-static_assert(kGatherBPW * sizeof(ExpandLds) <= 160 * 1024, "the workgroup's records fit the LDS");
-static int gather_bpw() {
-  static const int v = env_pick("HZ_GATHER_BPW", 8, kGatherBPW);
-  return v;
-}
-
 static int expand_backup(hz_mcts *m, hz_env *env, const float *policy, const float *value, const double *noise,
                          double eps, int32_t testing, const int32_t *slot, bool sel = false,
                          const uint8_t *active = nullptr, float cpuct = 0.f, float *board = nullptr,
                          float *glob = nullptr, int32_t *rows = nullptr, int32_t *count_out = nullptr,
                          int32_t *count_prev = nullptr, int add_prev = 0) {
   if (!m || !env || !policy || !value || hz_env_size(env) != m->n) return -1;
-  if (m->gumbel && m->leaf_key) return -1;  // (the symmetric instantiations exist without the Gumbel root only)
-  const bool forced = m->forced_k > 0.0;
-  if (m->gumbel && forced) return -1;  // (one root form per search)
+  const LaunchForm form = pick_form(*m, sel);
+  if (form.root < 0) return -1;
   float ome = (float)(1.0 - eps);
-  // default: registers capped for four waves per SIMD (38 VGPRs spilled;
-  // with the 9.8 KB LDS, 4096 boards fit the chip in one round): 44.7 vs
-  // 47.3 us per sim step for three waves (HZ_EXPAND_WAVES=3), profiles/r03
-  static const int waves = env_pick("HZ_EXPAND_WAVES", 3, 4);
-  // HZ_EXPAND_PRIO=0: the turn-end waves keep the default issue priority (A/B)
-  static const int prio = env_pick("HZ_EXPAND_PRIO", 0, 1);
-  static const bool wave_slot = env_pick("HZ_SLOT_WAVE", 1, 0);
+  const int prio = 1;  // (turn-end waves at issue priority 2; an argument still: as a constant it moves the register allocation)
   // the env's streams made current (materialize), once per call; the kernel
   // voids the saved draw window of every board whose stream it moves
   uint32_t *mt = nullptr;
   int32_t *mt_pos = nullptr, *win_tag = nullptr;
   if (hz_env_stream_ptrs(env, &mt, &mt_pos, &win_tag)) return 1;
-#define HZ_EXPAND_LAUNCH_G(W, S, ROOT, SYM, G, BP, ...)                                                         \
-  hipLaunchKernelGGL((k_expand_backup<W, S, ROOT, SYM, G, BP, ##__VA_ARGS__>), dim3((m->n + (BP) - 1) / (BP)), dim3(kWave * (BP)), \
-                     0, m->stream, *m, mt, mt_pos, win_tag, policy, value, noise, eps, ome, testing, slot, prio, active, cpuct, \
-                     board, glob, rows, count_out, count_prev, add_prev)
-  // (the Gumbel, forced-playout and leaf-symmetry gates pick the instantiation: with a gate off the kernels carry
-  // none of its code; the forced rule lives in the walk, so the forms without a select have no forced instantiation)
-#define HZ_EXPAND_LAUNCH_NOSEL(W)                                                             \
-  do {                                                                                        \
-    if (m->gumbel) HZ_EXPAND_LAUNCH_G(W, false, kRootGumbel, false, false, 1);                 \
-    else if (m->leaf_key) HZ_EXPAND_LAUNCH_G(W, false, kRootPuct, true, false, 1);             \
-    else HZ_EXPAND_LAUNCH_G(W, false, kRootPuct, false, false, 1);                             \
-  } while (0)
-#define HZ_EXPAND_LAUNCH(W, G, BP, ...)                                                            \
-  do {                                                                                             \
-    if (m->gumbel) HZ_EXPAND_LAUNCH_G(W, true, kRootGumbel, false, G, BP, ##__VA_ARGS__);           \
-    else if (forced && m->leaf_key) HZ_EXPAND_LAUNCH_G(W, true, kRootForced, true, G, BP, ##__VA_ARGS__); \
-    else if (forced) HZ_EXPAND_LAUNCH_G(W, true, kRootForced, false, G, BP, ##__VA_ARGS__);         \
-    else if (m->leaf_key) HZ_EXPAND_LAUNCH_G(W, true, kRootPuct, true, G, BP, ##__VA_ARGS__);       \
-    else HZ_EXPAND_LAUNCH_G(W, true, kRootPuct, false, G, BP, ##__VA_ARGS__);                       \
-  } while (0)
-  const bool gat = sel && count_out;
-  if (waves == 4) {
-    if (gat && gather_bpw() == 8) HZ_EXPAND_LAUNCH(4, true, 8);
-    else if (gat && wave_slot) HZ_EXPAND_LAUNCH(4, true, kGatherBPW, true);
-    else if (gat) HZ_EXPAND_LAUNCH(4, true, kGatherBPW);
-    else if (sel) HZ_EXPAND_LAUNCH(4, false, 1);
-    else HZ_EXPAND_LAUNCH_NOSEL(4);
-  } else {
-    if (gat && gather_bpw() == 8) HZ_EXPAND_LAUNCH(3, true, 8);
-    else if (gat) HZ_EXPAND_LAUNCH(3, true, kGatherBPW);
-    else if (sel) HZ_EXPAND_LAUNCH(3, false, 1);
-    else HZ_EXPAND_LAUNCH_NOSEL(3);
-  }
-#undef HZ_EXPAND_LAUNCH
-#undef HZ_EXPAND_LAUNCH_NOSEL
-#undef HZ_EXPAND_LAUNCH_G
+  const auto launch = [&](auto s, auto g, auto f) {
+    using F = decltype(f);
+    constexpr bool kSel = decltype(s)::value, kGather = decltype(g)::value;
+    constexpr int bpw = kGather ? kGatherBPW : 1;
+    hipLaunchKernelGGL((k_expand_backup<kSel, F::root, F::sym, kGather>), dim3((m->n + bpw - 1) / bpw),
+                       dim3(kWave * bpw), 0, m->stream, *m, mt, mt_pos, win_tag, policy, value, noise, eps, ome, testing,
+                       slot, prio, active, cpuct, board, glob, rows, count_out, count_prev, add_prev);
+  };
+  using std::false_type;
+  using std::true_type;
+  if (sel && count_out) with_form<true>(form, [&](auto f) { launch(true_type{}, true_type{}, f); });
+  else if (sel) with_form<true>(form, [&](auto f) { launch(true_type{}, false_type{}, f); });
+  else with_form<false>(form, [&](auto f) { launch(false_type{}, false_type{}, f); });
   return launch_err();
 }
 
@@ -1687,9 +1636,3 @@ int hz_mcts_leaf_ptrs(hz_mcts *m, int32_t **leaf, int32_t **leaf_gidx) {
 }
 
 }  // extern "C"
-
-#ifdef HZ_KEYCHECK
-extern "C" int hz_keycheck_counts(unsigned long long *out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_kc), sizeof(g_kc)) == hipSuccess ? 0 : 1;
-}
-#endif

@@ -1,10 +1,11 @@
 // hz_mcts.hpp — what the units of the tree search share (hz_mcts.hip: the
 // simulation; hz_mcts_report.hip: views of a finished tree; hz_mcts_carry.hip:
 // tree reuse): the kernels' argument struct, the handle, the request lists of
-// the handle's device buffers, and the device helpers more than one unit uses.
+// the handle's device buffers, the picker of a launch's kernel instantiation,
+// and the device helpers more than one unit uses.
 //
 // Everything above the HIP section compiles with a plain C++17 compiler
-// (tests/host_driver.cpp runs the request lists under ASan + UBSan without a GPU).
+// (tests/host_driver.cpp runs the request lists and the picker under ASan + UBSan without a GPU).
 #pragma once
 
 #include <cstddef>
@@ -18,7 +19,7 @@ struct hz_mcts_args {
   int32_t n, max_nodes, max_edges, hcap, max_depth;
   int32_t exact_keys;
   int32_t dedup_walk;    // hz_mcts_set_dedup_walk (tests): every sibling dedup takes the serial walk
-  int32_t gather_mode;   // hz_mcts_set_gather_encode: -1 process default (HZ_GATHER_ENCODE), 0 layered, 1 fused
+  int32_t gather_mode;   // hz_mcts_set_gather_encode: 0 layered, 1 or -1 (the default) fused
   hipStream_t stream;
   uint64_t *node_state;  // [n][max_nodes][6]
   uint64_t *node_key;    // [n][max_nodes][8] canonical key (a probe compares it whole: no key rebuilt)
@@ -164,6 +165,49 @@ bool request_forced(Bufs &o, hz_mcts_args &a) {
   o.get(a.forced_buf, n * sizeof(uint8_t), 0, (void *)a.stream);
   o.get(a.forced_cnt, n * 2 * sizeof(int32_t), 0, (void *)a.stream);
   return o.ok;
+}
+
+// ------------------------------------------------------------ the launch form
+// The root forms of the walk (select_board's template argument): PUCT, the
+// Gumbel root, or PUCT behind the forced-playout rule of hz_mcts_set_forced.
+constexpr int kRootPuct = 0, kRootGumbel = 1, kRootForced = 2;
+// Which instantiation of a tree kernel a launch takes: the walk's root form
+// and whether the leaf-symmetry code is in (with a gate off the kernels carry
+// none of its code); root -1: the gates' combination has no instantiation.
+struct LaunchForm {
+  int root;
+  bool sym;
+};
+// From the handle's gates (gumbel != nullptr, forced_k > 0, leaf_key !=
+// nullptr) and whether the launch walks (has a select).  One root form per
+// search, so the Gumbel root with forced playouts is refused; the symmetric
+// instantiations exist without the Gumbel root only; the forced rule lives in
+// the walk, so a launch without one never takes the forced form.
+inline LaunchForm pick_form(bool gumbel, bool forced, bool leaf_key, bool walk) {
+  if (gumbel && (leaf_key || forced)) return {-1, false};
+  if (gumbel) return {kRootGumbel, false};
+  return {forced && walk ? kRootForced : kRootPuct, leaf_key};
+}
+inline LaunchForm pick_form(const hz_mcts_args &a, bool walk) {
+  return pick_form(a.gumbel != nullptr, a.forced_k > 0.0, a.leaf_key != nullptr, walk);
+}
+// launch(FormOf<Root, Sym>{}) for the picked form, so a generic lambda names
+// the kernel by decltype(f)::root and ::sym.  Only what pick_form can return
+// is instantiated: no symmetric Gumbel form, the forced forms only with Walk.
+template <int Root, bool Sym>
+struct FormOf {
+  static constexpr int root = Root;
+  static constexpr bool sym = Sym;
+};
+template <bool Walk, class Launch>
+void with_form(LaunchForm f, Launch &&launch) {
+  if (f.root == kRootGumbel) launch(FormOf<kRootGumbel, false>{});
+  else if (f.root == kRootPuct && f.sym) launch(FormOf<kRootPuct, true>{});
+  else if (f.root == kRootPuct) launch(FormOf<kRootPuct, false>{});
+  else if constexpr (Walk) {
+    if (f.root == kRootForced && f.sym) launch(FormOf<kRootForced, true>{});
+    else if (f.root == kRootForced) launch(FormOf<kRootForced, false>{});
+  }
 }
 
 }  // namespace hz_tree
@@ -312,9 +356,6 @@ __device__ __forceinline__ void gumbel_sigma(const hz_mcts_args &m, int lane, in
 }
 
 // ------------------------------------------------------------ forced playouts
-// The root forms of the walk (select_board's template argument): PUCT, the
-// Gumbel root, or PUCT behind the forced-playout rule of hz_mcts_set_forced.
-constexpr int kRootPuct = 0, kRootGumbel = 1, kRootForced = 2;
 // Root edge e is forced iff N_e > 0 and (double)(N_e N_e) < (k (double)P_e)
 // (double)t: an exact integer product against two fp64 products in that order.
 __device__ __forceinline__ bool forced_edge(double k, int n, float p, int t) {

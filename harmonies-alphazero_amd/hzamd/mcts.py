@@ -24,7 +24,7 @@ no host round trip per simulation (BatchedPredictor's HIP kernels take
 count as their live-row bound).
 """
 import ctypes
-import os
+from typing import NamedTuple
 
 import torch
 
@@ -64,6 +64,14 @@ def considered_visit_table(max_considered, n_root):
             k = max(2, k // 2)
         table[m] = seq[:n_root]
     return table
+
+
+class Gate(NamedTuple):  # the handle's gates as _open() last set them (a captured simulation holds them by value)
+    budget: bool = False      # the budget gate is on
+    root_noise: bool = False  # the root-noise mask is on
+    gumbel: tuple = None      # the Gumbel gate's (max_considered, n_root, c_visit, c_scale), or None
+    leaf_sym: bool = False    # the leaf-symmetry gate is on
+    forced: tuple = None      # the forced gate's (k, mask given), or None
 
 
 class BatchedMCTS:
@@ -112,13 +120,11 @@ class BatchedMCTS:
         # children of :189-194 are not edges) are added on the device to
         # edges_total (two small launches per search, no host read)
         self.count_edges = False
-        # the next simulation's select inside each expand/backup launch
-        # (search(); HZ_FUSE_SELECT=0 runs them as separate launches)
-        self.fuse_select = os.environ.get("HZ_FUSE_SELECT", "1") != "0"
-        # ... and the next leaf batch's gather + encode too (each board that
-        # needs the network takes a row and encodes its leaf in that launch;
-        # HZ_FUSE_GATHER=0 keeps hz_mcts_gather_leaves' separate launch)
-        self.fuse_gather = os.environ.get("HZ_FUSE_GATHER", "1") != "0"
+        # the next simulation's select inside each expand/backup launch (search(); False: separate launches)
+        self.fuse_select = True
+        # ... and the next leaf batch's gather + encode too (each board that needs the network takes a row and
+        # encodes its leaf in that launch; False keeps hz_mcts_gather_leaves' separate launch)
+        self.fuse_gather = True
         self.edges_total = torch.zeros(1, dtype=torch.int64, device=d)
         # count_path: after each search, the edge levels its simulations
         # walked (the sum of the tree's edge visit counts, hz_mcts_path_edges)
@@ -135,9 +141,7 @@ class BatchedMCTS:
         # boards: only then can a row lie past them, and _finish() reads the
         # handle's error word (hz_mcts_set_row_cap)
         self._cap_risk = False
-        # (budget gate on, root-noise mask on, the Gumbel gate's settings or None, leaf-symmetry gate on, the forced
-        # gate's (k, mask given) or None), as last set by search()
-        self._gate = (False, False, None, False, None)
+        self._gate = Gate()  # as last set by _open()
         self._leaf_sym = torch.zeros(self.n, dtype=torch.uint8, device=d)  # leaf_symmetries()' report
         self._gumbel_tables = {}  # (max_considered, n_root) -> the device table (built once per shape)
         # tree reuse (advance() / search(carry=True)): advance's info rows, and
@@ -168,6 +172,12 @@ class BatchedMCTS:
         self._sync()
         nat.check(nat.lib().hz_mcts_begin(self._h, self.env.handle, nat.ptr(active)), "hz_mcts_begin")
 
+    def _per_board(self, t, dtype, name):
+        t = t.to(device=self.device, dtype=dtype).contiguous()
+        if t.shape != (self.n,):
+            raise ValueError(f"{name} of shape {tuple(t.shape)}, not ({self.n},)")
+        return t
+
     def _mask(self, mask, name="mask"):
         """A per-board mask of the masked entry points: uint8 [n] on the device."""
         if not torch.is_tensor(mask) or mask.shape != (self.n,):
@@ -190,13 +200,11 @@ class BatchedMCTS:
         order; every other board keeps its own.  The gate (the mask) must be
         on: set by the last search(budget=, root_noise=) or _set_gate()."""
         if budget is not None:
-            if not self._gate[0]:
+            if not self._gate.budget:
                 raise ValueError("set_gate_some(budget=) while the budget gate is off")
-            budget = budget.to(device=self.device, dtype=torch.int32).contiguous()
-            if budget.shape != (self.n,):
-                raise ValueError(f"budget of shape {tuple(budget.shape)}, not ({self.n},)")
+            budget = self._per_board(budget, torch.int32, "budget")
         if root_noise is not None:
-            if not self._gate[1]:
+            if not self._gate.root_noise:
                 raise ValueError("set_gate_some(root_noise=) while the root-noise mask is off")
             root_noise = self._mask(root_noise, "root_noise")
         nat.check(nat.lib().hz_mcts_set_gate_some(self._h, nat.ptr(budget), nat.ptr(root_noise),
@@ -226,9 +234,7 @@ class BatchedMCTS:
         of the handle's own buffer, rewritten by the next call.  The carry is
         taken up by the next search(carry=True) only."""
         self._sync()
-        action = action.to(device=self.device, dtype=torch.int16).contiguous()
-        if action.shape != (self.n,):
-            raise ValueError(f"action of shape {tuple(action.shape)}, not ({self.n},)")
+        action = self._per_board(action, torch.int16, "action")
         if active is not None:
             active = active.to(device=self.device, dtype=torch.uint8).contiguous()
         headroom = MAX_CHILDREN * self.num_simulations if headroom is None else int(headroom)
@@ -309,8 +315,6 @@ class BatchedMCTS:
         policy and value and no others (hz_mcts_set_row_cap); captured into a
         graph, the cap is the capture's max_rows."""
         cap = min(int(policy.shape[0]), int(value.numel()))
-        if not hasattr(nat.lib(), "hz_mcts_set_row_cap"):
-            return  # (an older A/B build named by HZ_LIB: unchecked, as it was)
         nat.check(nat.lib().hz_mcts_set_row_cap(self._h, cap), "hz_mcts_set_row_cap")
         if cap < self.n:
             self._cap_risk = True
@@ -333,8 +337,7 @@ class BatchedMCTS:
         (what a captured simulation holds of it) or None."""
         L = nat.lib()
         if gumbel is None:
-            if hasattr(L, "hz_mcts_set_gumbel"):  # (an older A/B build named by HZ_LIB has no gate to clear)
-                nat.check(L.hz_mcts_set_gumbel(self._h, None, None, 0, 0, 0.0, 0.0), "hz_mcts_set_gumbel")
+            nat.check(L.hz_mcts_set_gumbel(self._h, None, None, 0, 0, 0.0, 0.0), "hz_mcts_set_gumbel")
             return None
         gumbel = gumbel.to(device=self.device, dtype=torch.float64).contiguous()
         if gumbel.shape != (self.n, MAX_CHILDREN):
@@ -362,7 +365,7 @@ class BatchedMCTS:
         (the improved policy softmax(log P + sigma) over the root's edges, a
         zero row where there are none) and value f64 [n] (v_mix, from the
         root mover's side).  The handle's own tensors, rewritten by the next call."""
-        if self._gate[2] is None:
+        if self._gate.gumbel is None:
             raise ValueError("gumbel_result() after a search without root='gumbel'")
         r = self._report.get("gumbel")
         if r is None:
@@ -377,7 +380,7 @@ class BatchedMCTS:
         """After search(root="gumbel"): device f64 [n, 69], G + log P per root
         edge in edge order (hz_mcts_root_gumbel_scores: the values the root's
         select used; -inf where P is 0, 0.0 past the root's edges)."""
-        if self._gate[2] is None:
+        if self._gate.gumbel is None:
             raise ValueError("root_gumbel_scores() after a search without root='gumbel'")
         r = self._report.get("gumbel_scores")
         if r is None:
@@ -390,14 +393,11 @@ class BatchedMCTS:
         off), copied into the handle in stream order; returns whether it is on."""
         L = nat.lib()
         if keys is None:
-            if hasattr(L, "hz_mcts_set_leaf_symmetry"):  # (an older A/B build named by HZ_LIB has no gate to clear)
-                nat.check(L.hz_mcts_set_leaf_symmetry(self._h, None), "hz_mcts_set_leaf_symmetry")
+            nat.check(L.hz_mcts_set_leaf_symmetry(self._h, None), "hz_mcts_set_leaf_symmetry")
             return False
         if not torch.is_tensor(keys) or keys.dtype not in (torch.int64, torch.uint64):
             raise ValueError("leaf_symmetry: an int64 / uint64 tensor of one key per board (NoiseSource.leaf_symmetry)")
-        if keys.shape != (self.n,):
-            raise ValueError(f"leaf_symmetry of shape {tuple(keys.shape)}, not ({self.n},)")
-        keys = keys.to(device=self.device).contiguous()
+        keys = self._per_board(keys, keys.dtype, "leaf_symmetry")
         nat.check(L.hz_mcts_set_leaf_symmetry(self._h, nat.ptr(keys)), "hz_mcts_set_leaf_symmetry")
         return True
 
@@ -416,8 +416,7 @@ class BatchedMCTS:
         captured simulation holds of it by value, or None."""
         L = nat.lib()
         if forced is None or forced is False:
-            if hasattr(L, "hz_mcts_set_forced"):  # (an older A/B build named by HZ_LIB has no gate to clear)
-                nat.check(L.hz_mcts_set_forced(self._h, None, 0.0), "hz_mcts_set_forced")
+            nat.check(L.hz_mcts_set_forced(self._h, None, 0.0), "hz_mcts_set_forced")
             return None
         k = FORCED_K_DEFAULT if forced_k is None else float(forced_k)
         if not k > 0.0:
@@ -426,9 +425,7 @@ class BatchedMCTS:
         if forced is not True:
             if not torch.is_tensor(forced) or forced.dtype not in (torch.bool, torch.uint8):
                 raise ValueError("forced: True, or a bool / uint8 tensor of one flag per board")
-            if forced.shape != (self.n,):
-                raise ValueError(f"forced of shape {tuple(forced.shape)}, not ({self.n},)")
-            mask = forced.to(device=self.device, dtype=torch.uint8).contiguous()
+            mask = self._per_board(forced, torch.uint8, "forced")
         nat.check(L.hz_mcts_set_forced(self._h, nat.ptr(mask), k), "hz_mcts_set_forced")
         return k, mask is not None
 
@@ -439,7 +436,7 @@ class BatchedMCTS:
         search's).  A board whose forced bit was clear has its result() row, a
         board without a tree zeros.  The handle's own tensor, rewritten by the
         next call."""
-        if self._gate[4] is None:
+        if self._gate.forced is None:
             raise ValueError("pruned_visits() after a search without forced=")
         r = self._report.get("pruned")
         if r is None:
@@ -451,7 +448,7 @@ class BatchedMCTS:
         """After search(forced=) (hz_mcts_forced_counts): device int32 [n, 2],
         per board the root selections of the search under the gate and those
         the forced rule decided.  The handle's own tensor."""
-        if self._gate[4] is None:
+        if self._gate.forced is None:
             raise ValueError("forced_counts() after a search without forced=")
         r = self._report.get("forced_counts")
         if r is None:
@@ -459,27 +456,16 @@ class BatchedMCTS:
         nat.check(nat.lib().hz_mcts_forced_counts(self._h, nat.ptr(r)), "hz_mcts_forced_counts")
         return r
 
-    def _set_gate(self, budget, root_noise, gumbel=None, leaf_sym=False, forced=None):
-        """The budget gate and the root-noise mask of the search about to
-        begin (None: off), copied into the handle in stream order; gumbel:
-        the Gumbel gate's settings as _set_gumbel returned them; leaf_sym:
-        whether the leaf-symmetry gate is on (_set_leaf_symmetry); forced: the
-        forced gate's (k, mask given) as _set_forced returned it."""
+    def _set_gate(self, budget, root_noise):
+        """The budget gate and the root-noise mask of the search about to begin (None: off), in stream order."""
         L = nat.lib()
-        self._gate = (self._gate[0], self._gate[1], gumbel, leaf_sym, forced)
-        if budget is None and root_noise is None and not hasattr(L, "hz_mcts_set_budget"):
-            return  # (an older A/B build named by HZ_LIB: it has no gate to clear)
         if budget is not None:
-            budget = budget.to(device=self.device, dtype=torch.int32).contiguous()
-            if budget.shape != (self.n,):
-                raise ValueError(f"budget of shape {tuple(budget.shape)}, not ({self.n},)")
+            budget = self._per_board(budget, torch.int32, "budget")
         if root_noise is not None:
-            root_noise = root_noise.to(device=self.device, dtype=torch.uint8).contiguous()
-            if root_noise.shape != (self.n,):
-                raise ValueError(f"root_noise of shape {tuple(root_noise.shape)}, not ({self.n},)")
+            root_noise = self._per_board(root_noise, torch.uint8, "root_noise")
         nat.check(L.hz_mcts_set_budget(self._h, nat.ptr(budget)), "hz_mcts_set_budget")
         nat.check(L.hz_mcts_set_root_noise_mask(self._h, nat.ptr(root_noise)), "hz_mcts_set_root_noise_mask")
-        self._gate = (budget is not None, root_noise is not None, gumbel, leaf_sym, forced)
+        self._gate = self._gate._replace(budget=budget is not None, root_noise=root_noise is not None)
 
     def stats(self):
         nat.check(nat.lib().hz_mcts_stats(self._h, nat.ptr(self.counts)), "hz_mcts_stats")
@@ -566,12 +552,10 @@ class BatchedMCTS:
         return out
 
     # -- one full search per board -------------------------------------------
-    def _device_step(self, evaluator, cpuct, active, noise, eps, testing, max_rows=None):
-        """One simulation with a device-row evaluator: no host round trip."""
+    def _step(self, evaluator, device_rows, cpuct, active, noise, eps, testing, max_rows=None):
+        """One simulation as launches of its own (with a device-row evaluator: no host round trip)."""
         board, glob, rows, count = self.select_gather(cpuct, active)  # (adds count to eval_rows)
-        if max_rows is not None:  # the live rows are a prefix of at most max_rows
-            board, glob = board[:max_rows], glob[:max_rows]
-        policy, value = evaluator(board, glob, rows, count)
+        policy, value = self._evaluate(evaluator, device_rows, board, glob, rows, count, max_rows)
         self.expand_backup(policy, value, noise, eps, testing, gathered=True)
 
     def _capture_step(self, evaluator, cpuct, active, eps, testing, max_rows=None):
@@ -599,7 +583,7 @@ class BatchedMCTS:
         try:
             with torch.cuda.graph(g, stream=self._capture_stream):
                 self._sync()  # the handles launch on the capture stream
-                self._device_step(evaluator, cpuct, active, None, eps, testing, max_rows)
+                self._step(evaluator, True, cpuct, active, None, eps, testing, max_rows)
         finally:
             self._sync()  # back on the caller's stream, captured or not
         return g
@@ -678,6 +662,38 @@ class BatchedMCTS:
         form, with active=, budget=, root_noise=, tail=, max_rows= and
         leaf_symmetry=; not with root="gumbel" or carry=True (ValueError).  A
         search without it clears the gate."""
+        total = self.num_simulations if sims is None else int(sims)
+        if active is not None:
+            active = active.to(device=self.device, dtype=torch.uint8).contiguous()
+        self._open(total, budget, root_noise, noise, tail, carry, root, gumbel, max_considered, c_visit, c_scale,
+                   leaf_symmetry, forced, forced_k)
+        if carry:
+            self.begin_carried(active, noise, eps, testing)
+            if self.count_edges:
+                self._edges_base = self.stats()[:, 1].sum(dtype=torch.int64)
+            if self.count_path:  # the carried trees' edge visits: levels earlier searches walked
+                self._path_base = torch.zeros(1, dtype=torch.int64, device=self.device)
+                nat.check(nat.lib().hz_mcts_path_edges(self._h, nat.ptr(self._path_base)), "hz_mcts_path_edges")
+        else:
+            self.begin(active)
+        device_rows = bool(getattr(evaluator, "device_rows", False))
+        s0, tail_rows = total, max_rows
+        if tail is not None and device_rows:
+            s0 = max(0, int(tail[0]))
+            tail_rows = max(1, min(self.n if max_rows is None else int(max_rows), int(tail[1])))
+        run = (evaluator, cpuct, active, noise, eps, testing, total, max_rows, s0, tail_rows)
+        if graph and gather and device_rows and getattr(evaluator, "capturable", False) and total > 1:
+            self._run_graph(*run)
+        elif gather and total > 1 and self.n > 32 and self.fuse_select:
+            self._run_fused(*run, device_rows)
+        else:
+            self._run_layered(*run, device_rows, gather)
+        return self._finish()
+
+    def _open(self, total, budget=None, root_noise=None, noise=None, tail=None, carry=False, root=None, gumbel=None,
+              max_considered=None, c_visit=None, c_scale=None, leaf_symmetry=None, forced=None, forced_k=None):
+        """Opens a search of `total` simulations, closed by _finish(): ValueError for a combination of search()'s
+        arguments that does not exist, every gate set or cleared in stream order, the per-search counters reset."""
         if forced is False:
             forced = None
         if forced is not None and (root == "gumbel" or carry):
@@ -696,94 +712,80 @@ class BatchedMCTS:
                 raise ValueError("root='gumbel' needs gumbel= (NoiseSource.gumbel)")
             if noise is not None or root_noise is not None or budget is not None or tail is not None or carry:
                 raise ValueError("root='gumbel' does not combine with noise=, root_noise=, budget=, tail= or carry=True")
-        if active is not None:
-            active = active.to(device=self.device, dtype=torch.uint8).contiguous()
         self._sync()
-        self._set_gate(budget, root_noise, self._set_gumbel(
-            gumbel, self.num_simulations if sims is None else int(sims), max_considered, c_visit, c_scale),
-            self._set_leaf_symmetry(leaf_symmetry), self._set_forced(forced, forced_k))
+        self._gate = self._gate._replace(gumbel=self._set_gumbel(gumbel, total, max_considered, c_visit, c_scale),
+                                         leaf_sym=self._set_leaf_symmetry(leaf_symmetry),
+                                         forced=self._set_forced(forced, forced_k))
+        self._set_gate(budget, root_noise)
         self._edges_base = self._path_base = None
-        if carry:
-            self.begin_carried(active, noise, eps, testing)
-            if self.count_edges:
-                self._edges_base = self.stats()[:, 1].sum(dtype=torch.int64)
-            if self.count_path:  # the carried trees' edge visits: levels earlier searches walked
-                self._path_base = torch.zeros(1, dtype=torch.int64, device=self.device)
-                nat.check(nat.lib().hz_mcts_path_edges(self._h, nat.ptr(self._path_base)), "hz_mcts_path_edges")
-        else:
-            self.begin(active)
         self.eval_rows.zero_()
         self._cap_risk = False
-        device_rows = bool(getattr(evaluator, "device_rows", False))
-        total = self.num_simulations if sims is None else int(sims)
-        s0, tail_rows = total, max_rows
-        if tail is not None and device_rows:
-            s0 = max(0, int(tail[0]))
-            tail_rows = max(1, min(self.n if max_rows is None else int(max_rows), int(tail[1])))
-        if graph and gather and device_rows and getattr(evaluator, "capturable", False) and total > 1:
-            self._device_step(evaluator, cpuct, active, noise, eps, testing, max_rows if s0 > 0 else tail_rows)
-            # an evaluator with a graph_key (the network object and its weight
-            # generation) lets the captured simulation be kept for the next
-            # search with the same settings (the drop-in's one search per move);
-            # only without an `active` mask, whose tensor the graph would bake in
-            gk = getattr(evaluator, "graph_key", None)
-            # (a capture holds the handle by value: whether each gate and each
-            # mask, the forced gate's too, are on, and each step's row cap,
-            # belong to the key)
-            head = min(max(s0 - 1, 0), total - 1)  # replays before the tail (simulation 0 ran eagerly)
-            steps = ((max_rows, head), (tail_rows, total - 1 - head))
-            key = None if gk is None or active is not None else (
-                id(gk[0]), gk[1], float(cpuct), float(eps), bool(testing), self._gate)
-            cached = self._graph_cache
-            if key is None or cached is None or cached[0] != key:
-                cached = self._graph_cache = None
-            graphs = {} if cached is None else cached[1]
-            wanted = {rows for rows, times in steps if times}
-            if len(wanted | set(graphs)) > 4:  # (row bounds that change from search to search: keep a few)
-                for rows in set(graphs) - wanted:
-                    del graphs[rows]
-            for rows, times in steps:
-                if times and rows not in graphs:
-                    graphs[rows] = self._capture_step(evaluator, cpuct, active, eps, testing, rows)
-            if key is not None and cached is None:
-                self._graph_cache = (key, graphs, gk[0])  # holds the network: its id stays unique
-            for rows, times in steps:
-                if times and rows is not None and rows < self.n:
-                    self._cap_risk = True  # (a cached capture: no expand call of this search set it)
-                for _ in range(times):
-                    graphs[rows].replay()
-            return self._finish()
-        if gather and total > 1 and self.n > 32 and self.fuse_select:
-            # the next simulation's select rides in each expand/backup launch
-            # (and, fuse_gather, the gather + encode of its leaf batch: the
-            # two count buffers alternate, each zeroed by the launch after the
-            # one that filled it, so both are zero between searches)
-            # rows in arrival order only for an evaluator that opts in: one
-            # that maps rows to boards by position, or whose results depend on
-            # a row's place in the batch, keeps the board-order gather
-            fuse_gather = self.fuse_gather and bool(getattr(evaluator, "row_independent", False))
-            if fuse_gather:
-                self.count_b.zero_()  # (defensive: a search cut short may have left it set)
-            board, glob, rows, count = self.select_gather(cpuct, active)
-            bufs, cur = (self.count, self.count_b), 0
-            for s in range(total):
-                policy, value = self._evaluate(evaluator, device_rows, board, glob, rows, count,
-                                               max_rows if s < s0 else tail_rows)
-                if s + 1 < total:
-                    if fuse_gather:
-                        self.expand_backup_select_gather(policy, value, cpuct, active, noise, eps, testing,
-                                                         bufs[cur ^ 1], bufs[cur], add_prev=s > 0)
-                        cur ^= 1
-                        count = bufs[cur]
-                    else:
-                        self.expand_backup_select(policy, value, cpuct, active, noise, eps, testing)
-                        board, glob, rows, count = self.gather_leaves()
+
+    def _run_graph(self, evaluator, cpuct, active, noise, eps, testing, total, max_rows, s0, tail_rows):
+        """The first simulation eager, the others replays of one captured simulation (two with a tail)."""
+        self._step(evaluator, True, cpuct, active, noise, eps, testing, max_rows if s0 > 0 else tail_rows)
+        # an evaluator with a graph_key (the network object and its weight generation) lets the captured
+        # simulation be kept for the next search with the same settings (the drop-in's one search per move);
+        # only without an `active` mask, whose tensor the graph would bake in
+        gk = getattr(evaluator, "graph_key", None)
+        # (a capture holds the handle by value: whether each gate and each mask, the forced gate's too, are on,
+        # and each step's row cap, belong to the key)
+        head = min(max(s0 - 1, 0), total - 1)  # replays before the tail (simulation 0 ran eagerly)
+        steps = ((max_rows, head), (tail_rows, total - 1 - head))
+        key = None if gk is None or active is not None else (
+            id(gk[0]), gk[1], float(cpuct), float(eps), bool(testing), self._gate)
+        cached = self._graph_cache
+        if key is None or cached is None or cached[0] != key:
+            cached = self._graph_cache = None
+        graphs = {} if cached is None else cached[1]
+        wanted = {rows for rows, times in steps if times}
+        if len(wanted | set(graphs)) > 4:  # (row bounds that change from search to search: keep a few)
+            for rows in set(graphs) - wanted:
+                del graphs[rows]
+        for rows, times in steps:
+            if times and rows not in graphs:
+                graphs[rows] = self._capture_step(evaluator, cpuct, active, eps, testing, rows)
+        if key is not None and cached is None:
+            self._graph_cache = (key, graphs, gk[0])  # holds the network: its id stays unique
+        for rows, times in steps:
+            if times and rows is not None and rows < self.n:
+                self._cap_risk = True  # (a cached capture: no expand call of this search set it)
+            for _ in range(times):
+                graphs[rows].replay()
+
+    def _run_fused(self, evaluator, cpuct, active, noise, eps, testing, total, max_rows, s0, tail_rows, device_rows):
+        """The next simulation's select rides in each expand/backup launch (and, fuse_gather, the gather + encode
+        of its leaf batch: the two count buffers alternate, each zeroed by the launch after the one that filled
+        it, so both are zero between searches)."""
+        # rows in arrival order only for an evaluator that opts in: one
+        # that maps rows to boards by position, or whose results depend on
+        # a row's place in the batch, keeps the board-order gather
+        fuse_gather = self.fuse_gather and bool(getattr(evaluator, "row_independent", False))
+        if fuse_gather:
+            self.count_b.zero_()  # (defensive: a search cut short may have left it set)
+        board, glob, rows, count = self.select_gather(cpuct, active)
+        bufs, cur = (self.count, self.count_b), 0
+        for s in range(total):
+            policy, value = self._evaluate(evaluator, device_rows, board, glob, rows, count,
+                                           max_rows if s < s0 else tail_rows)
+            if s + 1 < total:
+                if fuse_gather:
+                    self.expand_backup_select_gather(policy, value, cpuct, active, noise, eps, testing,
+                                                     bufs[cur ^ 1], bufs[cur], add_prev=s > 0)
+                    cur ^= 1
+                    count = bufs[cur]
                 else:
-                    self.expand_backup(policy, value, noise, eps, testing, gathered=True)
-            if fuse_gather:  # the last batch's count: no gather call added it
-                self.eval_rows += count
-                count.zero_()
-            return self._finish()
+                    self.expand_backup_select(policy, value, cpuct, active, noise, eps, testing)
+                    board, glob, rows, count = self.gather_leaves()
+            else:
+                self.expand_backup(policy, value, noise, eps, testing, gathered=True)
+        if fuse_gather:  # the last batch's count: no gather call added it
+            self.eval_rows += count
+            count.zero_()
+
+    def _run_layered(self, evaluator, cpuct, active, noise, eps, testing, total, max_rows, s0, tail_rows, device_rows,
+                     gather):
+        """Every simulation its own launches; gather=False: one row per board."""
         for s in range(total):
             if not gather:
                 self.select(cpuct, active)
@@ -792,15 +794,11 @@ class BatchedMCTS:
                 self.eval_rows += self.n
                 self.expand_backup(policy, value, noise, eps, testing)
                 continue
-            board, glob, rows, count = self.select_gather(cpuct, active)  # (adds count to eval_rows)
-            policy, value = self._evaluate(evaluator, device_rows, board, glob, rows, count,
-                                           max_rows if s < s0 else tail_rows)
-            self.expand_backup(policy, value, noise, eps, testing, gathered=True)
-        return self._finish()
+            self._step(evaluator, device_rows, cpuct, active, noise, eps, testing, max_rows if s < s0 else tail_rows)
 
     def _evaluate(self, evaluator, device_rows, board, glob, rows, count, max_rows):
         if device_rows:
-            if max_rows is not None:
+            if max_rows is not None:  # the live rows are a prefix of at most max_rows
                 board, glob = board[:max_rows], glob[:max_rows]
             return evaluator(board, glob, rows, count)
         k = int(count.item())  # one host read per simulation
@@ -808,26 +806,26 @@ class BatchedMCTS:
             return evaluator(board[:k], glob[:k])
         return self._nil_pol, self._nil_val
 
-    def _finish(self):
-        """Root visits of the search just run, after making sure no leaf
-        evaluation of it went through a timed-out split-tower hand-off (whose
-        NaN priors would have steered PUCT silently): NativeError if one did;
-        and, where an expand call had fewer rows than boards, that no board's
-        row lay past them (the handle's error word: one read per search)."""
+    def _finish(self, trees=True):
+        """Closes what _open() opened: root visits of the search just run, after making sure no leaf evaluation of
+        it went through a timed-out split-tower hand-off (whose NaN priors would have steered PUCT silently):
+        NativeError if one did; and, where an expand call had fewer rows than boards, that no board's row lay past
+        them (the handle's error word: one read per search).  trees=False (play_async, whose trees are not one
+        search's): no counter read from the trees, no visits."""
         from .infer import check_split_timeouts
         self.eval_rows_total += self.eval_rows
-        if self.count_edges:
+        if trees and self.count_edges:
             self.edges_total += self.stats()[:, 1].sum(dtype=torch.int64)
             if self._edges_base is not None:  # a carried search: only the edges it created
                 self.edges_total -= self._edges_base
-        if self.bounded:
+        if trees and self.bounded:
             c = self.stats()  # (a board left out of this search has no nodes and keeps its last flag)
             self.limit_hits_total += ((c[:, 3] != 0) & (c[:, 0] > 0)).sum(dtype=torch.int64)
-        if self.count_path:
+        if trees and self.count_path:
             nat.check(nat.lib().hz_mcts_path_edges(self._h, nat.ptr(self.path_total)), "hz_mcts_path_edges")
             if self._path_base is not None:  # a carried search: only the levels it walked
                 self.path_total -= self._path_base
-        visits = self.result()
+        visits = self.result() if trees else None
         if self._cap_risk:
             self._cap_risk = False
             word = ctypes.c_int32(0)

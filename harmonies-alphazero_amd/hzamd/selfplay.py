@@ -627,12 +627,7 @@ class SelfPlay:
         noise, u, coin = z(torch.float64, n, MAX_CHILDREN), z(torch.float64, n), z(torch.float64, n, fill=1.0)
         budget_all = z(torch.int32, n, fill=nsims)
         step0 = self.step_counter
-        # the budget gate and the root-noise mask on, every other gate off
-        mcts._sync()
-        mcts._set_gate(budget_all, z(torch.uint8, n, fill=1), mcts._set_gumbel(None, nsims, None, None, None),
-                       mcts._set_leaf_symmetry(None), mcts._set_forced(None, None))
-        mcts.eval_rows.zero_()
-        mcts._cap_risk = False
+        mcts._open(nsims, budget_all, z(torch.uint8, n, fill=1))  # the budget gate and the root-noise mask on
         device_rows = bool(getattr(self.evaluator, "device_rows", False))
 
         def begin_turned():
@@ -694,10 +689,8 @@ class SelfPlay:
             done_at = landed(self.ASYNC_LAG)
         if done_at is None:
             done_at = landed(0)
-        mcts.eval_rows_total += mcts.eval_rows
         self.step_counter = step0 + M
-        from .infer import check_split_timeouts
-        check_split_timeouts(d)
+        mcts._finish(trees=False)
         nbad = torch.nonzero(bad).flatten().tolist()  # (the run's one wait for the device)
         if nbad:
             raise RuntimeError(f"self-play step failed on boards {nbad[:8]}")

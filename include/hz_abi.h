@@ -331,8 +331,8 @@ int hz_mcts_set_eval_counter(hz_mcts *mcts, int64_t *counter);
 int hz_mcts_set_dedup_walk(hz_mcts *mcts, int32_t on);
 /* Test / A-B switch (no reference counterpart): how hz_mcts_gather_leaves
  * runs on this handle: 1 = one k_gather_encode launch, 0 = k_gather + the
- * encoder launches (same rows, slots, count and tensors), -1 = the process
- * default (HZ_GATHER_ENCODE, fused unless it is 0). */
+ * encoder launches (same rows, slots, count and tensors), -1 = the default a
+ * new handle has (the fused launch). */
 int hz_mcts_set_gather_encode(hz_mcts *mcts, int32_t mode);
 /* expand_leaf (MCTS.py:151-218) with policy[n][143] (probabilities, as
  * ModelManager.predict returns them, model.py:81-110), root Dirichlet mix

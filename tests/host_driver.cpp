@@ -1,5 +1,5 @@
 // Stand-alone check of libhz's host layer (csrc/hz_host.hpp, its HIP-free
-// part, and the request lists of the search handle's buffers, csrc/hz_mcts.hpp): built with ASan + UBSan by tests/test_host_cpu.py and run without a
+// part, and the request lists of the search handle's buffers and its launch-form picker, csrc/hz_mcts.hpp): built with ASan + UBSan by tests/test_host_cpu.py and run without a
 // GPU.  The expected values are written out from the rules the knobs had
 // before they shared a reader; nothing here is computed by the code under test.
 #include <cstdio>
@@ -40,15 +40,10 @@ static const PickCase kPick[] = {
     {"HZ_AR_AHEAD", 0, 1, "0", "-5", {1, 0, 0, 1, 0, 0, 1}},
     {"HZ_X6_W4", 0, 1, "0", "2", {1, 0, 0, 1, 0, 0, 1}},
     {"HZ_STEM_CS4", 0, 1, "0", "2", {1, 0, 0, 1, 0, 0, 1}},
-    {"HZ_GATHER_ENCODE", 0, 1, "0", "2", {1, 0, 0, 1, 0, 0, 1}},
-    {"HZ_EXPAND_PRIO", 0, 1, "0", "7", {1, 0, 0, 1, 0, 0, 1}},
     // off unless it parses to 1
     {"HZ_X6_CS4", 1, 0, "1", "2", {0, 0, 0, 1, 0, 1, 0}},
-    {"HZ_SLOT_WAVE", 1, 0, "1", "11", {0, 0, 0, 1, 0, 1, 0}},
     // this one value or the default
     {"HZ_PIPELINE", 1, 2, "1", "3", {2, 2, 2, 1, 2, 1, 2}},
-    {"HZ_EXPAND_WAVES", 3, 4, "3", "5", {4, 4, 4, 4, 4, 3, 4}},
-    {"HZ_GATHER_BPW", 8, 16, "8", "32", {16, 16, 16, 16, 16, 8, 16}},
     {"HZ_TS_AHEAD", 12, 4, "12", "18", {4, 4, 4, 4, 4, 12, 4}},
 };
 
@@ -347,6 +342,59 @@ static void test_tree_groups() {
   delete h;
 }
 
+// ------------------------------------------------------------ the launch form
+// pick_form over every combination of the gates and of a launch with or
+// without a select, against the instantiation the three launch ladders of
+// hz_mcts.hip chose before they shared it (root form 0 PUCT, 1 Gumbel, 2
+// forced; -1: the entry point returned -1), and with_form reaching exactly
+// that instantiation
+struct FormCase {
+  bool gumbel, forced, leaf_key, walk;
+  int root;
+  bool sym;
+};
+static const FormCase kForms[16] = {
+    {false, false, false, false, 0, false}, {false, false, false, true, 0, false},
+    {false, false, true, false, 0, true},   {false, false, true, true, 0, true},
+    {false, true, false, false, 0, false},  {false, true, false, true, 2, false},
+    {false, true, true, false, 0, true},    {false, true, true, true, 2, true},
+    {true, false, false, false, 1, false},  {true, false, false, true, 1, false},
+    {true, false, true, false, -1, false},  {true, false, true, true, -1, false},
+    {true, true, false, false, -1, false},  {true, true, false, true, -1, false},
+    {true, true, true, false, -1, false},   {true, true, true, true, -1, false},
+};
+
+static void test_launch_forms() {
+  for (const FormCase &c : kForms) {
+    const hz_tree::LaunchForm f = hz_tree::pick_form(c.gumbel, c.forced, c.leaf_key, c.walk);
+    if (f.root != c.root || (c.root >= 0 && f.sym != c.sym))
+      printf("gumbel %d forced %d leaf_key %d walk %d: root %d sym %d\n", c.gumbel, c.forced, c.leaf_key, c.walk, f.root,
+             f.sym);
+    CHECK(f.root == c.root);
+    if (c.root >= 0) CHECK(f.sym == c.sym);
+    // the handle's fields read as the gates
+    hz_mcts_args a{};
+    double g = 0.0;
+    uint64_t key = 0;
+    a.gumbel = c.gumbel ? &g : nullptr;
+    a.forced_k = c.forced ? 2.0 : 0.0;
+    a.leaf_key = c.leaf_key ? &key : nullptr;
+    CHECK(hz_tree::pick_form(a, c.walk).root == c.root && (c.root < 0 || hz_tree::pick_form(a, c.walk).sym == c.sym));
+    // the dispatch: one call, with the picked form's constants; none for a refused combination
+    int calls = 0, root = -2;
+    bool sym = false;
+    const auto note = [&](auto form) {
+      calls++;
+      root = decltype(form)::root;
+      sym = decltype(form)::sym;
+    };
+    if (c.walk) hz_tree::with_form<true>(f, note);
+    else hz_tree::with_form<false>(f, note);
+    CHECK(calls == (c.root >= 0 ? 1 : 0));
+    if (c.root >= 0) CHECK(root == c.root && sym == c.sym);
+  }
+}
+
 // --------------------------------------------------------- stream windows
 struct FakeEnv {
   int32_t *pw_tag;
@@ -376,6 +424,7 @@ int main() {
   test_settings();
   test_bufs();
   test_tree_groups();
+  test_launch_forms();
   test_windows_voided();
   if (g_fail) {
     printf("host driver: %d checks failed\n", g_fail);

@@ -2,15 +2,19 @@
 
     hipcc <the Makefile's flags> -Rpass-analysis=kernel-resource-usage -c csrc/hz_mcts.hip 2> new.txt
     (the same in a checkout of the parent commit)                                            2> old.txt
-    python tools/kernel_resources.py old.txt new.txt [--root-forms]
+    python tools/kernel_resources.py old.txt new.txt [--root-forms | --retired-knobs]
 
 Prints, per kernel of old.txt, its SGPR / VGPR / AGPR / scratch / occupancy /
 spill / LDS numbers and whether new.txt has a kernel of that name with the
 same numbers, then the kernels only new.txt has.  --root-forms: new.txt's
 select kernels take the root form as an int where old.txt's took the Gumbel
 gate as a bool: form 0 is matched with false,
-form 1 with true, and form 2 has no counterpart.  Exit status 1 if a kernel of
-old.txt is missing from new.txt or differs.  Cross-compiles; needs no GPU.
+form 1 with true, and form 2 has no counterpart.  --retired-knobs: old.txt's
+k_expand_backup<Waves, Sel, Root, Sym, Gather, BPW, WaveSlot> is new.txt's
+<Sel, Root, Sym, Gather> where Waves is 4, BPW is Gather ? 16 : 1 and WaveSlot
+is false; the other forms served knobs that are gone (DESIGN.md section 10
+item 12) and are listed as retired.  Exit status 1 if a kernel of old.txt is
+missing from new.txt or differs.  Cross-compiles; needs no GPU.
 """
 import re
 import subprocess
@@ -68,10 +72,26 @@ def old_name_of(name):
     return f"{m.group(1)}<{', '.join(args)}>"
 
 
+def knob_name_of(name):
+    """old.txt's name of an expand kernel as new.txt spells it (None: a retired knob's form)."""
+    m = re.match(r"k_expand_backup<(.*)>$", name)
+    if not m:
+        return name
+    waves, sel, root, sym, gather, bpw, wave_slot = (re.sub(r"^\(\w+\)", "", a.strip()) for a in m.group(1).split(","))
+    if waves != "4" or bpw != ("16" if gather == "true" else "1") or wave_slot != "false":
+        return None
+    return f"k_expand_backup<{sel}, {root}, {sym}, {gather}>"
+
+
 def main(argv):
     root_forms = "--root-forms" in argv
     paths = [a for a in argv if not a.startswith("--")]
     old, new = parse(paths[0]), parse(paths[1])
+    retired = {}
+    if "--retired-knobs" in argv:
+        named = {name: knob_name_of(name) for name in old}
+        retired = {name: row for name, row in old.items() if named[name] is None}
+        old = {named[name]: row for name, row in old.items() if named[name] is not None}
     by_old, added = {}, []
     for name, row in new.items():
         was = old_name_of(name) if root_forms else name
@@ -87,8 +107,10 @@ def main(argv):
         verdict = "missing" if got is None else ("same" if got[1] == row else "DIFFERS " + "/".join(got[1]))
         bad += verdict != "same"
         print(f"| `{name}` | " + " | ".join(row) + f" | {verdict} |")
-    print(f"\n{len(old)} kernels in {paths[0]}, {len(new)} in {paths[1]}; {len(old) - bad} with the same numbers; "
-          f"{len(added)} new:")
+    for name, row in retired.items():
+        print(f"| `{name}` | " + " | ".join(row) + " | retired |")
+    print(f"\n{len(old) + len(retired)} kernels in {paths[0]}, {len(new)} in {paths[1]}; {len(old) - bad} with the same "
+          f"numbers; {len(retired)} retired; {len(added)} new:")
     for name in added:
         print(f"  {name}: " + ", ".join(f"{f} {v}" for f, v in zip(FIELDS, new[name])))
     return 1 if bad else 0

@@ -3,7 +3,7 @@
 set -e
 O=gpurun_out/${1:-v9}; mkdir -p $O
 R=$GRAFT_REPO_ROOT
-timeout -k 10 200 python tools/kc_search.py > $O/kc.json 2>&1
+timeout -k 10 200 python tools/key_check.py > $O/kc.json 2>&1
 HZ_LIB=tools/libhz_diag.so timeout -k 10 200 python tools/expand_phases.py 200 6 > $O/phases.json 2> $O/phases.err
 cd /tmp && export TMPDIR=/tmp
 for i in 1 2; do
